@@ -9,6 +9,10 @@ A "step" is one forward() of the hot path over one synthetic utterance batch alr
 (BASELINE.json config 2: batch 16, phoneme_len 128, mel_len ~1024, d_model 256, 4+4 FFT layers).  With N > 1
 every rank runs its own 16-utterance shard (config 3 = 128 utterances over 8 GPUs; weak scaling, no data-path
 collective; weights replicated by ONE RCCL broadcast before the timed region).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds every secondary leg after the timed steps
+(per-kernel timing pass, pipelined and sustained legs, latency, variable-length batches, the other BASELINE configs, the CPU
+baseline and the oracle check).  `--dump-outputs DIR` writes the arrays the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -49,6 +53,36 @@ HBM_MEASURED_GBS = 6400.0
 # SURVEY.md §8(d) algorithmic bytes per valid frame (weights once per forward + every sub-layer boundary tensor once each way)
 ALGORITHMIC_KB_PER_FRAME = {"cfg1_single": 190.0, "cfg2_b16": 77.0, "cfg3_b128_sharded": 77.0, "cfg4_d512": 174.0,
                             "cfg5_longform": 70.0, "cfg5_longform_gaussian": 70.0}
+# --dump-outputs: the forward's 12-tuple (model/fastspeech2_align.py:87-100) by position, without its two trailing Nones
+OUTPUT_NAMES = ("output", "postnet_output", "p_predictions", "e_predictions", "log_d_predictions", "d_rounded", "src_masks",
+                "mel_masks", "src_lens", "mel_lens")
+DUMP_CAP_BYTES = 64 << 20
+
+
+def write_outputs(out, dirname, cap_bytes=DUMP_CAP_BYTES):
+    """Every array of one forward's return as <dirname>/<name>.npy: float32 as it is, masks as float32 0 / 1, integers (lengths)
+    as float64, which holds them exactly.  Every array is batch-major; when they hold more than `cap_bytes` in all, the same
+    seeded sample of utterances is taken from each, and its positions in the batch are written as sample_index.npy.
+    Returns the names written."""
+    arrays = {}
+    for name, t in zip(OUTPUT_NAMES, out):
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype == np.bool_ else np.float64)
+        arrays[name] = a
+    B = int(arrays["output"].shape[0])
+    total = sum(a.nbytes for a in arrays.values())
+    if total > cap_bytes:
+        per_utt = total // B + 8  # (+ its float64 entry in sample_index)
+        idx = np.sort(np.random.RandomState(0).choice(B, max(1, cap_bytes // per_utt), replace=False))
+        arrays = {n: a[idx] for n, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(dirname, n + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def pci_bus_id(dev_index: int):
@@ -269,9 +303,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="cfg2_b16", help="cfg2_b16 | cfg4_d512 | cfg5_longform | cfg5_longform_gaussian | cfg1_single")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary leg: per-kernel timing pass, pipelined and sustained legs, "
+                         "latency, variable-length batches, the other BASELINE configs, CPU baseline and oracle check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64; rank 0's shard; "
+                         "a seeded sample of utterances beyond 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="profiling runs: only warm-up + timed steps (no latency leg, no pipelined leg, no CPU baseline), so that a "
+                    help="profiling runs: only warm-up + timed steps, even with --full (what a plain run does), so that a "
                          "kernel trace holds exactly (warmup + steps) forwards of the workload")
     ap.add_argument("--ragged", action="store_true", help="ragged utterance lengths instead of the uniform BASELINE batch (phase 2 then runs on packed rows; NS_PACKED=0 keeps the padded grid)")
     ap.add_argument("--host-lens", action="store_true", help="hand src_lens to forward() as a HOST tensor (what a caller that collates on the host holds): "
@@ -284,11 +324,12 @@ def main():
                          "phoneme counts; default: contiguous for the uniform BASELINE batch, phonemes with --ragged")
     ap.add_argument("--sustained-s", type=float, default=10.0,
                     help="sustained leg after the timed region: back-to-back forwards for this many seconds or 2000 steps, whichever "
-                         "comes first (0 = off; skipped with --no-extras)")
+                         "comes first (0 = off; --full only, skipped with --no-extras)")
     ap.add_argument("--matmul", choices=["fp32", "bf16x3"], default="fp32",
                     help="EXPERIMENT, never the headline: bf16x3 runs the large decoder-FFN / PostNet contractions from an exact "
                          "3-way bf16 split on the bf16 matrix cores (fp32-sized error, different bits); the line is labelled")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
 
@@ -419,10 +460,12 @@ def main():
         step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)) if marks else None
         k_ms, k_flops, k_launches = model.read_profile(0)
         model.profile_dominant_kernel(False)
+        if args.dump_outputs and rank == 0:
+            write_outputs(out, args.dump_outputs)
         # the next two heaviest kernels (attention, PostNet 512->512) in a pass of their own, outside the timed region: a
         # timed launch costs its stream ~5 us (include/nar_fs2.h), and seven more of them per forward were 1 % of the step
         by_kernel = {}
-        if not args.no_extras:
+        if extras:
             model.profile_slots((1, 2))
             for _ in range(min(args.steps, 5)):
                 step()
@@ -434,7 +477,7 @@ def main():
         # batching.synthesize(streams=2) does for consecutive batches), so the small-grid phase 1 and the host read of
         # step i+1 overlap the chip-filling phase 2 of step i.  Reported beside the headline value, never as it.
         pipelined = None
-        if streams is None and args.gpus == 1 and not args.no_extras:
+        if streams is None and args.gpus == 1 and extras:
             ps = [torch.cuda.Stream(device=dev) for _ in range(2)]
             for i in range(2):
                 with torch.cuda.stream(ps[i]):
@@ -550,7 +593,7 @@ def main():
 
 
     sustained = None
-    if args.sustained_s > 0 and not args.no_extras and streams is None:
+    if args.sustained_s > 0 and extras and streams is None:
         if dist is None:
             try:  # (single process: a failure of this secondary leg must not cost the run its headline line)
                 sustained = run_sustained()
@@ -689,7 +732,7 @@ def main():
     if step_ms:
         res["step_ms_spread"] = {"p50": round(step_ms[len(step_ms) // 2], 3), "min": round(step_ms[0], 3),
                                  "max": round(step_ms[-1], 3), "n": len(step_ms)}
-    if args.gpus == 1 and not args.no_extras:
+    if args.gpus == 1 and extras:
         # p50 per-utterance latency (the second half of BASELINE.json's metric), config 1: B=1, L=100
         c1, B1, L1, f1 = wl.WORKLOADS["cfg1_single"]
         if c1 == cfg_name and f1 == fpp:  # same architecture AND same synthetic duration bias (mel_len 788)
@@ -744,7 +787,7 @@ def main():
                 "bit_identical_to_sync_path": same,
                 "note": "200 B=1 forwards round-robin over 1 and 8 streams, one host thread (8: the HIP runtime spreads streams over 4 hardware queues, and 4 streams may share 2 of them — profiles/r04_multi_stream_small.txt); tools/multi_stream_small.py has B=1,2,4 x 1..8 streams"}
 
-    if args.gpus == 1 and not args.no_extras and not b3:
+    if args.gpus == 1 and extras and not b3:
         # Variable-length batches (BASELINE.json config 5: "variable-length masking stress"): the same model on a RAGGED batch of
         # this workload's shape — phoneme counts uniform in [L/8, L], one utterance at L — with phase 2 on packed rows
         # (include/nar_fs2.h ns_forward_mel_packed, the synchronous path's default) and on the reference's padded [B, T] grid.
@@ -796,7 +839,7 @@ def main():
         res["variable_length"] = vl
 
 
-    if args.gpus == 1 and not args.no_extras and not b3 and args.workload == "cfg2_b16" and args.batch == 0 and not args.ragged:
+    if args.gpus == 1 and extras and not b3 and args.workload == "cfg2_b16" and args.batch == 0 and not args.ragged:
         # The other BASELINE configs on the driver's clock (config 1 = single utterance, 4 = d_model 512 / 6+6 layers / B = 64,
         # 5 = long-form B = 8 with both length regulators): secondary figures beside the headline workload, each with its own
         # oracle check on a slice.  A failure of one leg is recorded, never fatal to the line.
@@ -820,7 +863,7 @@ def main():
             torch.cuda.empty_cache()
         res["other_configs"] = others
 
-    if args.gpus == 1 and not args.no_cpu_baseline and not args.no_extras:
+    if args.gpus == 1 and not args.no_cpu_baseline and extras:
         # CPU baseline beside it: the oracle (a torch-CPU restatement of the reference forward, "port") on this box's
         # host cores, same workload, bounded to ~10-30 s.
         from oracle import fs2_oracle as orc

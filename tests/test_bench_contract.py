@@ -1,11 +1,12 @@
 """bench.py's output contract (the driver parses the LAST stdout line as JSON): every required key with the right
-type, one short run on the GPU box, CPU-baseline leg included; the plain `python bench.py --gpus N` form launches
-its own ranks."""
+type, one short `--full` run on the GPU box, CPU-baseline leg included; a plain run holds the headline only and can dump
+its outputs; the plain `python bench.py --gpus N` form launches its own ranks."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +25,7 @@ def _run(args, env=None, timeout=900):
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
     assert d["metric"] == "mel_frames_per_sec" and d["unit"] == "frames/s"
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -105,9 +106,38 @@ def test_bench_json_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times --steps forwards and prints the headline without the secondary legs; --dump-outputs writes
+    the arrays of its last timed step, and a second process with the same arguments writes the same bits (seeded inputs)."""
+    runs = []
+    for tag in ("a", "b"):
+        d = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / tag)])
+        runs.append((d, {f[:-4]: np.load(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)}))
+    d, arr = runs[0]
+    assert d["metric"] == "mel_frames_per_sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["valid_frames_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for leg in ("sustained", "burst", "pipelined", "latency", "latency_capacity_mode", "variable_length", "other_configs",
+                "cpu_baseline", "check_vs_oracle"):
+        assert leg not in d, leg
+    assert set(d["roofline_by_kernel"]) == {"ffn_w1"} and d["roofline"]["launches"] == 4
+    assert set(arr) == {"output", "postnet_output", "p_predictions", "e_predictions", "log_d_predictions", "d_rounded", "src_masks",
+                        "mel_masks", "src_lens", "mel_lens"}
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values()) and sum(a.nbytes for a in arr.values()) <= 64 << 20
+    T_pad = d["roofline"]["geometry"]["rows"] // 16
+    assert arr["postnet_output"].shape == (16, T_pad, 80) and arr["mel_masks"].shape == (16, T_pad)
+    assert arr["mel_lens"].sum() == d["config"]["valid_frames_per_step"] and arr["mel_lens"].max() == T_pad
+    assert (arr["mel_masks"] == 0).sum() == d["config"]["valid_frames_per_step"]
+    assert np.isfinite(arr["postnet_output"]).all()
+    for name, a in arr.items():
+        assert np.array_equal(a, runs[1][1][name]), name
+
+
+@pytest.mark.gpu
 def test_bench_other_workload_has_no_stale_traffic():
     """roofline.traffic is a measurement of ONE launch geometry; a different workload must report null, not config 2's number."""
-    d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "cfg1_single", "--no-cpu-baseline", "--sustained-s", "1"])
+    d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "cfg1_single", "--no-cpu-baseline", "--sustained-s", "1",
+              "--full"])
     assert d["roofline"]["traffic"] is None and d["roofline"]["geometry"]["rows"] != 16160
 
 
@@ -118,7 +148,7 @@ def test_bench_plain_command_launches_its_own_ranks():
     env = {"NS_BENCH_ONE_GPU": "1"}
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         os.environ.pop(k, None)
-    d = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sustained-s", "1"], env=env)
+    d = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sustained-s", "1", "--full"], env=env)
     assert d["sustained"]["steps"] >= 50 and d["init"]["weights_broadcast_ms"] is not None  # the sustained leg runs on every rank, fenced
     assert d["n_gpus"] == 2 and d["world_size_seen_by_rccl"] == 2 and d["one_gpu_rig"] is True and d["backend"] == "gloo"
     assert [x["rank"] for x in d["devices"]] == [0, 1] and all(x["device"] == "cuda:0" for x in d["devices"])
@@ -256,3 +286,37 @@ def test_self_launch_command_line(monkeypatch):
     assert c[c.index("--master-addr") + 1] == "127.0.0.1" and int(c[c.index("--master-port") + 1]) > 0
     assert c[-4:] == ["--gpus", "4", "--steps", "3"] and c[-5].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_write_outputs_float_dtypes_and_seeded_sample(tmp_path):
+    """CPU: --dump-outputs' writer keeps float32, stores masks as float32 and integers as float64, skips the tuple's Nones, and
+    over its size cap keeps the same seeded sample of utterances in every array (positions in sample_index.npy)."""
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B, L, T = 12, 7, 30
+    g = torch.Generator().manual_seed(3)
+    mel_lens = torch.randint(1, T + 1, (B,), generator=g)
+    mel_masks = torch.arange(T)[None, :] >= mel_lens[:, None]
+    f = lambda *shape: torch.randn(*shape, generator=g)  # noqa: E731
+    out = (f(B, T, 80), f(B, T, 80), f(B, L), f(B, L), f(B, L), f(B, L).round(), torch.zeros(B, L, dtype=torch.bool), mel_masks,
+           torch.full((B,), L), mel_lens, None, None)
+    names = bench.write_outputs(out, str(tmp_path / "all"))
+    assert names == sorted(bench.OUTPUT_NAMES)
+    a = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in names}
+    assert a["postnet_output"].dtype == np.float32 and np.array_equal(a["postnet_output"], out[1].numpy())
+    assert a["mel_masks"].dtype == np.float32 and np.array_equal(a["mel_masks"], mel_masks.numpy().astype(np.float32))
+    assert a["mel_lens"].dtype == np.float64 and np.array_equal(a["mel_lens"], mel_lens.numpy().astype(np.float64))
+    cap = sum(x.nbytes for x in a.values()) // 3
+    for tag in ("s1", "s2"):
+        assert "sample_index" in bench.write_outputs(out, str(tmp_path / tag), cap_bytes=cap)
+    s = {n: np.load(tmp_path / "s1" / f"{n}.npy") for n in names + ["sample_index"]}
+    idx = s["sample_index"].astype(np.int64)
+    assert 1 <= len(idx) < B and np.all(np.diff(idx) > 0) and sum(x.nbytes for x in s.values()) <= cap
+    for n in names:
+        assert np.array_equal(s[n], a[n][idx]), n
+        assert np.array_equal(s[n], np.load(tmp_path / "s2" / f"{n}.npy")), n

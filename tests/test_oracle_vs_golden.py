@@ -10,6 +10,16 @@ from tests.util import load_golden, weights_for
 TOL = 2e-5  # oracle vs reference: same torch CPU kernels, differences only from op grouping
 
 
+@pytest.fixture(autouse=True, scope="module")
+def _fixture_threads():
+    """The fixtures were generated with 8 torch threads (tests/golden/make_golden.py), and the CPU kernels split their sums by
+    thread count: run with the same count whatever the host's OMP_NUM_THREADS or core count, then restore it."""
+    keep = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(keep)
+
+
 def _run(meta, z, texts_key="texts"):
     cfg, sd = weights_for(meta)
     w = orc.to_torch_weights(sd)

@@ -15,7 +15,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 
-python "$ROOT/bench.py" > "$OUT/${R}_bench.log" 2>&1
+python "$ROOT/bench.py" --full > "$OUT/${R}_bench.log" 2>&1
 tail -1 "$OUT/${R}_bench.log" > "$OUT/${R}_bench.json"
 
 for WL in cfg2_b16 cfg1_single cfg4_d512 cfg5_longform cfg5_longform_gaussian; do
@@ -64,7 +64,7 @@ BENCH="python $ROOT/bench.py --workload cfg1_single --steps 5 --warmup 2 --no-ex
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/${R}_fetch_cfg1_single" -o t -- $BENCH > "$OUT/${R}_fetch_cfg1_single.log" 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/${R}_write_cfg1_single" -o t -- $BENCH > "$OUT/${R}_write_cfg1_single.log" 2>&1
 # the opt-in bf16x3 mode, for the record (never the headline)
-python "$ROOT/bench.py" --matmul bf16x3 --no-cpu-baseline > "$OUT/${R}_bench_bf16x3.log" 2>&1
+python "$ROOT/bench.py" --full --matmul bf16x3 --no-cpu-baseline > "$OUT/${R}_bench_bf16x3.log" 2>&1
 tail -1 "$OUT/${R}_bench_bf16x3.log" > "$OUT/${R}_bench_bf16x3.json"
 rocprofv3 --kernel-trace --stats --output-format rocpd csv -d "$OUT/${R}_trace_bf16x3" -o t -- python $ROOT/bench.py --matmul bf16x3 --steps 5 --warmup 2 --no-extras > "$OUT/${R}_trace_bf16x3.log" 2>&1
 # the long randomized parity run (the -m gpu suite holds a time-boxed slice of it: tests/test_gpu_stress.py)

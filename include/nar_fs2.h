@@ -60,7 +60,15 @@ typedef struct ns_config {
                                convolutions (downstream of every discrete duration / bucket decision; only launches large
                                enough to fill the chip with 64..256-row tiles, smaller ones stay fp32) run from an exact
                                3-way bf16 split of both operands on the bf16 matrix cores, 6 products, fp32 accumulation:
-                               fp32-sized error, different bits, ~1.8x faster on those layers (csrc/gemm_bf16x3.hip) */
+                               fp32-sized error, different bits, ~1.8x faster on those layers (csrc/gemm_bf16x3.hip);
+                               2 = OPT-IN "bf16": every contraction from the decoder input through the PostNet output
+                               (decoder QKV, Q K^T, P V, fc, FFN w_1 / w_2, mel_linear, all five PostNet convolutions) takes
+                               both operands rounded to bf16 (nearest even) and accumulates in fp32 on the bf16 matrix cores,
+                               at every launch size; bias, activations, residuals, LayerNorm, softmax stay fp32.  Everything
+                               upstream (encoder, durations, length regulator, pitch / energy) is the exact fp32 path, so
+                               durations, frame counts, masks and predictions are bit-identical to mode 0; mel deviates from
+                               the fp32 reference by ~1e-2 max / ~1e-3 mean (csrc/gemm_bf16.hip, csrc/attention.hip).
+                               Adds one bf16 plane per covered weight to the arena.  Any other value is rejected. */
   int32_t row_epilogue;     /* 0 = the default: on small grids LayerNorm / the predictor tail / attention's key-range merge run as
                                TICKETED last-arriver epilogues inside the producing launch (csrc/gemm_conv.hip TICKET,
                                csrc/attention.hip); 1 = "two_launch": the same row functions as separate launches, no ticket is

@@ -28,9 +28,11 @@ static int fail(const std::string& s) { g_err = s; return 1; }
 
 namespace {
 
-struct LayerW { size_t qkv_w, qkv_b, fc_w, fc_b, ln1_g, ln1_b, w1, w1_b, w2, w2_b, ln2_g, ln2_b, qkv_b3, fc_b3, w1_b3, w2_b3; };  // *_b3: bf16x3 planes or NO_B3
+struct LayerW {  // *_b3: bf16x3 planes or NO_B3; *_bf: the "bf16" mode's one rounded plane or NO_B3
+  size_t qkv_w, qkv_b, fc_w, fc_b, ln1_g, ln1_b, w1, w1_b, w2, w2_b, ln2_g, ln2_b, qkv_b3, fc_b3, w1_b3, w2_b3, qkv_bf, fc_bf, w1_bf, w2_bf;
+};
 struct PredW { size_t c1, c1_b, ln1_g, ln1_b, c2, c2_b, ln2_g, ln2_b, lin_w, lin_b; int cin; };
-struct PostW { size_t w, b, w_b3; int cin, cout; };
+struct PostW { size_t w, b, w_b3, w_bf; int cin, cout; };
 constexpr size_t NO_B3 = (size_t)-1;
 
 struct Arena {
@@ -48,6 +50,7 @@ struct ns_model {
   PredW pred[3];
   size_t hdr;  // arena header: magic, layout version, arena size, config hash (arena_header below)
   size_t emb, enc_pos, dec_pos, pitch_bins, energy_bins, pitch_emb, energy_emb, mel_w, mel_b;
+  size_t mel_bf;                   // "bf16" mode: mel_linear's rounded plane (else NO_B3)
   size_t pn_in, pn_hid, pn_const;  // derived at ns_finalize_weights: the PostNet over an all-padding utterance (packed rows, forward_mel)
   size_t pos_long;                 // derived at ns_finalize_weights: the sinusoid table regenerated for POS_LONG_ROWS positions (position_rows)
   std::vector<PostW> post;
@@ -126,12 +129,19 @@ static void plan_stack(ns_model* m, const char* prefix, int n_layer, int d, std:
     L.ln2_g = m->ar.take(d); L.ln2_b = m->ar.take(d);
     // opt-in bf16x3 mode: three bf16 planes of the (packed) k=9 weights of the DECODER stack — 1.5x their fp32 size
     // (decoder stack only: everything upstream of the duration / pitch / energy decisions stays exact fp32)
-    const bool b3 = c.matmul_bf16x3 && decoder;
+    const bool b3 = c.matmul_bf16x3 == 1 && decoder;
     auto planes = [&](size_t n) { return b3 ? m->ar.take((3 * n + 1) / 2) : NO_B3; };
     L.qkv_b3 = planes((size_t)3 * d * d);
     L.fc_b3 = planes((size_t)d * d);
     L.w1_b3 = planes((size_t)c.d_inner * c.ffn_k1 * d);
     L.w2_b3 = planes((size_t)d * c.ffn_k2 * c.d_inner);
+    // opt-in bf16 mode: ONE plane per decoder weight, rounded to nearest even (gemm_bf16.hip layout: channels padded to 32)
+    const bool bf = c.matmul_bf16x3 == 2 && decoder;
+    auto plane = [&](int n, int kw, int cin) { return bf ? m->ar.take((bf16_plane_elems(n, kw, cin) + 1) / 2) : NO_B3; };
+    L.qkv_bf = plane(3 * d, 1, d);
+    L.fc_bf = plane(d, 1, d);
+    L.w1_bf = plane(c.d_inner, c.ffn_k1, d);
+    L.w2_bf = plane(d, c.ffn_k2, c.d_inner);
     out.push_back(L);
   }
 }
@@ -153,7 +163,7 @@ extern "C" int ns_create(const ns_config* cfg, ns_model** out) {
   if (!(c.ffn_k1 & 1) || !(c.ffn_k2 & 1) || !(c.vp_kernel & 1) || !(c.postnet_k & 1))
     return fail("ns_create: kernel sizes must be odd");
   if (c.length_regulator != 0 && c.length_regulator != 1) return fail("ns_create: length_regulator must be 0 (hard) or 1 (gaussian)");
-  if (c.matmul_bf16x3 != 0 && c.matmul_bf16x3 != 1) return fail("ns_create: matmul_bf16x3 must be 0 (fp32) or 1 (bf16x3)");
+  if (c.matmul_bf16x3 < 0 || c.matmul_bf16x3 > 2) return fail("ns_create: matmul_bf16x3 must be 0 (fp32), 1 (bf16x3) or 2 (bf16)");
   if (c.row_epilogue != 0 && c.row_epilogue != 1) return fail("ns_create: row_epilogue must be 0 (fused) or 1 (two_launch)");
   if (c.phase1_packing < 0 || c.phase1_packing > 2) return fail("ns_create: phase1_packing must be 0 (auto), 1 (always) or 2 (never)");
   if (c.vp_kernel != 3) return fail("ns_create: variance predictor conv1d_2 hard-codes padding=1 (model/modules.py:267); kernel_size must be 3");
@@ -199,6 +209,7 @@ extern "C" int ns_create(const ns_config* cfg, ns_model** out) {
   expect(m, "mel_linear.weight", {c.n_mel, c.d_dec});
   expect(m, "mel_linear.bias", {c.n_mel});
   m->mel_w = m->ar.take((size_t)c.n_mel * c.d_dec); m->mel_b = m->ar.take(c.n_mel);
+  m->mel_bf = c.matmul_bf16x3 == 2 ? m->ar.take((bf16_plane_elems(c.n_mel, 1, c.d_dec) + 1) / 2) : NO_B3;
   for (int i = 0; i < c.postnet_n; ++i) {
     const int cin = i == 0 ? c.n_mel : c.postnet_dim, cout = i == c.postnet_n - 1 ? c.n_mel : c.postnet_dim;
     std::string p = "postnet.convolutions." + std::to_string(i);
@@ -207,7 +218,8 @@ extern "C" int ns_create(const ns_config* cfg, ns_model** out) {
     for (const char* s : {"weight", "bias", "running_mean", "running_var"}) expect(m, p + ".1." + s, {cout});
     PostW w; w.cin = cin; w.cout = cout;
     w.w = m->ar.take((size_t)cout * c.postnet_k * cin); w.b = m->ar.take(cout);
-    w.w_b3 = (c.matmul_bf16x3 && cin == c.postnet_dim && cout == c.postnet_dim) ? m->ar.take(((size_t)3 * cout * c.postnet_k * cin + 1) / 2) : NO_B3;
+    w.w_b3 = (c.matmul_bf16x3 == 1 && cin == c.postnet_dim && cout == c.postnet_dim) ? m->ar.take(((size_t)3 * cout * c.postnet_k * cin + 1) / 2) : NO_B3;
+    w.w_bf = c.matmul_bf16x3 == 2 ? m->ar.take((bf16_plane_elems(cout, c.postnet_k, cin) + 1) / 2) : NO_B3;  // all five layers
     m->post.push_back(w);
   }
   // PostNet constants for packed rows (forward_mel): input, ping-pong scratch and output of one PostNet run over
@@ -371,6 +383,14 @@ extern "C" int ns_finalize_weights(ns_model* m, void* stream) {
       split(L.fc_w, L.fc_b3, (size_t)d * d);
       split(L.w1, L.w1_b3, (size_t)c.d_inner * c.ffn_k1 * d);
       split(L.w2, L.w2_b3, (size_t)d * c.ffn_k2 * c.d_inner);
+      // opt-in bf16 mode: the same packed fp32 values, rounded once
+      auto round_bf = [&](size_t src, size_t dst, int n, int kw, int cin) {
+        if (dst != NO_B3) round_weights_bf16(&img[src], n, kw, cin, reinterpret_cast<unsigned short*>(&img[dst]));
+      };
+      round_bf(L.qkv_w, L.qkv_bf, 3 * d, 1, d);
+      round_bf(L.fc_w, L.fc_bf, d, 1, d);
+      round_bf(L.w1, L.w1_bf, c.d_inner, c.ffn_k1, d);
+      round_bf(L.w2, L.w2_bf, d, c.ffn_k2, c.d_inner);
     }
   };
   do_stack("txt_encoder", m->enc, c.d_enc);
@@ -390,6 +410,7 @@ extern "C" int ns_finalize_weights(ns_model* m, void* stream) {
   cp(m->pitch_bins, "variance_adaptor.pitch_bins"); cp(m->energy_bins, "variance_adaptor.energy_bins");
   cp(m->pitch_emb, "variance_adaptor.pitch_embedding.weight"); cp(m->energy_emb, "variance_adaptor.energy_embedding.weight");
   cp(m->mel_w, "mel_linear.weight"); cp(m->mel_b, "mel_linear.bias");
+  if (m->mel_bf != NO_B3) round_weights_bf16(&img[m->mel_w], c.n_mel, 1, c.d_dec, reinterpret_cast<unsigned short*>(&img[m->mel_bf]));
 
   // PostNet: fold eval-mode BatchNorm1d (running stats, eps 1e-5) into the conv (transformer/Layers.py:120-167)
   for (size_t i = 0; i < m->post.size(); ++i) {
@@ -408,6 +429,8 @@ extern "C" int ns_finalize_weights(ns_model* m, void* stream) {
       unsigned short* pl = reinterpret_cast<unsigned short*>(&img[w.w_b3]);
       split_weights_b3(&img[w.w], n, pl, pl + n, pl + 2 * n);
     }
+    // bf16 mode: rounded after the fp64 BatchNorm fold (the plane holds exactly the fp32 weights the fp32 path uses, rounded)
+    if (w.w_bf != NO_B3) round_weights_bf16(&img[w.w], w.cout, c.postnet_k, w.cin, reinterpret_cast<unsigned short*>(&img[w.w_bf]));
   }
   hipStream_t st = (hipStream_t)stream;
   NS_HIP(hipMemcpyAsync(m->arena, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, st));
@@ -518,7 +541,7 @@ static int rows_of(const Scratch& sc, int B, int S) { return sc.pk ? sc.pk->Mp :
 
 static int gemm(const Scratch& sc, const float* X, int ldx, const float* W, const float* bias, const float* resid, int ldr, float* Y, int ldy,
                 int M, int N, int Cin, int KW, int S, int act, hipStream_t st, const RowEpilogue* epi = nullptr, int epi_mode = EPI_NONE,
-                const unsigned short* Wb3 = nullptr, const LaunchTiming* tm = nullptr) {
+                const unsigned short* Wb3 = nullptr, const LaunchTiming* tm = nullptr, const unsigned short* Wbf = nullptr) {
   ConvGemm p;
   memset(&p, 0, sizeof(p));
   p.X = X; p.ldx = ldx; p.W = W; p.bias = bias; p.resid = resid; p.ldr = ldr; p.Y = Y; p.ldy = ldy;
@@ -526,6 +549,16 @@ static int gemm(const Scratch& sc, const float* X, int ldx, const float* W, cons
   p.epi = epi ? epi_mode : EPI_NONE;
   if (epi) p.e = *epi;
   if (sc.pk) { p.rm = sc.pk->rm; p.e.row_b = sc.pk->rm.row_b; p.e.row_t = sc.pk->rm.row_t; }
+  // opt-in bf16 mode: this weight has a rounded plane — the bf16 contraction at every launch size (no fp32 fallback)
+  if (Wbf) {
+    if (p.epi != EPI_NONE && p.epi != EPI_LN) return fail("gemm: the bf16 path has no predictor-tail epilogue");
+    p.Wbf = Wbf;
+    p.e.ticket = nullptr; p.e.y_out = nullptr;
+    if (tm && tm->start) NS_HIP(hipEventRecord(tm->start, st));
+    NS_HIP(launch_conv_gemm_bf16(p, st));
+    if (tm && tm->stop) NS_HIP(hipEventRecord(tm->stop, st));
+    return 0;
+  }
   // opt-in bf16x3 planes exist for this weight AND the launch is large enough for the 128-row tiles: split-bf16 matrix cores
   if (Wb3 && conv_gemm_b3_ok(M, N, Cin, KW, p.epi)) {
     p.Wb3 = Wb3;
@@ -553,10 +586,17 @@ static bool fuse_row_epilogue(int M, int N, int Cin) {
 // or when the phase's ticket block is spent.
 static int gemm_ln(const float* X, int ldx, const float* W, const float* bias, const float* resid, float* tmp, float* Y,
                    int M, int N, int Cin, int KW, int S, int act, const float* g, const float* b, const long long* lens,
-                   Scratch& sc, hipStream_t st, const unsigned short* Wb3 = nullptr) {
+                   Scratch& sc, hipStream_t st, const unsigned short* Wb3 = nullptr, const unsigned short* Wbf = nullptr) {
   RowEpilogue e;
   memset(&e, 0, sizeof(e));
   e.ln_g = g; e.ln_b = b; e.lens = lens;
+  if (Wbf) {  // bf16 mode: the full-row tile on large launches, else the plain bf16 GEMM and k_layernorm (same bits either way)
+    if (conv_gemm_bf16_ok(M, N, Cin, KW, EPI_LN))
+      return gemm(sc, X, ldx, W, bias, resid, N, Y, N, M, N, Cin, KW, S, act, st, &e, EPI_LN, nullptr, nullptr, Wbf);
+    NS_TRY(gemm(sc, X, ldx, W, bias, resid, N, tmp, N, M, N, Cin, KW, S, act, st, nullptr, EPI_NONE, nullptr, nullptr, Wbf));
+    NS_HIP(launch_layernorm(tmp, g, b, Y, M, N, S, lens, st, cur_rm(sc)));
+    return 0;
+  }
   if (Wb3 && !conv_gemm_b3_ok(M, N, Cin, KW, EPI_LN) && conv_gemm_b3_ok(M, N, Cin, KW, EPI_NONE)) {
     NS_TRY(gemm(sc, X, ldx, W, bias, resid, N, tmp, N, M, N, Cin, KW, S, act, st, nullptr, EPI_NONE, Wb3));
     NS_HIP(launch_layernorm(tmp, g, b, Y, M, N, S, lens, st, cur_rm(sc)));
@@ -609,17 +649,19 @@ static int mha(ns_model* m, const LayerW& L, int d, int H, const float* x, const
                float* out, bool mask_rows, Scratch& sc, hipStream_t st) {
   const int M = rows_of(sc, B, S);
   auto b3 = [&](size_t off) { return off != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(off)) : nullptr; };
-  NS_TRY(gemm(sc, x, d, m->P(L.qkv_w), m->P(L.qkv_b), nullptr, 0, sc.qkv, 3 * d, M, 3 * d, d, 1, S, ACT_NONE, st, nullptr, EPI_NONE, b3(L.qkv_b3)));
+  const bool bf = L.qkv_bf != NO_B3;  // bf16 mode, decoder layer: the attention's contractions on bf16 too
+  NS_TRY(gemm(sc, x, d, m->P(L.qkv_w), m->P(L.qkv_b), nullptr, 0, sc.qkv, 3 * d, M, 3 * d, d, 1, S, ACT_NONE, st, nullptr, EPI_NONE, b3(L.qkv_b3),
+              nullptr, b3(L.qkv_bf)));
   {
     ProfScope ps(m, 1, 4.0 * (double)M * (double)S * (double)d);
     NS_TRY(ps.begin());
     NS_HIP(launch_attention(sc.qkv, lens, B, S, H, d / H, sc.att, sc.att_part, sc.att_part_floats,
                             (sc.att_part && attention_uses_tickets(B, S, H)) ? sc.take_tickets(attention_ticket_ints(B, S, H)) : nullptr, st, cur_rm(sc),
-                            ps.timing()));
+                            ps.timing(), bf));
     ps.end();
   }
   return gemm_ln(sc.att, d, m->P(L.fc_w), m->P(L.fc_b), x, sc.t1, out, M, d, d, 1, S, ACT_NONE, m->P(L.ln1_g), m->P(L.ln1_b),
-                 mask_rows ? lens : nullptr, sc, st, b3(L.fc_b3));
+                 mask_rows ? lens : nullptr, sc, st, b3(L.fc_b3), b3(L.fc_bf));
 }
 
 // PositionwiseFeedForward.forward (transformer/SubLayers.py:87-95)
@@ -631,12 +673,14 @@ static int ffn(ns_model* m, const LayerW& L, int d, const float* x, const long l
     ProfScope ps(m, 0, 2.0 * (double)M * (double)c.ffn_k1 * (double)d * (double)c.d_inner);
     NS_TRY(ps.begin());
     NS_TRY(gemm(sc, x, d, m->P(L.w1), m->P(L.w1_b), nullptr, 0, sc.hid, c.d_inner, M, c.d_inner, d, c.ffn_k1, S, ACT_RELU, st, nullptr, EPI_NONE,
-                L.w1_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w1_b3)) : nullptr, ps.timing()));
+                L.w1_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w1_b3)) : nullptr, ps.timing(),
+                L.w1_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w1_bf)) : nullptr));
     ps.end();
   }
   return gemm_ln(sc.hid, c.d_inner, m->P(L.w2), m->P(L.w2_b), x, sc.t1, out, M, d, c.d_inner, c.ffn_k2, S, ACT_NONE, m->P(L.ln2_g),
                  m->P(L.ln2_b), mask_rows ? lens : nullptr, sc, st,
-                 L.w2_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w2_b3)) : nullptr);
+                 L.w2_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w2_b3)) : nullptr,
+                 L.w2_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w2_bf)) : nullptr);
 }
 
 // FFTBlock.forward (transformer/Layers.py:39-48): both masked_fill's are fused into the LayerNorm kernels
@@ -704,7 +748,8 @@ static int postnet(ns_model* m, const float* mel, int B, int T, const float* res
     if (mid) NS_TRY(ps.begin());
     NS_TRY(gemm(sc, cur, ld, m->P(w.w), m->P(w.b), last ? resid : nullptr, c.n_mel, dst, w.cout, M, w.cout, w.cin, c.postnet_k, T,
                 last ? ACT_NONE : ACT_TANH, st, nullptr, EPI_NONE,
-                w.w_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(w.w_b3)) : nullptr, mid ? ps.timing() : nullptr));
+                w.w_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(w.w_b3)) : nullptr, mid ? ps.timing() : nullptr,
+                w.w_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(w.w_bf)) : nullptr));
     if (mid) ps.end();
     cur = dst;
     ld = w.cout;
@@ -942,7 +987,7 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
   const int d = c.d_dec;
   // packed rows: the exact fp32 path, and only when the windows are a real saving over the grid
   size_t Mp = 0;
-  bool packed = lens_host && !c.matmul_bf16x3 && !m->dec.empty();
+  bool packed = lens_host && c.matmul_bf16x3 != 1 && !m->dec.empty();  // (fp32 and bf16 modes; bf16x3 stays on the grid)
   if (packed) {
     Mp = packed_rows(lens_host, B, T);
     // measured, packed against grid over length distributions (profiles/r03_packed_vs_grid_by_padding.txt): any saving of 10 %
@@ -1036,7 +1081,8 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
   m->prof_active = m->prof != 0;  // time only phase 2's launches: one shape per slot (the encoder runs the same kernels at B*L rows)
   int rc = decoder_stack(m, cur, lens, B, T, sc.att, sc, st);
   // note: decoder_stack's last layer writes into sc.att only after its own attention output was consumed
-  if (!rc) rc = gemm(sc, sc.att, d, m->P(m->mel_w), m->P(m->mel_b), nullptr, 0, mel_dst, c.n_mel, M, c.n_mel, d, 1, T, ACT_NONE, st);
+  if (!rc) rc = gemm(sc, sc.att, d, m->P(m->mel_w), m->P(m->mel_b), nullptr, 0, mel_dst, c.n_mel, M, c.n_mel, d, 1, T, ACT_NONE, st, nullptr,
+                     EPI_NONE, nullptr, nullptr, m->mel_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(m->mel_bf)) : nullptr);
   if (!rc) rc = postnet(m, mel_dst, B, T, mel_dst, post_dst, sc, st);
   m->prof_active = false;
   if (!rc && packed) {

@@ -32,6 +32,8 @@ namespace ns {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 constexpr int ATT_STRIP_SPLIT_MAX = 8;  // workgroups sharing one 32-query strip's key axis (k_attention_strip)
 
@@ -43,7 +45,24 @@ __device__ __forceinline__ f32x4 merge_fma(f32x4 o, float w, f32x4 acc) {
   return f32x4{__builtin_fmaf(o[0], w, acc[0]), __builtin_fmaf(o[1], w, acc[1]), __builtin_fmaf(o[2], w, acc[2]), __builtin_fmaf(o[3], w, acc[3])};
 }
 
-template <int DK>
+// ---- the "bf16" precision mode (BF = true, decoder only; api.hip): the same kernels with both contractions on the bf16
+// matrix cores (v_mfma_f32_32x32x16_bf16), operands rounded to nearest even by the plain cast (v_cvt_pk_bf16_f32: the NaN of a
+// zero-length utterance survives), fp32 accumulation.  Q is loaded unscaled; the fp32 scores are multiplied by
+// log2(e)/sqrt(d_k) after the MFMA, then masked and soft-maxed in fp32 exactly as in the fp32 kernels.  The k index of an MFMA
+// is free as long as A and B agree, so both contractions reuse the fp32 kernels' fragments:
+//   S^T = K Q^T: k step t <-> the 16 d values of the fp32 k-groups 2t and 2t+1 (a lane's 4 + 4 of them, both operands);
+//   O^T += V^T P^T: k step u, lane half h, element j <-> key(8u + j, h), i.e. the B operand is P registers 8u .. 8u+7 and the
+//   A operand the V values the fp32 kernel feeds at steps 8u .. 8u+7.
+// P enters P V rounded, un-normalised — p = 2^(s - M), divided by the fp32 sum l at the end — with the reference M kept an
+// INTEGER (ceil of the running maximum): rounding commutes with powers of two, so the bf16 P does not depend on which integer
+// reference the online softmax, a split-key range or a wave of the strip kernel happened to hold (and every rescale by
+// 2^(M_old - M_new) is exact): every launch form rounds the same P as a two-pass softmax would.
+__device__ __forceinline__ bf16x8 to_bf16x8(f32x4 a, f32x4 b) {
+  const f32x8 x = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  return __builtin_convertvector(x, bf16x8);
+}
+
+template <int DK, bool BF = false>
 __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv, const long long* __restrict__ lens,
                                                     int S_grid, int d, float c_scale, float* __restrict__ out, int nsplit,
                                                     float* __restrict__ opart, float* __restrict__ mlpart,
@@ -162,7 +181,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
     // stored).  With `if (q < S)` around each load hipcc emitted load -> s_waitcnt vmcnt(0) NG times in a row — 16 serialized
     // round trips (~10 us) at the head of every workgroup, ahead of the first K / V DMA.
     const float* qrow = base + (size_t)(q < S ? q : S - 1) * ld + 4 * h;
-    const float qs = q < S ? c_scale : 0.f;
+    const float qs = q < S ? (BF ? 1.f : c_scale) : 0.f;  // (bf16: the scale goes on the fp32 scores)
 #pragma unroll
     for (int g = 0; g < NG; ++g) qreg[g] = *reinterpret_cast<const f32x4*>(qrow + 8 * g);
 #pragma unroll
@@ -188,11 +207,22 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
   auto qk = [&](const float* kp, f32x16& s) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
+    if constexpr (BF) {
 #pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const f32x4 kf = *reinterpret_cast<const f32x4*>(kp + koff[g]);
+      for (int t = 0; t < NG / 2; ++t) {
+        const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp + koff[2 * t]);
+        const f32x4 k1 = *reinterpret_cast<const f32x4*>(kp + koff[2 * t + 1]);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(to_bf16x8(k0, k1), to_bf16x8(qreg[2 * t], qreg[2 * t + 1]), s, 0, 0, 0);
+      }
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qreg[g][e], s, 0, 0, 0);
+      for (int r = 0; r < 16; ++r) s[r] *= c_scale;
+    } else {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const f32x4 kf = *reinterpret_cast<const f32x4*>(kp + koff[g]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qreg[g][e], s, 0, 0, 0);
+      }
     }
   };
   // key-padding mask + online softmax of tile kt; s becomes P, returns the O rescale factor
@@ -215,7 +245,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
     // removes the 64-register O^T rescale (and its accumulator-file round trip) from the steady state.
     constexpr float RESCALE_LOG2 = 10.f;
     const bool need = mt > m_run + RESCALE_LOG2;  // (-inf + 10 = -inf: the first finite tile always fires)
-    const float m_new = need ? mt : m_run;
+    const float m_new = need ? (BF ? ceilf(mt) : mt) : m_run;  // (bf16: an integer reference, see to_bf16x8)
     const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
     const float alpha = need ? __builtin_amdgcn_exp2f(m_run - m_use) : 1.0f;
     float psum = 0.f;
@@ -251,14 +281,33 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
     }
+    if constexpr (BF) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      typedef float vrow_t __attribute__((ext_vector_type(NDB)));
-      const vrow_t vv = *reinterpret_cast<const vrow_t*>(vp + ((r & 3) + 8 * (r >> 2)) * DK);
+      for (int u = 0; u < 2; ++u) {
+        typedef float vrow_t __attribute__((ext_vector_type(NDB)));
+        f32x8 va[NDB], pp;
 #pragma unroll
-      for (int db = 0; db < NDB; ++db) {
-        const float v = vv[db];
-        o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(v, pr[r], o[db], 0, 0, 0);
+        for (int j = 0; j < 8; ++j) {
+          const int r = 8 * u + j;
+          const vrow_t vv = *reinterpret_cast<const vrow_t*>(vp + ((r & 3) + 8 * (r >> 2)) * DK);
+#pragma unroll
+          for (int db = 0; db < NDB; ++db) va[db][j] = vv[db];
+          pp[j] = pr[r];
+        }
+        const bf16x8 pb = __builtin_convertvector(pp, bf16x8);
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_convertvector(va[db], bf16x8), pb, o[db], 0, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        typedef float vrow_t __attribute__((ext_vector_type(NDB)));
+        const vrow_t vv = *reinterpret_cast<const vrow_t*>(vp + ((r & 3) + 8 * (r >> 2)) * DK);
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) {
+          const float v = vv[db];
+          o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(v, pr[r], o[db], 0, 0, 0);
+        }
       }
     }
   };
@@ -344,7 +393,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
 // partial bytes) and removes the merge launch altogether when nsplit == 1 (the encoder).
 // Merging, in-workgroup and across workgroups alike: out = sum_i O_i 2^(m_i - m) / sum_i l_i 2^(m_i - m), m = max_i m_i,
 // i in key order — exact for any split (each partial is an exact softmax numerator / denominator relative to its own m_i).
-template <int DK>
+template <int DK, bool BF = false>
 __global__ __launch_bounds__(256) void k_attention_strip(const float* __restrict__ qkv, const long long* __restrict__ lens,
                                                           int S_grid, int d, float c_scale, float* __restrict__ out, int nsplit,
                                                           float* __restrict__ opart, float* __restrict__ mlpart,
@@ -413,7 +462,7 @@ __global__ __launch_bounds__(256) void k_attention_strip(const float* __restrict
     // stored).  With `if (q < S)` around each load hipcc emitted load -> s_waitcnt vmcnt(0) NG times in a row — 16 serialized
     // round trips (~10 us) at the head of every workgroup, ahead of the first K / V DMA.
     const float* qrow = base + (size_t)(q < S ? q : S - 1) * ld + 4 * h;
-    const float qs = q < S ? c_scale : 0.f;
+    const float qs = q < S ? (BF ? 1.f : c_scale) : 0.f;  // (bf16: the scale goes on the fp32 scores)
 #pragma unroll
     for (int g = 0; g < NG; ++g) qreg[g] = *reinterpret_cast<const f32x4*>(qrow + 8 * g);
 #pragma unroll
@@ -442,11 +491,22 @@ __global__ __launch_bounds__(256) void k_attention_strip(const float* __restrict
     f32x16 sc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) sc[r] = 0.f;
+    if constexpr (BF) {
 #pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const f32x4 kf = *reinterpret_cast<const f32x4*>(Kw + koff[g]);
+      for (int t = 0; t < NG / 2; ++t) {
+        const f32x4 k0 = *reinterpret_cast<const f32x4*>(Kw + koff[2 * t]);
+        const f32x4 k1 = *reinterpret_cast<const f32x4*>(Kw + koff[2 * t + 1]);
+        sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(to_bf16x8(k0, k1), to_bf16x8(qreg[2 * t], qreg[2 * t + 1]), sc, 0, 0, 0);
+      }
 #pragma unroll
-      for (int e = 0; e < 4; ++e) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qreg[g][e], sc, 0, 0, 0);
+      for (int r = 0; r < 16; ++r) sc[r] *= c_scale;
+    } else {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const f32x4 kf = *reinterpret_cast<const f32x4*>(Kw + koff[g]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qreg[g][e], sc, 0, 0, 0);
+      }
     }
     if (kt + 1 < nkt) {  // K(kt) is consumed (its fragment reads returned before the MFMAs issued): refill it under the softmax
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -466,7 +526,7 @@ __global__ __launch_bounds__(256) void k_attention_strip(const float* __restrict
     mt = fmaxf(mt, __shfl_xor(mt, 32));
     constexpr float RESCALE_LOG2 = 10.f;
     const bool need = mt > m_run + RESCALE_LOG2;
-    const float m_new = need ? mt : m_run;
+    const float m_new = need ? (BF ? ceilf(mt) : mt) : m_run;  // (bf16: an integer reference, see to_bf16x8)
     const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
     const float alpha = need ? __builtin_amdgcn_exp2f(m_run - m_use) : 1.0f;
     float psum = 0.f;
@@ -485,12 +545,31 @@ __global__ __launch_bounds__(256) void k_attention_strip(const float* __restrict
     }
     if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (BF) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      typedef float vrow_t __attribute__((ext_vector_type(NDB)));
-      const vrow_t vv = *reinterpret_cast<const vrow_t*>(vp + ((r & 3) + 8 * (r >> 2)) * DK);
+      for (int u = 0; u < 2; ++u) {
+        typedef float vrow_t __attribute__((ext_vector_type(NDB)));
+        f32x8 va[NDB], pp;
 #pragma unroll
-      for (int db = 0; db < NDB; ++db) o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[db], sc[r], o[db], 0, 0, 0);
+        for (int j = 0; j < 8; ++j) {
+          const int r = 8 * u + j;
+          const vrow_t vv = *reinterpret_cast<const vrow_t*>(vp + ((r & 3) + 8 * (r >> 2)) * DK);
+#pragma unroll
+          for (int db = 0; db < NDB; ++db) va[db][j] = vv[db];
+          pp[j] = sc[r];
+        }
+        const bf16x8 pb = __builtin_convertvector(pp, bf16x8);
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_convertvector(va[db], bf16x8), pb, o[db], 0, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        typedef float vrow_t __attribute__((ext_vector_type(NDB)));
+        const vrow_t vv = *reinterpret_cast<const vrow_t*>(vp + ((r & 3) + 8 * (r >> 2)) * DK);
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[db], sc[r], o[db], 0, 0, 0);
+      }
     }
     if (kt + 1 < nkt) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -714,10 +793,21 @@ int attention_split_packed(int att_wgs, int S, int dk, size_t Mp, int d) {
 }
 
 // k_attention with optional dispatch-attached timing events (kernels.h LaunchTiming)
+template <int DK, bool BF = false, typename... Args>
+static void launch_k_attention_t(dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, Args... args) {
+  if (e0 || e1) hipExtLaunchKernelGGL((k_attention<DK, BF>), grid, dim3(256), 0, st, e0, e1, 0, args...);
+  else hipLaunchKernelGGL((k_attention<DK, BF>), grid, dim3(256), 0, st, args...);
+}
+// (bf: the bf16 mode's variant)
 template <int DK, typename... Args>
-static void launch_k_attention(dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, Args... args) {
-  if (e0 || e1) hipExtLaunchKernelGGL((k_attention<DK>), grid, dim3(256), 0, st, e0, e1, 0, args...);
-  else hipLaunchKernelGGL((k_attention<DK>), grid, dim3(256), 0, st, args...);
+static void launch_k_attention(bool bf, dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, Args... args) {
+  if (bf) launch_k_attention_t<DK, true>(grid, st, e0, e1, args...);
+  else launch_k_attention_t<DK, false>(grid, st, e0, e1, args...);
+}
+template <int DK, typename... Args>
+static void launch_k_strip(bool bf, dim3 grid, hipStream_t st, Args... args) {
+  if (bf) hipLaunchKernelGGL((k_attention_strip<DK, true>), grid, dim3(256), 0, st, args...);
+  else hipLaunchKernelGGL((k_attention_strip<DK, false>), grid, dim3(256), 0, st, args...);
 }
 
 // Few workgroups (single-utterance latency, the encoder): a 128-query workgroup's time is its serial sweep over the key tiles.
@@ -727,7 +817,7 @@ static void launch_k_attention(dim3 grid, hipStream_t st, hipEvent_t e0, hipEven
 // of a ragged batch on packed phoneme rows used k_attention + k_attention_merge, one launch more per layer): the grid is sized
 // for the longest window S, every utterance's strips address its own rows.  false = not taken (the caller's other paths).
 static bool launch_strips(const float* qkv, const long long* lens, int B, int S, int H, int dk, float* out, float* scratch, size_t scratch_floats,
-                          int* tickets, hipStream_t st, const RowMap* rm, hipEvent_t ev0, hipEvent_t ev1) {
+                          int* tickets, hipStream_t st, const RowMap* rm, hipEvent_t ev0, hipEvent_t ev1, bool bf) {
   const int d = H * dk, tiles = (S + 31) / 32;
   const float c = 1.4426950408889634f / sqrtf((float)dk);
   const size_t M = rm ? (size_t)rm->rows : (size_t)B * S;
@@ -750,9 +840,10 @@ static bool launch_strips(const float* qkv, const long long* lens, int B, int S,
   const int rows = rm ? rm->rows : 0;
   dim3 grid(tiles * nsplit, H, B), block(256);
   if (ev0) (void)hipEventRecord(ev0, st);  // (small-grid path: plain marker events, this launch is not a roofline case)
-  if (dk == 128) hipLaunchKernelGGL((k_attention_strip<128>), grid, block, 0, st, qkv, lens, S, d, c, out, nsplit, opart, mlpart, tickets, off, win, rows);
-  else if (dk == 64) hipLaunchKernelGGL((k_attention_strip<64>), grid, block, 0, st, qkv, lens, S, d, c, out, nsplit, opart, mlpart, tickets, off, win, rows);
-  else hipLaunchKernelGGL((k_attention_strip<32>), grid, block, 0, st, qkv, lens, S, d, c, out, nsplit, opart, mlpart, tickets, off, win, rows);
+  (void)block;
+  if (dk == 128) launch_k_strip<128>(bf, grid, st, qkv, lens, S, d, c, out, nsplit, opart, mlpart, tickets, off, win, rows);
+  else if (dk == 64) launch_k_strip<64>(bf, grid, st, qkv, lens, S, d, c, out, nsplit, opart, mlpart, tickets, off, win, rows);
+  else launch_k_strip<32>(bf, grid, st, qkv, lens, S, d, c, out, nsplit, opart, mlpart, tickets, off, win, rows);
   // without a ticket block (ns_config.row_epilogue = two_launch, or the phase's block is spent) the strips' partials are
   // merged by a launch of their own: same layout, same split order, same arithmetic as the last arriver's merge
   if (nsplit > 1 && !tickets) hipLaunchKernelGGL(k_attention_merge, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, opart, mlpart, (int)M, d, H, dk, nsplit, out);
@@ -761,7 +852,7 @@ static bool launch_strips(const float* qkv, const long long* lens, int B, int S,
 }
 
 hipError_t launch_attention(const float* qkv, const long long* lens, int B, int S, int H, int dk, float* out, float* scratch,
-                            size_t scratch_floats, int* tickets, hipStream_t st, const RowMap* rm, const LaunchTiming* tm) {
+                            size_t scratch_floats, int* tickets, hipStream_t st, const RowMap* rm, const LaunchTiming* tm, bool bf) {
   if (B <= 0 || S <= 0) return hipSuccess;
   hipEvent_t ev0 = tm ? tm->start : nullptr, ev1 = tm ? tm->stop : nullptr;
   if (rm) {  // packed rows: one workgroup per (128-query tile, head) of every utterance's window, longest utterances first
@@ -770,7 +861,7 @@ hipError_t launch_attention(const float* qkv, const long long* lens, int B, int 
     if (!rm->att_off || !rm->att_order || rm->att_wgs <= 0 || rm->rows <= 0) return hipErrorInvalidValue;
     // a handful of short windows (phase 1 of a ragged batch, L <= ~500): the strip kernel on the packed rows, no merge launch
     if ((long)((S + 127) / 128) * H * B < ATT_SPLIT_MAX_BLOCKS && (long long)rm->rows * 3 * d * 4 < (1ll << 31) &&
-        launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, rm, ev0, ev1))
+        launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, rm, ev0, ev1, bf))
       return hipGetLastError();
     const float c = 1.4426950408889634f / sqrtf((float)dk);
     // Few workgroups (a handful of ragged utterances): the launch would last as long as the longest utterance's sweep while
@@ -788,9 +879,9 @@ hipError_t launch_attention(const float* qkv, const long long* lens, int B, int 
     dim3 grid(rm->att_wgs * nsplit);
     hipEvent_t k1 = nsplit > 1 ? nullptr : ev1;  // (with a merge launch the stop event rides on the merge)
 #define NS_PK rm->off, rm->win, rm->att_off, rm->att_order, B, (int)Mp, H
-    if (dk == 128) launch_k_attention<128>(grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, NS_PK);
-    else if (dk == 64) launch_k_attention<64>(grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, NS_PK);
-    else launch_k_attention<32>(grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, NS_PK);
+    if (dk == 128) launch_k_attention<128>(bf, grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, NS_PK);
+    else if (dk == 64) launch_k_attention<64>(bf, grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, NS_PK);
+    else launch_k_attention<32>(bf, grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, NS_PK);
 #undef NS_PK
     if (nsplit > 1) {
       if (ev1) hipExtLaunchKernelGGL(k_attention_merge, dim3((unsigned)((Mp + 3) / 4)), dim3(256), 0, st, nullptr, ev1, 0, opart, mlpart, (int)Mp, d, H, dk, nsplit, out);
@@ -806,7 +897,7 @@ hipError_t launch_attention(const float* qkv, const long long* lens, int B, int 
   const long blocks = (long)qtiles * H * B;
   const size_t M = (size_t)B * S;
   auto part_floats = [&](int n) { return (size_t)n * (M * d + 2 * M * H); };
-  if (blocks < ATT_SPLIT_MAX_BLOCKS && launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, nullptr, ev0, ev1)) return hipGetLastError();
+  if (blocks < ATT_SPLIT_MAX_BLOCKS && launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, nullptr, ev0, ev1, bf)) return hipGetLastError();
   // Otherwise k_attention; still few workgroups (long single utterances): split the key sweep over up to ATT_SPLIT_MAX
   // workgroups per 128-query tile until the launch has ~256 of them, then merge the partials with k_attention_merge.
   // Needs nsplit * (M*d + 2*M*H) floats of scratch.
@@ -830,9 +921,9 @@ hipError_t launch_attention(const float* qkv, const long long* lens, int B, int 
   float* mlpart = nsplit > 1 ? scratch + (size_t)nsplit * M * d : nullptr;
   dim3 grid(qtiles * nsplit, H, B);
   hipEvent_t k1 = nsplit > 1 ? nullptr : ev1;
-  if (dk == 128) launch_k_attention<128>(grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0, 0, 0);
-  else if (dk == 64) launch_k_attention<64>(grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0, 0, 0);
-  else launch_k_attention<32>(grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0, 0, 0);
+  if (dk == 128) launch_k_attention<128>(bf, grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0, 0, 0);
+  else if (dk == 64) launch_k_attention<64>(bf, grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0, 0, 0);
+  else launch_k_attention<32>(bf, grid, st, ev0, k1, qkv, lens, S, d, c, out, nsplit, opart, mlpart, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0, 0, 0);
   if (nsplit > 1) {
     if (ev1) hipExtLaunchKernelGGL(k_attention_merge, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, nullptr, ev1, 0, opart, mlpart, (int)M, d, H, dk, nsplit, out);
     else hipLaunchKernelGGL(k_attention_merge, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, opart, mlpart, (int)M, d, H, dk, nsplit, out);

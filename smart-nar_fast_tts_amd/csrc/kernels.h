@@ -53,6 +53,7 @@ struct ConvGemm {
   const float* W;               // packed [N][KW*Cin], row stride ldw
   int ldw;                      // floats between weight rows; 0 = KW*Cin (dense)
   const unsigned short* Wb3;    // optional: the same weights as three bf16 planes [3][N][KW*Cin] (gemm_bf16x3.hip), else nullptr
+  const unsigned short* Wbf;    // "bf16" mode: the weights rounded to one bf16 plane [N][KW][Cinp] (gemm_bf16.hip), else nullptr
   const float* bias;            // [N] or nullptr
   const float* resid; int ldr;  // [M, N] or nullptr
   float* Y; int ldy;
@@ -83,6 +84,12 @@ bool launch_planner_enabled();
 bool conv_gemm_b3_ok(int M, int N, int Cin, int KW, int epi);  // epi: EPI_NONE or EPI_LN
 hipError_t launch_conv_gemm_b3(const ConvGemm& p, hipStream_t st);
 void split_weights_b3(const float* w, size_t n, unsigned short* hi, unsigned short* mid, unsigned short* lo);
+// opt-in "bf16" precision mode (gemm_bf16.hip): both operands rounded to bf16, fp32 accumulation, at every launch size
+bool conv_gemm_bf16_ok(int M, int N, int Cin, int KW, int epi);  // epi: EPI_NONE, or EPI_LN (the 64 x 256 full-row tile)
+void conv_gemm_bf16_plan(int M, int N, int* bm, int* bn);     // tile of a plain launch
+hipError_t launch_conv_gemm_bf16(const ConvGemm& p, hipStream_t st);
+size_t bf16_plane_elems(int N, int KW, int Cin);               // N * KW * (Cin rounded up to 32)
+void round_weights_bf16(const float* w, int N, int KW, int Cin, unsigned short* dst);
 // true when launch_conv_gemm has a full-row tile for this shape (so p.epi may be set); otherwise the caller runs the
 // plain GEMM followed by the row kernel
 bool conv_gemm_row_epilogue_ok(int M, int N, int Cin);
@@ -99,8 +106,11 @@ constexpr int ATT_SPLIT_MAX = 16, ATT_SPLIT_MAX_BLOCKS = 128;
 inline int attention_ticket_ints(int B, int S, int H) { return B * H * ((S + 31) / 32); }
 bool attention_uses_tickets(int B, int S, int H);  // false: launch_attention(B, S, H, ...) never touches `tickets` (pass nullptr)
 // rm (packed rows): utterance b's rows start at rm->off[b] and number rm->win[b] <= S (S = the longest window); no split-key path
+// bf16 (the "bf16" precision mode, decoder only): Q K^T and P V on the bf16 matrix cores from operands rounded to bf16,
+// scores scaled, masked and soft-maxed in fp32
 hipError_t launch_attention(const float* qkv, const long long* lens, int B, int S, int H, int dk, float* out, float* scratch,
-                            size_t scratch_floats, int* tickets, hipStream_t st, const RowMap* rm = nullptr, const LaunchTiming* tm = nullptr);
+                            size_t scratch_floats, int* tickets, hipStream_t st, const RowMap* rm = nullptr, const LaunchTiming* tm = nullptr,
+                            bool bf16 = false);
 // key ranges per 128-query tile the dense launch of (B, S, H, dk) will use when it has the scratch for them (1 = no split):
 // the caller sizes `scratch` as attention_split(...) * B*S*(H*dk + 2*H) floats
 int attention_split(int B, int S, int H, int dk);

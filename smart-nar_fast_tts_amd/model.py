@@ -47,9 +47,11 @@ def config_struct(preprocess_config: dict, model_config: dict) -> _lib.NsConfig:
         # EXTENSION key (absent from the reference's model.yaml): "gaussian" wires the reference's unused
         # GaussianUpsampling module in place of the hard LengthRegulator
         length_regulator={"hard": 0, "gaussian": 1}[model_config.get("length_regulator", "hard")],
-        # EXTENSION key: "bf16x3" opts the large decoder-FFN / PostNet contractions into the split-bf16 matrix-core path
-        # (include/nar_fs2.h ns_config.matmul_bf16x3); "fp32" (default) is the reference's arithmetic everywhere
-        matmul_bf16x3={"fp32": 0, "bf16x3": 1}[model_config.get("matmul", "fp32")],
+        # EXTENSION key: "bf16x3" opts the large decoder-FFN / PostNet contractions into the split-bf16 matrix-core path;
+        # "bf16" runs every contraction from the decoder input through the PostNet output on bf16 operands with fp32
+        # accumulation, everything upstream (durations, pitch, energy) stays exact fp32 (include/nar_fs2.h
+        # ns_config.matmul_bf16x3); "fp32" (default) is the reference's arithmetic everywhere
+        matmul_bf16x3={"fp32": 0, "bf16x3": 1, "bf16": 2}[model_config.get("matmul", "fp32")],
         # EXTENSION key (tests): "two_launch" never draws a ticket — LayerNorm / predictor tails / attention merges of small
         # grids run as separate launches instead of last-arriver epilogues (include/nar_fs2.h ns_config.row_epilogue); same bits
         row_epilogue={"fused": 0, "two_launch": 1}[model_config.get("row_epilogue", "fused")],
@@ -280,7 +282,8 @@ class FastSpeech2Align:
 
     def _no_cast(self, what):
         raise NotImplementedError(f"{what}: this path computes in float32 only (the reference's arithmetic, mel max-abs < 1e-3); "
-                                  "the opt-in bf16x3 matrix mode is model_config['matmul'] = 'bf16x3', not a dtype cast")
+                                  "the opt-in reduced-precision modes are model_config['matmul'] = 'bf16' (bf16 decoder / PostNet, "
+                                  "exact durations and pitch) or 'bf16x3', not a dtype cast")
 
     def half(self):
         self._no_cast("half()")

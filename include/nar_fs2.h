@@ -272,6 +272,62 @@ int ns_profile_enable(ns_model* m, int on);
 int ns_profile_read(ns_model* m, double* total_ms, double* total_flops, int64_t* launches);
 int ns_profile_read_slot(ns_model* m, int slot, double* total_ms, double* total_flops, int64_t* launches);
 
+/* ==== HiFi-GAN vocoder (the reference's inference tail: utils/model.py:38-88, utils/tools.py:189-199) ==========================
+ * A separate handle with its own weights and arena; nothing above changes.  The generator (hifigan.Generator, resblock "1"):
+ *   x = conv_pre(mel)                              Conv1d(n_mel, C0, 7, padding 3)
+ *   for i < n_up:  x = ups[i](lrelu(x, 0.1))       ConvTranspose1d(C0 >> i, C0 >> (i+1), up_kernels[i], up_rates[i], padding (k-u)/2)
+ *                  x = (rb[n_rb i](x) + ... + rb[n_rb i + n_rb - 1](x)) / n_rb     (summed left to right)
+ *   wav = tanh(conv_post(lrelu(x, 0.01)))          Conv1d(C0 >> n_up, 1, 7, padding 3)
+ * ResBlock1(ch, k, d[0..2]): for each d: x = c2(lrelu(c1(lrelu(x, 0.1)), 0.1)) + x, c1 = Conv1d(ch, ch, k, dilation d, "same"),
+ * c2 = Conv1d(ch, ch, k, "same").  Every convolution has a bias.  Weights are plain `weight` tensors (weight norm already folded:
+ * torch._weight_norm(weight_v, weight_g, 0), which is what remove_weight_norm() leaves), torch-native layouts — Conv1d
+ * [Cout, Cin, k], ConvTranspose1d [Cin, Cout, k] — under the reference's module paths: conv_pre, ups.{i},
+ * resblocks.{n_rb i + j}.convs{1,2}.{n}, conv_post.  The library allocates no device memory here either. */
+#define NS_VOC_ABI_VERSION 1
+typedef struct ns_vocoder ns_vocoder;
+typedef struct ns_voc_config {
+  int32_t n_mel;             /* num_mels: 80 */
+  int32_t initial_channel;   /* upsample_initial_channel: 512 */
+  int32_t n_up;              /* len(upsample_rates), 1..4 */
+  int32_t up_rates[4];       /* [8, 8, 2, 2]: even */
+  int32_t up_kernels[4];     /* [16, 16, 4, 4]: 2 * rate */
+  int32_t n_rb;              /* len(resblock_kernel_sizes), 1..4 */
+  int32_t rb_kernels[4];     /* [3, 7, 11]: odd */
+  int32_t rb_dilations[4][4];/* [[1, 3, 5]] * 3: three dilations per resblock (ResBlock1), entry 3 must be 0 */
+  int32_t resblock;          /* 1 ("1"): ResBlock2 is not supported */
+} ns_voc_config;
+int ns_voc_abi_version(void);
+/* Rejects (nonzero, ns_last_error) anything but resblock 1, k = 2u with u even, odd resblock kernels, channel counts C0 >> i
+ * that are multiples of 32 (i = 1 .. n_up) and n_mel a multiple of 16. */
+int ns_voc_create(const ns_voc_config* cfg, ns_vocoder** out);
+void ns_voc_destroy(ns_vocoder* v);
+size_t ns_voc_arena_bytes(const ns_vocoder* v);
+int ns_voc_bind_arena(ns_vocoder* v, void* dev_arena, size_t bytes);  /* 256-byte aligned */
+/* host float32 `weight` / `bias`; unknown keys and shape mismatches are errors.  check: the same validation, no side effect. */
+int ns_voc_set_weight(ns_vocoder* v, const char* name, const float* host, const int64_t* shape, int ndim);
+int ns_voc_check_weight(ns_vocoder* v, const char* name, const int64_t* shape, int ndim);
+/* repack (Conv1d -> [Cout][k][Cin]; ConvTranspose1d -> the polyphase [u Cout][2 Cin]) and upload; fails if a key is missing */
+int ns_voc_finalize_weights(ns_vocoder* v, void* stream);
+/* Workspace of ns_voc_forward: four buffers of B * A floats, each rounded up to 256 bytes, where
+ * A = max(T * n_mel, T * C0, max_i T * (u_0 ... u_i) * (C0 >> (i+1))). */
+size_t ns_voc_ws_bytes(const ns_vocoder* v, int B, int T);
+/* wav [B, T * prod(up_rates)] (the memory of the reference's [B, 1, T * hop]) from the padded mel grid.
+ * mel_layout 0: mel is [B, n_mel, T] contiguous (what Generator.forward takes); 1: mel is [B, T, n_mel] contiguous, i.e. the caller
+ * holds a transpose(1, 2) view of the forward's postnet_output — consumed in place, 16-byte aligned. */
+#define NS_VOC_MEL_CHANNEL_MAJOR 0
+#define NS_VOC_MEL_TIME_MAJOR 1
+int ns_voc_forward(ns_vocoder* v, const float* mel, int mel_layout, int B, int T, float* wav, void* ws, size_t ws_bytes, void* stream);
+/* ---- per-operator entry points (tests), time-major [B, S, C] activations ----
+ * conv:     name = "resblocks.{r}.convs{1,2}.{n}": out = conv(lrelu(x, 0.1)) + bias, [B, S, ch] -> [B, S, ch];
+ *           "conv_pre": out = conv(x) + bias, [B, S, n_mel] -> [B, S, C0];
+ *           "conv_post": out = tanh(conv(lrelu(x, 0.01)) + bias), [B, S, C_last] -> [B, S].
+ * upsample: out = ups[i](lrelu(x, 0.1)), [B, S, 2 ch] -> [B, S u, ch]
+ * stage:    upsample i followed by its n_rb resblocks and their mean, [B, S, 2 ch] -> [B, S u, ch]; ws >= ns_voc_op_stage_ws_bytes */
+int ns_voc_op_conv(ns_vocoder* v, const char* name, const float* x, int B, int S, float* out, void* stream);
+int ns_voc_op_upsample(ns_vocoder* v, int i, const float* x, int B, int S, float* out, void* stream);
+size_t ns_voc_op_stage_ws_bytes(const ns_vocoder* v, int i, int B, int S);
+int ns_voc_op_stage(ns_vocoder* v, int i, const float* x, int B, int S, float* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,21 @@ SIGNATURES = {
     "ns_profile_enable": (_I, [_P, _I]),
     "ns_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ns_profile_read_slot": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    # HiFi-GAN vocoder (vocoder.py; the config pointer is a vocoder.NsVocConfig)
+    "ns_voc_abi_version": (_I, []),
+    "ns_voc_create": (_I, [_P, C.POINTER(_P)]),
+    "ns_voc_destroy": (None, [_P]),
+    "ns_voc_arena_bytes": (_Z, [_P]),
+    "ns_voc_bind_arena": (_I, [_P, _P, _Z]),
+    "ns_voc_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
+    "ns_voc_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
+    "ns_voc_finalize_weights": (_I, [_P, _P]),
+    "ns_voc_ws_bytes": (_Z, [_P, _I, _I]),
+    "ns_voc_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "ns_voc_op_conv": (_I, [_P, _S, _P, _I, _I, _P, _P]),
+    "ns_voc_op_upsample": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "ns_voc_op_stage_ws_bytes": (_Z, [_P, _I, _I, _I]),
+    "ns_voc_op_stage": (_I, [_P, _I, _P, _I, _I, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

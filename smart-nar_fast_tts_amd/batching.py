@@ -4,7 +4,7 @@ the padded outputs back into per-utterance results.  Host-side numpy/torch plumb
 * ``TextDataset.collate_fn``  dataset.py:182-191     -> :func:`collate`
 * ``pad_1D``                  utils/tools.py:254-264  -> :func:`pad_1D`
 * ``to_device`` (6-tuple)     utils/tools.py:56-63    -> :func:`to_device`
-* ``synthesize``              synthesize.py:59-76     -> :func:`synthesize` (forward only: no plots, no vocoder)
+* ``synthesize``              synthesize.py:59-76     -> :func:`synthesize` (no plots; the vocoder when one is passed)
 * per-utterance slicing       utils/tools.py:153-171  -> :func:`split_outputs`
 * ``expand``                  utils/tools.py:100-104  -> :func:`expand`
 
@@ -78,7 +78,7 @@ def split_outputs(batch, predictions, preprocess_config):
 
 
 def synthesize(model, batchs, preprocess_config, device="cuda", p_control: float = 1.0, e_control: float = 1.0,
-               streams: int = 1, host_lens: bool = False, max_mel_len=None):
+               streams: int = 1, host_lens: bool = False, max_mel_len=None, vocoder=None):
     """synthesize.py:59-76 reduced to its tensor contract: to_device -> model(*(batch[2:])) under no_grad ->
     per-utterance results (what synth_samples would plot / vocode).
 
@@ -93,7 +93,10 @@ def synthesize(model, batchs, preprocess_config, device="cuda", p_control: float
     reference's with ``max_len = max_mel_len``: a batch's longest utterance gains padding, which changes ITS output in the
     reference too (the variance predictors are unmasked between their convolutions) — pass the exact length
     for single utterances whose un-padded result is wanted.  An utterance longer than ``max_mel_len`` raises ValueError once
-    the batches are done — it is never silently cut."""
+    the batches are done — it is never silently cut.
+    ``vocoder`` (a vocoder.Generator, e.g. from vocoder.get_vocoder): every result item also carries ``"wav"``, the int16 waveform
+    of ``mel_len * hop_length`` samples that synth_samples writes (utils/tools.py:189-199: the padded postnet output, transposed, through
+    vocoder_infer, then trimmed); each batch is vocoded on the stream its forward ran on.  ``None``: no vocoder, results as before."""
     if max_mel_len is not None and streams <= 1:
         raise ValueError("max_mel_len is the capacity of the multi-stream mode; pass streams > 1 with it")
     if streams <= 1:
@@ -102,7 +105,7 @@ def synthesize(model, batchs, preprocess_config, device="cuda", p_control: float
             batch = to_device(batch, device, host_lens)
             with torch.no_grad():
                 output = model(*(batch[2:]), p_control=p_control, e_control=e_control)
-            results.extend(split_outputs(batch, output, preprocess_config))
+            results.extend(_with_wavs(split_outputs(batch, output, preprocess_config), output, model, vocoder, preprocess_config))
         return results
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -119,11 +122,28 @@ def synthesize(model, batchs, preprocess_config, device="cuda", p_control: float
             done.append((batch, output))
     torch.cuda.synchronize(dev)
     results = []
-    for batch, output in done:
+    for i, (batch, output) in enumerate(done):
         if max_mel_len is not None:
             output.check()
-        results.extend(split_outputs(batch, output, preprocess_config))
+        items = split_outputs(batch, output, preprocess_config)
+        if vocoder is not None:
+            with torch.cuda.stream(pool[i % streams]):
+                items = _with_wavs(items, output, model, vocoder, preprocess_config)
+        results.extend(items)
     return results
+
+
+def _with_wavs(items, output, model, vocoder, preprocess_config):
+    """synth_samples' vocoder step (utils/tools.py:189-194) on one batch's forward output: item i gains "wav"."""
+    if vocoder is None:
+        return items
+    from .vocoder import hop_length, vocoder_infer
+
+    lengths = [int(item["mel_len"]) * hop_length(preprocess_config) for item in items]
+    wavs = vocoder_infer(output[1].transpose(1, 2), vocoder, getattr(model, "model_config", {}), preprocess_config, lengths=lengths)
+    for item, wav in zip(items, wavs):
+        item["wav"] = wav
+    return items
 
 
 # A forward's time is (nearly) a function of its ROWS, B * T_pad on the padded grid, through the launch plan (include/nar_fs2.h

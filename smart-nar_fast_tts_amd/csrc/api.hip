@@ -147,6 +147,7 @@ static void plan_stack(ns_model* m, const char* prefix, int n_layer, int d, std:
 }
 
 extern "C" const char* ns_last_error(void) { return g_err.c_str(); }
+int ns::api_fail(const char* msg) { return fail(msg); }  // (the vocoder's C-ABI, vocoder_api.hip, reports through the same slot)
 
 extern "C" int ns_create(const ns_config* cfg, ns_model** out) {
   if (!cfg || !out) return fail("ns_create: null argument");

@@ -185,4 +185,28 @@ hipError_t launch_gaussian_upsampling(const float* x, const float* dur, int B, i
                                       float* out, float* s, float* w, const long long* own_len, int32_t* status, int* zero, int nzero,
                                       hipStream_t st, const RowMap* rm = nullptr);  // rm: out is the packed layout (w must be nullptr)
 
+// ---- HiFi-GAN vocoder (vocoder.hip) -----------------------------------------------------------
+// One implicit GEMM over a grid of Sg rows per utterance (Sg = S_in for a "same" Conv1d, S_in + 1 for a polyphase transposed conv):
+//   v[m, n] = sum_{j < KW} sum_{c < Cin} act_in(X[b, t + off0 + j dil, c]) W[n][j Cin + c]   (rows outside [0, S_in) read zero)
+//   v = v + bias[n % Cb]; v = lrelu(v, out_slope) if out_act; v = v + R[o] if R
+//   mrf 0: Y[o] = v   1: Y[o] = Y[o] + v   2: Y[o] = (Y[o] + v) / mrf_div
+// with m = b Sg + t and o = b out_ustride + (t N + n - out_shift), stored only when 0 <= t N + n - out_shift < out_ustride.
+// act_in(x) = lrelu(x, in_slope) when in_act, else x.  Cin % 32 == 0, N % 32 == 0, X / W 16-byte aligned.
+struct VocGemm {
+  const float* X; const float* W; const float* bias; const float* R; float* Y;
+  int B, S_in, Sg, Cin, KW, dil, off0, N, Cb;
+  long long out_ustride, out_shift;
+  int in_act; float in_slope; int out_act; float out_slope;
+  int mrf; float mrf_div;
+};
+bool voc_gemm_ok(const VocGemm& p);
+hipError_t launch_voc_gemm(const VocGemm& p, hipStream_t st);
+// wav[b, t] = tanh(bias[0] + sum_j sum_c lrelu(x[b, t + j - (KW-1)/2, c], slope) w[j C + c]) over [B, S, C] time-major x
+size_t voc_post_lds_bytes(int C, int KW);
+hipError_t launch_voc_post(const float* x, const float* w, const float* bias, float* wav, int B, int S, int C, int KW, float slope, hipStream_t st);
+// dst [B, T, C] = src [B, C, T] transposed
+hipError_t launch_voc_transpose(const float* src, float* dst, int B, int C, int T, hipStream_t st);
+// sets ns_last_error() (api.hip) and returns 1
+int api_fail(const char* msg);
+
 }  // namespace ns

@@ -363,3 +363,91 @@ def algorithmic_flops_per_frame(model_cfg: dict, S_dec: int, S_enc: int, frames_
     post = 2 * POSTNET_K * (N_MEL * POSTNET_DIM + (POSTNET_N - 2) * POSTNET_DIM ** 2 + POSTNET_DIM * N_MEL)
     lin = 2 * d_d * N_MEL
     return float(dec + enc + pe + du + post + lin)
+
+
+# ---- HiFi-GAN vocoder (the reference's hifigan/config.json, utils/model.py:52-56) --------------------------------------------
+# V1: the LJSpeech generator the reference loads (hifigan/generator_LJSpeech.pth.tar); values only, it is data, not code
+HIFIGAN_V1 = {
+    "resblock": "1",
+    "num_gpus": 0,
+    "batch_size": 16,
+    "learning_rate": 0.0002,
+    "adam_b1": 0.8,
+    "adam_b2": 0.99,
+    "lr_decay": 0.999,
+    "seed": 1234,
+    "upsample_rates": [8, 8, 2, 2],
+    "upsample_kernel_sizes": [16, 16, 4, 4],
+    "upsample_initial_channel": 512,
+    "resblock_kernel_sizes": [3, 7, 11],
+    "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+    "segment_size": 8192,
+    "num_mels": 80,
+    "num_freq": 1025,
+    "n_fft": 1024,
+    "hop_size": 256,
+    "win_size": 1024,
+    "sampling_rate": 22050,
+    "fmin": 0,
+    "fmax": 8000,
+    "fmax_for_loss": None,
+}
+# pre-tanh gain of the synthetic conv_post: waveform std ~0.3 with little tanh saturation on the V1 shapes (mel inputs of
+# O(1) magnitude, like the forward's postnet output)
+VOCODER_POST_GAIN = 2.0
+
+
+def hifigan_config(name: str = "v1") -> dict:
+    """hifigan/config.json of a named generator (a plain dict; vocoder.AttrDict wraps it like the reference does)."""
+    if name == "v1":
+        return copy.deepcopy(HIFIGAN_V1)
+    raise KeyError(name)
+
+
+def vocoder_flops_per_frame(h: dict) -> dict:
+    """Algorithmic FLOP (2 * MAC) per mel frame of each part of the generator, from the shapes: conv_pre, every upsample stage
+    (its transposed conv on the polyphase grid, k / u = 2 taps per output, plus its resblocks), conv_post."""
+    c0, n_mel = h["upsample_initial_channel"], h.get("num_mels", 80)
+    out = {"conv_pre": 2.0 * 7 * n_mel * c0}
+    s = 1
+    for i, u in enumerate(h["upsample_rates"]):
+        cin, ch = c0 >> i, c0 >> (i + 1)
+        s *= u
+        ups = 2.0 * s * 2 * cin * ch
+        rb = sum(2.0 * s * 2 * len(d) * k * ch * ch for k, d in zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"]))
+        out[f"stage{i}"] = ups + rb
+    out["conv_post"] = 2.0 * s * 7 * (c0 >> len(h["upsample_rates"]))
+    return out
+
+
+def synth_vocoder_state_dict(h: dict, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """Seeded generator weights in the checkpoint's weight-norm form (``weight_g`` / ``weight_v`` / ``bias`` per conv, the keys of
+    generator_*.pth.tar["generator"]).  v ~ U(+-1/sqrt(n)) over the n products one output sums (Cin * k), except the upsamplers
+    (n = 2 Cin products per output for k = 2u): U(+-sqrt(6/n)), the He gain for the leaky ReLU ahead of them, without which every
+    stage shrinks the signal ~2.4x; g = ||v|| (1 + 0.05 N(0, 1)) so that the fold is not the identity; biases U(+-0.05 / sqrt(n));
+    conv_post scaled by VOCODER_POST_GAIN.  Activations stay O(1) through the stack."""
+    rs = np.random.RandomState(seed)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+
+    def wn(prefix, shape, n, gain=1.0, transposed=False, bound=None):
+        v = _uniform(rs, shape, bound if bound is not None else 1.0 / math.sqrt(n))
+        red = tuple(range(1, v.ndim))
+        norm = np.sqrt((v.astype(np.float64) ** 2).sum(axis=red, keepdims=True))
+        g = norm * (1.0 + 0.05 * rs.standard_normal(norm.shape)) * gain
+        sd[prefix + ".weight_g"] = g.astype(np.float32)
+        sd[prefix + ".weight_v"] = v
+        nb = shape[1] if transposed else shape[0]
+        sd[prefix + ".bias"] = _uniform(rs, (nb,), 0.05 / math.sqrt(n))
+
+    c0, n_mel = h["upsample_initial_channel"], h.get("num_mels", 80)
+    wn("conv_pre", (c0, n_mel, 7), n_mel * 7)
+    nk = len(h["resblock_kernel_sizes"])
+    for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
+        cin, ch = c0 >> i, c0 >> (i + 1)
+        wn(f"ups.{i}", (cin, ch, k), 2 * cin, transposed=True, bound=math.sqrt(6.0 / (2 * cin)))
+        for j, (kk, dil) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
+            for n in range(len(dil)):
+                for w in ("convs1", "convs2"):
+                    wn(f"resblocks.{i * nk + j}.{w}.{n}", (ch, ch, kk), ch * kk)
+    wn("conv_post", (1, c0 >> len(h["upsample_rates"]), 7), (c0 >> len(h["upsample_rates"])) * 7, gain=VOCODER_POST_GAIN)
+    return sd

@@ -301,6 +301,18 @@ int ns_voc_abi_version(void);
  * that are multiples of 32 (i = 1 .. n_up) and n_mel a multiple of 16. */
 int ns_voc_create(const ns_voc_config* cfg, ns_vocoder** out);
 void ns_voc_destroy(ns_vocoder* v);
+/* Matmul mode of the GEMM layers (every upsampler and every resblock convs1 / convs2), valid only between ns_voc_create and
+ * ns_voc_bind_arena (fails after that, and for any mode but 0 and 1):
+ *   0  fp32 (the default when this is never called);
+ *   1  bf16, opt-in: the input leaky ReLU in fp32, then the activation rounded to bf16 (round to nearest even, a NaN stays a
+ *      NaN); the folded weights rounded to bf16 (RNE) once, at ns_voc_finalize_weights; products accumulated in fp32, every
+ *      output element one fp32 sum in a fixed k order whatever the batch or tile.  Bias, activations after the GEMM, the
+ *      residual, the multi-receptive-field sum / mean, every stored tensor, conv_pre and conv_post stay fp32.
+ * ns_voc_ws_bytes is the same in both modes. */
+int ns_voc_set_matmul(ns_vocoder* v, int mode);
+/* mode 0: the fp32 image, every tensor at a 256-byte aligned offset.  mode 1: the same image plus one bf16 plane per GEMM weight,
+ *   arena_bytes(1) = arena_bytes(0) + sum over W in {ups.{i}.weight, resblocks.{r}.convs{1,2}.{n}.weight} of
+ *                    roundup(2 * numel(W), 256). */
 size_t ns_voc_arena_bytes(const ns_vocoder* v);
 int ns_voc_bind_arena(ns_vocoder* v, void* dev_arena, size_t bytes);  /* 256-byte aligned */
 /* host float32 `weight` / `bias`; unknown keys and shape mismatches are errors.  check: the same validation, no side effect. */

@@ -79,6 +79,7 @@ SIGNATURES = {
     "ns_voc_abi_version": (_I, []),
     "ns_voc_create": (_I, [_P, C.POINTER(_P)]),
     "ns_voc_destroy": (None, [_P]),
+    "ns_voc_set_matmul": (_I, [_P, _I]),
     "ns_voc_arena_bytes": (_Z, [_P]),
     "ns_voc_bind_arena": (_I, [_P, _P, _Z]),
     "ns_voc_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),

@@ -198,9 +198,12 @@ struct VocGemm {
   long long out_ustride, out_shift;
   int in_act; float in_slope; int out_act; float out_slope;
   int mrf; float mrf_div;
+  const unsigned short* Wbf;  // "bf16" matmul mode: W rounded to bf16 (RNE), same packed layout (k_voc_gemm ignores it)
 };
 bool voc_gemm_ok(const VocGemm& p);
 hipError_t launch_voc_gemm(const VocGemm& p, hipStream_t st);
+// opt-in "bf16" matmul mode (vocoder_bf16.hip): the same GEMM from the bf16 plane p.Wbf and bf16-rounded activations, fp32 accumulation
+hipError_t launch_voc_gemm_bf16(const VocGemm& p, hipStream_t st);
 // wav[b, t] = tanh(bias[0] + sum_j sum_c lrelu(x[b, t + j - (KW-1)/2, c], slope) w[j C + c]) over [B, S, C] time-major x
 size_t voc_post_lds_bytes(int C, int KW);
 hipError_t launch_voc_post(const float* x, const float* w, const float* bias, float* wav, int B, int S, int C, int KW, float slope, hipStream_t st);

@@ -28,15 +28,18 @@ constexpr float POST_SLOPE = 0.01f;   // F.leaky_relu's default, what the genera
 constexpr int PRE_POST_K = 7;         // conv_pre / conv_post: kernel 7, padding 3
 constexpr int N_DIL = 3;              // ResBlock1: three (c1, c2) pairs
 
-struct Conv { size_t w = 0, b = 0; int cin = 0, cout = 0, k = 0, dil = 1; };
+struct Conv { size_t w = 0, b = 0, wbf = 0; int cin = 0, cout = 0, k = 0, dil = 1; };  // wbf: bf16 plane, bytes past the fp32 image
 struct Staged { std::vector<int64_t> shape; std::vector<float> data; bool set = false; };
 size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }  // floats: 256-byte aligned offsets
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }  // bytes
 }  // namespace
 
 struct ns_vocoder {
   ns_voc_config cfg;
   std::map<std::string, Staged> staged;
   size_t n_floats = 0;
+  size_t bf16_bytes = 0;  // the bf16 planes of matmul mode 1: one per upsampler and resblock conv weight, after the fp32 image
+  int matmul = 0;         // 0 fp32, 1 bf16 (ns_voc_set_matmul)
   Conv pre, post;
   std::vector<Conv> ups;     // polyphase weights [u Cout][2 Cin], bias [Cout]
   std::vector<Conv> c1, c2;  // [(n_rb i + j) * 3 + n]
@@ -44,6 +47,7 @@ struct ns_vocoder {
   bool ready = false;
 
   size_t take(size_t n) { size_t o = n_floats; n_floats += align64(n); return o; }
+  size_t take_bf16(size_t n) { size_t o = bf16_bytes; bf16_bytes += align256(n * 2); return o; }
   int ch(int i) const { return cfg.initial_channel >> i; }  // channels after upsampler i - 1 (ch(0) = C0)
   long long hop() const { long long h = 1; for (int i = 0; i < cfg.n_up; ++i) h *= cfg.up_rates[i]; return h; }
 };
@@ -90,7 +94,7 @@ extern "C" int ns_voc_create(const ns_voc_config* cfg, ns_vocoder** out) {
     expect(v, p + ".weight", {cin, cout, k});
     expect(v, p + ".bias", {cout});
     Conv q; q.cin = cin; q.cout = cout; q.k = k;
-    q.w = v->take((size_t)u * cout * 2 * cin); q.b = v->take(cout);
+    q.w = v->take((size_t)u * cout * 2 * cin); q.b = v->take(cout); q.wbf = v->take_bf16((size_t)u * cout * 2 * cin);
     v->ups.push_back(q);
     for (int j = 0; j < c.n_rb; ++j) {
       const int r = c.n_rb * i + j, kk = c.rb_kernels[j];
@@ -100,7 +104,7 @@ extern "C" int ns_voc_create(const ns_voc_config* cfg, ns_vocoder** out) {
           expect(v, p2 + ".weight", {cout, cout, kk});
           expect(v, p2 + ".bias", {cout});
           Conv w; w.cin = cout; w.cout = cout; w.k = kk; w.dil = which == 1 ? c.rb_dilations[j][n] : 1;
-          w.w = v->take((size_t)cout * cout * kk); w.b = v->take(cout);
+          w.w = v->take((size_t)cout * cout * kk); w.b = v->take(cout); w.wbf = v->take_bf16((size_t)cout * cout * kk);
           (which == 1 ? v->c1 : v->c2).push_back(w);
         }
     }
@@ -115,7 +119,17 @@ extern "C" int ns_voc_create(const ns_voc_config* cfg, ns_vocoder** out) {
 }
 
 extern "C" void ns_voc_destroy(ns_vocoder* v) { delete v; }
-extern "C" size_t ns_voc_arena_bytes(const ns_vocoder* v) { return v ? v->n_floats * sizeof(float) : 0; }
+extern "C" size_t ns_voc_arena_bytes(const ns_vocoder* v) {
+  return v ? v->n_floats * sizeof(float) + (v->matmul == 1 ? v->bf16_bytes : 0) : 0;
+}
+
+extern "C" int ns_voc_set_matmul(ns_vocoder* v, int mode) {
+  if (!v) return vfail("ns_voc_set_matmul: null vocoder");
+  if (mode != 0 && mode != 1) return vfail("ns_voc_set_matmul: mode must be 0 (fp32) or 1 (bf16), got " + std::to_string(mode));
+  if (v->arena) return vfail("ns_voc_set_matmul: the arena is already bound (call it between ns_voc_create and ns_voc_bind_arena)");
+  v->matmul = mode;
+  return 0;
+}
 
 extern "C" int ns_voc_bind_arena(ns_vocoder* v, void* dev, size_t bytes) {
   if (!v || !dev) return vfail("ns_voc_bind_arena: null argument");
@@ -210,7 +224,20 @@ extern "C" int ns_voc_finalize_weights(ns_vocoder* v, void* stream) {
   cp(v->post.b, "conv_post.bias");
   hipStream_t st = (hipStream_t)stream;
   VOC_HIP(hipMemcpyAsync(v->arena, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, st));
-  VOC_HIP(hipStreamSynchronize(st));  // img is a local
+  std::vector<unsigned short> bf;
+  if (v->matmul == 1) {  // every GEMM weight rounded to bf16 (RNE) once, in its packed layout
+    bf.assign(v->bf16_bytes / 2, 0);
+    auto rnd = [&](const Conv& w, int rows, int taps, int cin) { round_weights_bf16(&img[w.w], rows, taps, cin, &bf[w.wbf / 2]); };
+    for (int i = 0; i < c.n_up; ++i) {
+      rnd(v->ups[i], c.up_rates[i] * v->ups[i].cout, 2, v->ups[i].cin);
+      for (size_t idx = (size_t)c.n_rb * i * N_DIL; idx < (size_t)c.n_rb * (i + 1) * N_DIL; ++idx) {
+        rnd(v->c1[idx], v->c1[idx].cout, v->c1[idx].k, v->c1[idx].cin);
+        rnd(v->c2[idx], v->c2[idx].cout, v->c2[idx].k, v->c2[idx].cin);
+      }
+    }
+    VOC_HIP(hipMemcpyAsync((char*)v->arena + v->n_floats * sizeof(float), bf.data(), v->bf16_bytes, hipMemcpyHostToDevice, st));
+  }
+  VOC_HIP(hipStreamSynchronize(st));  // img and bf are locals
   for (auto& kv : v->staged) { kv.second.data.clear(); kv.second.data.shrink_to_fit(); kv.second.set = false; }
   v->ready = true;
   return 0;
@@ -218,11 +245,17 @@ extern "C" int ns_voc_finalize_weights(ns_vocoder* v, void* stream) {
 
 // ------------------------------------------------------------------------------------------------ launches
 static const float* A(const ns_vocoder* v, size_t off) { return v->arena + off; }
+// the bf16 plane of a GEMM weight in matmul mode 1, else nullptr (the fp32 kernel)
+static const unsigned short* Abf(const ns_vocoder* v, const Conv& w) {
+  return v->matmul == 1 ? (const unsigned short*)((const char*)v->arena + v->n_floats * sizeof(float) + w.wbf) : nullptr;
+}
+// every k_voc_gemm launch goes through here: the bf16 kernel when the weights have a bf16 plane
+static hipError_t voc_gemm(const VocGemm& p, hipStream_t st) { return p.Wbf ? launch_voc_gemm_bf16(p, st) : launch_voc_gemm(p, st); }
 
 // "same" Conv1d of the resblocks: [B, S, cin] -> [B, S, cout]
 static VocGemm same_conv(const ns_vocoder* v, const Conv& w, const float* x, int B, int S, float* y) {
   VocGemm p{};
-  p.X = x; p.W = A(v, w.w); p.bias = A(v, w.b); p.R = nullptr; p.Y = y;
+  p.X = x; p.W = A(v, w.w); p.Wbf = Abf(v, w); p.bias = A(v, w.b); p.R = nullptr; p.Y = y;
   p.B = B; p.S_in = S; p.Sg = S; p.Cin = w.cin; p.KW = w.k; p.dil = w.dil; p.off0 = -w.dil * (w.k - 1) / 2;
   p.N = w.cout; p.Cb = w.cout;
   p.out_ustride = (long long)S * w.cout; p.out_shift = 0;
@@ -235,13 +268,13 @@ static int upsample(const ns_vocoder* v, int i, const float* x, int B, int S, fl
   const Conv& w = v->ups[i];
   const int u = v->cfg.up_rates[i];
   VocGemm p{};
-  p.X = x; p.W = A(v, w.w); p.bias = A(v, w.b); p.R = nullptr; p.Y = y;
+  p.X = x; p.W = A(v, w.w); p.Wbf = Abf(v, w); p.bias = A(v, w.b); p.R = nullptr; p.Y = y;
   p.B = B; p.S_in = S; p.Sg = S + 1; p.Cin = w.cin; p.KW = 2; p.dil = 1; p.off0 = -1;
   p.N = u * w.cout; p.Cb = w.cout;
   p.out_ustride = (long long)S * u * w.cout; p.out_shift = (long long)(u / 2) * w.cout;
   p.in_act = 1; p.in_slope = LRELU_SLOPE; p.out_act = 0; p.out_slope = LRELU_SLOPE;
   p.mrf = 0; p.mrf_div = 1.f;
-  VOC_HIP(launch_voc_gemm(p, st));
+  VOC_HIP(voc_gemm(p, st));
   return 0;
 }
 
@@ -256,7 +289,7 @@ static int stage(const ns_vocoder* v, int i, const float* x, int B, int S, float
       const float* in = n == 0 ? U : CUR;
       VocGemm p1 = same_conv(v, v->c1[idx], in, B, So, H);
       p1.out_act = 1;  // lrelu(c1(.), 0.1): c2's input
-      VOC_HIP(launch_voc_gemm(p1, st));
+      VOC_HIP(voc_gemm(p1, st));
       VocGemm p2 = same_conv(v, v->c2[idx], H, B, So, n == N_DIL - 1 ? xs : CUR);
       p2.in_act = 0;
       p2.R = in;
@@ -264,7 +297,7 @@ static int stage(const ns_vocoder* v, int i, const float* x, int B, int S, float
         p2.mrf = j == 0 ? 0 : (j == c.n_rb - 1 ? 2 : 1);
         p2.mrf_div = (float)c.n_rb;
       }
-      VOC_HIP(launch_voc_gemm(p2, st));
+      VOC_HIP(voc_gemm(p2, st));
     }
   }
   return 0;
@@ -354,7 +387,7 @@ extern "C" int ns_voc_op_conv(ns_vocoder* v, const char* name_c, const float* x,
       (which != 1 && which != 2) || n < 0 || n >= N_DIL)
     return vfail("ns_voc_op_conv: unknown module '" + name + "' (conv_pre, conv_post or resblocks.{r}.convs{1,2}.{n})");
   const Conv& w = (which == 1 ? v->c1 : v->c2)[r * N_DIL + n];
-  VOC_HIP(launch_voc_gemm(same_conv(v, w, x, B, S, out), st));
+  VOC_HIP(voc_gemm(same_conv(v, w, x, B, S, out), st));
   return 0;
 }
 

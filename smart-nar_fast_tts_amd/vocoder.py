@@ -19,6 +19,7 @@ from . import _lib
 DEFAULT_VOCODER = {"model": "HiFi-GAN", "speaker": "LJSpeech"}  # config/LJSpeech/model.yaml `vocoder`
 MAX_WAV_VALUE = 32768.0  # config/LJSpeech/preprocess.yaml preprocessing.audio.max_wav_value
 HOP_LENGTH = 256         # config/LJSpeech/preprocess.yaml preprocessing.stft.hop_length
+MATMUL_MODES = {"fp32": 0, "bf16": 1}  # ns_voc_set_matmul
 
 
 class AttrDict(dict):
@@ -71,17 +72,26 @@ class Generator:
     ``weight_g`` / ``weight_v`` pairs, folded here exactly like ``remove_weight_norm`` — or plain ``weight`` tensors; unknown keys and
     shape mismatches raise before anything loaded is replaced.  ``remove_weight_norm()`` is then a no-op.
 
+    ``matmul="bf16"`` (opt-in) runs every upsampler and resblock convolution on the bf16 matrix cores: weights and the activated
+    inputs rounded to bf16 (round to nearest even), products summed in fp32; everything else stays fp32 (include/nar_fs2.h
+    ns_voc_set_matmul).  The default "fp32" path is the one the library runs without the call.
+
     Threading: one instance serves one host thread at a time; several HIP streams from that thread are fine (one workspace each)."""
 
     MAX_WORKSPACE_STREAMS = 4
 
-    def __init__(self, h):
+    def __init__(self, h, matmul: str = "fp32"):
+        if matmul not in MATMUL_MODES:
+            raise ValueError(f"matmul must be one of {sorted(MATMUL_MODES)}, got {matmul!r}")
         self.h = h if isinstance(h, AttrDict) else AttrDict(h)
         self._lib = _lib.load()
         self._cfg = config_struct(self.h)
         hd = C.c_void_p()
         _lib.check(self._lib.ns_voc_create(C.byref(self._cfg), C.byref(hd)), "Generator")
         self._h = hd
+        self.matmul = matmul
+        if matmul != "fp32":
+            _lib.check(self._lib.ns_voc_set_matmul(self._h, MATMUL_MODES[matmul]), "Generator")
         self.hop = int(np.prod(self.h["upsample_rates"]))
         self.n_mel = int(self._cfg.n_mel)
         self._device = None
@@ -291,9 +301,10 @@ class Generator:
         return out
 
 
-def get_vocoder(model_config, device, config_path: str = "hifigan/config.json", ckpt_path=None):
+def get_vocoder(model_config, device, config_path: str = "hifigan/config.json", ckpt_path=None, matmul=None):
     """utils/model.py:38-67 for "HiFi-GAN": Generator(AttrDict(config.json)), load ckpt["generator"], eval(), remove_weight_norm(),
     to(device).  ``ckpt_path`` defaults to the reference's hifigan/generator_{LJSpeech,universal}.pth.tar by speaker.
+    ``matmul`` ("fp32" | "bf16") defaults to ``model_config["vocoder"].get("matmul", "fp32")``.
     "MelGAN" raises: the reference fetches it with torch.hub."""
     voc = model_config.get("vocoder", DEFAULT_VOCODER)
     name, speaker = voc["model"], voc.get("speaker", "LJSpeech")
@@ -301,9 +312,11 @@ def get_vocoder(model_config, device, config_path: str = "hifigan/config.json", 
         raise NotImplementedError("MelGAN is loaded through torch.hub by the reference; only HiFi-GAN has a native implementation")
     if name != "HiFi-GAN":
         raise ValueError(f"unknown vocoder {name!r}")
+    if matmul is None:
+        matmul = voc.get("matmul", "fp32")
     with open(config_path, "r") as f:
         config = AttrDict(json.load(f))
-    vocoder = Generator(config)
+    vocoder = Generator(config, matmul=matmul)
     if ckpt_path is None:
         if speaker == "LJSpeech":
             ckpt_path = "hifigan/generator_LJSpeech.pth.tar"

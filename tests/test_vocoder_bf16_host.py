@@ -1,0 +1,85 @@
+"""CPU-only checks of the opt-in bf16 matmul mode of the HiFi-GAN vocoder (Generator(h, matmul="bf16"), ns_voc_set_matmul):
+construction without a device, mode validation, the arena growth by the documented bf16-plane formula, the unchanged workspace,
+and the register gate of csrc/vocoder_bf16.hip.  The GPU side is tests/test_gpu_vocoder_bf16.py."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import smart_nar_fast_tts_amd.workload as wl  # noqa: E402
+
+pytestmark = pytest.mark.filterwarnings("ignore::FutureWarning")
+
+
+@pytest.fixture(scope="module")
+def V():
+    from smart_nar_fast_tts_amd import vocoder
+
+    return vocoder
+
+
+@pytest.fixture(scope="module")
+def h():
+    return wl.hifigan_config("v1")
+
+
+def test_bf16_generator_constructs_without_a_device(V, h):
+    g = V.Generator(h, matmul="bf16")
+    assert g.matmul == "bf16" and g.hop == 256
+    assert V.Generator(h).matmul == "fp32"
+
+
+@pytest.mark.parametrize("bad", ["bf32", "fp16", "BF16", "", None, 1])
+def test_bad_matmul_mode_raises(V, h, bad):
+    with pytest.raises(ValueError, match="bf16.*fp32|fp32.*bf16"):
+        V.Generator(h, matmul=bad)
+
+
+def test_set_matmul_rejects_other_modes(V, h):
+    g = V.Generator(h)
+    lib = g._lib
+    for mode in (2, -1, 16):
+        assert lib.ns_voc_set_matmul(g._h, mode) != 0
+        assert b"mode must be 0 (fp32) or 1 (bf16)" in lib.ns_last_error()
+    assert lib.ns_voc_set_matmul(None, 1) != 0
+    assert lib.ns_voc_set_matmul(g._h, 1) == 0 and lib.ns_voc_set_matmul(g._h, 0) == 0  # either way before bind_arena
+
+
+def _bf16_plane_bytes(h):
+    """include/nar_fs2.h: sum of roundup(2 numel(W), 256) over ups.{i}.weight and resblocks.{r}.convs{1,2}.{n}.weight"""
+    c0, total = h["upsample_initial_channel"], 0
+    r256 = lambda n: (n + 255) // 256 * 256  # noqa: E731
+    for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
+        cin, cout = c0 >> i, c0 >> (i + 1)
+        total += r256(2 * cin * cout * k)
+        for kk in h["resblock_kernel_sizes"]:
+            total += 6 * r256(2 * cout * cout * kk)  # three dilations x (convs1, convs2)
+    return total
+
+
+@pytest.mark.parametrize("name", ["v1", "small"])
+def test_arena_grows_by_the_bf16_planes_and_ws_is_unchanged(V, h, name):
+    hh = h if name == "v1" else dict(h, upsample_initial_channel=128, upsample_rates=[4, 4], upsample_kernel_sizes=[8, 8],
+                                      resblock_kernel_sizes=[3, 5], resblock_dilation_sizes=[[1, 3, 5], [1, 2, 3]])
+    a, b = V.Generator(hh), V.Generator(hh, matmul="bf16")
+    na, nb = a._lib.ns_voc_arena_bytes(a._h), b._lib.ns_voc_arena_bytes(b._h)
+    assert nb - na == _bf16_plane_bytes(hh), (na, nb)
+    assert na % 256 == 0 and nb % 256 == 0
+    for B, T in ((1, 1), (3, 33), (16, 1013)):
+        assert a.ws_bytes(B, T) == b.ws_bytes(B, T) > 0
+    for i in range(len(hh["upsample_rates"])):
+        assert a._lib.ns_voc_op_stage_ws_bytes(a._h, i, 3, 33) == b._lib.ns_voc_op_stage_ws_bytes(b._h, i, 3, 33)
+    assert a._lib.ns_voc_abi_version() == 1 and a._lib.ns_abi_version() == 6
+
+
+def test_vocoder_bf16_kernels_do_not_spill():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
+                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "vocoder_bf16.hip"), "--assert-no-spill"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    assert r.stdout.count("k_voc_gemm_bf16<") == 4, r.stdout

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """HiFi-GAN vocoder (smart_nar_fast_tts_amd.vocoder) on one MI355X: whole-generator time, per-stage kernel time, FLOP from the
-shapes and each stage's share of the fp32 MFMA peak, the same generator run by torch-ROCm's own conv1d as a comparison line, and
-(--accuracy) the per-layer distance from a float64 evaluation relative to the CPU's own fp32 run.
+shapes and each stage's share of the MFMA peak of its matmul mode (fp32, or the bf16 dense peak with --matmul bf16), the same
+generator run by torch-ROCm's own conv1d as a comparison line, and (--accuracy) the per-layer distance from a float64 evaluation
+relative to the CPU's own fp32 run — or, with --matmul bf16, the per-layer distance to the CPU bf16 emulation and the
+whole-generator SNR against float64 and against the fp32 GPU run.
 
-    python tools/vocoder_bench.py --workload cfg2_b16 --steps 5 --warmup 2 [--torch] [--accuracy] [--json out.json]
+    python tools/vocoder_bench.py --workload cfg2_b16 --steps 5 --warmup 2 [--matmul bf16] [--torch] [--accuracy] [--json out.json]
 
 The mel comes from the real FastSpeech2Align forward with the synthetic weights of the workload (bench.py's inputs), transposed
 the way synth_samples hands it over: a [B, 80, T] view of the [B, T, 80] postnet output.  Nothing here runs without the GPU."""
@@ -21,6 +23,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 F32_MFMA_PEAK_TFLOPS = 157.3  # MI355X fp32 matrix peak (v_mfma_f32_32x32x2_f32)
+BF16_MFMA_PEAK_TFLOPS = 16 * F32_MFMA_PEAK_TFLOPS  # dense bf16 matrix peak (~2.5 PF, 16x the fp32 MFMA rate)
 HBM_PEAK_GBS = 8000.0
 
 
@@ -68,11 +71,12 @@ def bench(args):
 
     h = wl.hifigan_config("v1")
     sd = wl.synth_vocoder_state_dict(h, seed=0)
-    gen = Generator(h).to("cuda").eval()
+    gen = Generator(h, matmul=args.matmul).to("cuda").eval()
     gen.load_state_dict(sd)
     mel, mel_lens = mel_from_forward(args.workload)
     B, _, T = mel.shape
-    res = {"workload": args.workload, "B": int(B), "T_pad": int(T), "valid_frames": int(mel_lens.sum()),
+    peak, frac = (BF16_MFMA_PEAK_TFLOPS, "frac_bf16_mfma_peak") if args.matmul == "bf16" else (F32_MFMA_PEAK_TFLOPS, "frac_fp32_mfma_peak")
+    res = {"workload": args.workload, "matmul": args.matmul, "B": int(B), "T_pad": int(T), "valid_frames": int(mel_lens.sum()),
            "mel_std": round(float(mel.std()), 4)}
     with torch.no_grad():
         med, lo, hi = events_ms(lambda: gen(mel), args.steps, args.warmup)
@@ -82,7 +86,7 @@ def bench(args):
     res.update({"ms_per_batch": round(med, 3), "ms_min": round(lo, 3), "ms_max": round(hi, 3),
                 "audio_seconds_per_second": round(audio_s / (med / 1e3), 1),
                 "gflop_per_batch": round(flops / 1e9, 1), "tflops": round(flops / (med / 1e3) / 1e12, 2),
-                "frac_fp32_mfma_peak": round(flops / (med / 1e3) / 1e12 / F32_MFMA_PEAK_TFLOPS, 3)})
+                frac: round(flops / (med / 1e3) / 1e12 / peak, 3)})
     # per stage: the same kernels the forward runs, one entry point each, timed with device events
     x = mel.transpose(1, 2).contiguous()
     stages = {}
@@ -97,7 +101,7 @@ def bench(args):
             f = fl[f"stage{i}"] * B * T
             by = stage_bytes(B, S, cin, u, ch)
             stages[f"stage{i}"] = {"ms": round(t, 3), "gflop": round(f / 1e9, 1), "tflops": round(f / (t / 1e3) / 1e12, 2),
-                                   "frac_fp32_mfma_peak": round(f / (t / 1e3) / 1e12 / F32_MFMA_PEAK_TFLOPS, 3),
+                                   frac: round(f / (t / 1e3) / 1e12 / peak, 3),
                                    "min_hbm_gb": round(by / 1e9, 2), "frac_hbm_peak": round(by / (t / 1e3) / 1e9 / HBM_PEAK_GBS, 3)}
             y = gen.op_stage(i, y)
             S *= u
@@ -120,6 +124,8 @@ def bench(args):
 
 def accuracy(args):
     """per layer: worst |y - f64| / conv(|x|, |W|) of the GPU and of torch's CPU fp32, and their ratio (B = 3, 33 frames)"""
+    if args.matmul == "bf16":
+        return accuracy_bf16(args)
     import smart_nar_fast_tts_amd.workload as wl
     from smart_nar_fast_tts_amd.vocoder import Generator
     from tests import hifigan_cpu
@@ -171,6 +177,66 @@ def accuracy(args):
     return {"layers": rows, "generator": whole}
 
 
+def accuracy_bf16(args):
+    """bf16 mode.  Per layer (B = 3, 33 frames): worst |gpu - emu| / (conv(|a_bf16|, |w_bf16|) + |bias|), emu = the CPU bf16
+    emulation of tests/hifigan_bf16_emu.py in float64 (only the fp32 summation order differs), next to the 2^-9 of one bf16
+    rounding.  Whole generator: waveform SNR against float64 and against the fp32 GPU run, and the emulation's own SNR."""
+    import smart_nar_fast_tts_amd.workload as wl
+    from smart_nar_fast_tts_amd.vocoder import Generator
+    from tests import hifigan_cpu
+    from tests.hifigan_bf16_emu import bf, emulation, snr_db
+    from tests.hifigan_bf16_emu import lrelu32 as _lrelu32
+
+    h = wl.hifigan_config("v1")
+    sd = wl.synth_vocoder_state_dict(h, seed=0)
+    gen = Generator(h, matmul="bf16").to("cuda").eval()
+    gen.load_state_dict(sd)
+    g32 = Generator(h).to("cuda").eval()
+    g32.load_state_dict(sd)
+    r64, emu = hifigan_cpu.folded(h, sd, torch.float64), emulation(h, sd)
+    rs = np.random.RandomState(1)
+    rows, S = [], 33
+
+    def row(name, K, g, ref, unit):
+        return {"layer": name, "K": K, "gpu_vs_emu": float(((g.double() - ref).abs() / unit.clamp_min(1e-30)).max())}
+
+    for i in range(4):
+        S_i = S * int(np.prod(h["upsample_rates"][:i]))
+        up = emu.ups[i]
+        u, k = h["upsample_rates"][i], h["upsample_kernel_sizes"][i]
+        x = torch.from_numpy(rs.standard_normal((3, S_i, up.in_channels)).astype(np.float32))
+        a = bf(_lrelu32(x)).double().transpose(1, 2)
+        kw = dict(stride=u, padding=(k - u) // 2)
+        ref = F.conv_transpose1d(a, up.weight.detach(), up.bias.detach(), **kw).transpose(1, 2)
+        unit = F.conv_transpose1d(a.abs(), up.weight.detach().abs(), up.bias.detach().abs(), **kw).transpose(1, 2)
+        rows.append(row(f"ups.{i}", 2 * up.in_channels, gen.op_upsample(i, x.cuda()).cpu(), ref, unit))
+        for j in range(3):
+            rb = 3 * i + j
+            for n in range(3):
+                for which in (1, 2):
+                    conv = getattr(emu.resblocks[rb], f"convs{which}")[n]
+                    ch, kk = conv.in_channels, conv.kernel_size[0]
+                    x = torch.from_numpy(rs.standard_normal((3, S_i * u, ch)).astype(np.float32))
+                    a = bf(_lrelu32(x)).double().transpose(1, 2)
+                    kw = dict(padding=conv.padding[0], dilation=conv.dilation[0])
+                    ref = F.conv1d(a, conv.weight.detach(), conv.bias.detach(), **kw).transpose(1, 2)
+                    unit = F.conv1d(a.abs(), conv.weight.detach().abs(), conv.bias.detach().abs(), **kw).transpose(1, 2)
+                    g = gen.op_conv(f"resblocks.{rb}.convs{which}.{n}", x.cuda()).cpu()
+                    rows.append(row(f"resblocks.{rb}.convs{which}.{n}", ch * kk, g, ref, unit))
+    whole = {}
+    mels = {"ragged_N(0,1)_B3_T33": torch.from_numpy(rs.standard_normal((3, 80, S)).astype(np.float32)),
+            "N(0,0.56^2)_B2_T48": torch.from_numpy((0.56 * np.random.RandomState(1).standard_normal((2, 80, 48))).astype(np.float32))}
+    for name, mel in mels.items():
+        with torch.no_grad():
+            ref = r64(mel.double())[:, 0]
+            e = emu(mel.double())[:, 0]
+        g = gen(mel.cuda())[:, 0].cpu().double()
+        f = g32(mel.cuda())[:, 0].cpu().double()
+        whole[name] = {"wav_std": float(ref.std()), "snr_db_vs_f64": snr_db(ref, g), "snr_db_vs_fp32_gpu": snr_db(f, g),
+                       "emu_snr_db_vs_f64": snr_db(ref, e), "max_abs_vs_f64": float((g - ref).abs().max())}
+    return {"matmul": "bf16", "layers": rows, "generator": whole}
+
+
 def _acc_row(name, K, g, c32, ref, unit):
     eg = float(((g.double() - ref).abs() / unit.clamp_min(1e-30)).max())
     ec = float(((c32.double() - ref).abs() / unit.clamp_min(1e-30)).max())
@@ -182,6 +248,7 @@ def main():
     ap.add_argument("--workload", default="cfg2_b16")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--matmul", choices=("fp32", "bf16"), default="fp32", help="the Generator's matmul mode")
     ap.add_argument("--torch", action="store_true", help="also time the same generator on torch-ROCm's conv1d (comparison line)")
     ap.add_argument("--accuracy", action="store_true", help="per-layer float64 distances instead of timing")
     ap.add_argument("--json", default="")

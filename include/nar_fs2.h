@@ -226,6 +226,16 @@ int ns_op_ffn_conv1(ns_model* m, const char* prefix, const float* x, int B, int 
  * (single-utterance latency); 8 * (B*S*H*dk + 2*B*S*H) floats always suffice. */
 int ns_op_attention_core(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
                          size_t scratch_bytes, void* stream);
+/* The same with the precision mode chosen by the caller: bf16 = 0 is ns_op_attention_core, bf16 = 1 the "bf16" mode's attention
+ * (Q K^T and P V from operands rounded to bf16, fp32 softmax: the kernels a bf16 model's decoder layers run). */
+int ns_op_attention_core_mode(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
+                              size_t scratch_bytes, void* stream, int bf16);
+/* One named contraction alone, for tests: x [B*S, Cin] -> out [B*S, N] on the dense grid (zero padding per utterance of S rows),
+ * in the model's precision mode and through the forward's own dispatch, with bias and the layer's activation (ReLU for w_1, tanh
+ * for every PostNet layer but the last) and neither residual nor LayerNorm.  name: "<layer prefix>.slf_attn.qkv" (N = 3 d: Q | K |
+ * V), "<layer prefix>.slf_attn.fc", "<layer prefix>.pos_ffn.w_1", "<layer prefix>.pos_ffn.w_2", "mel_linear",
+ * "postnet.convolutions.<i>" (BatchNorm folded); any other name is an error. */
+int ns_op_gemm(ns_model* m, const char* name, const float* x, int B, int S, float* out, void* stream);
 
 /* Introspection of the step-aware launch plan (csrc/gemm_conv.hip plan_rows, csrc/attention.hip plan_key_split); host-side, no GPU
  * needed.  ns_plan_gemm: how a plain Conv1D-as-GEMM of M rows, N output channels, kernel size KW over Cin input channels
@@ -251,6 +261,15 @@ int ns_acc_chunk(void);
  * (round 5 grew ns_plan_gemm's out[6] to out[8]). */
 int ns_abi_version(void);
 int ns_plan_attention_split(int B, int S, int H, int dk);
+/* the tile (rows x columns: 256x256, 128x256, 64x128 or 64x64) a plain "bf16"-mode GEMM of M rows and N output channels is
+ * launched with (csrc/gemm_bf16.hip conv_gemm_bf16_plan; every tile gives the same bits).  Host-side, no GPU needed. */
+int ns_plan_gemm_bf16(int M, int N, int32_t* bm, int32_t* bn);
+/* 1 when the "bf16"-mode GEMM + LayerNorm of M rows, N columns takes the 64 x 256 full-row LayerNorm tile, 0 when it runs the
+ * plain GEMM followed by the row kernel (same bits either way). */
+int ns_plan_gemm_bf16_ln(int M, int N, int Cin, int KW);
+/* bytes of scratch with which ns_op_attention_core[_mode] splits its keys exactly as a model's own attention of this shape
+ * does (the partials its workspace reserves plus the op's ticket block); 0 = pass no scratch. */
+size_t ns_op_attention_scratch_bytes(int B, int S, int H, int dk);
 
 /* Measurement hook for bench.py's roofline legs: while enabled, the launches of the three heaviest kernels inside
  * ns_forward_mel carry hipEvents ON THEIR OWN DISPATCH PACKETS (hipExtLaunchKernel start / stop events: the kernel's begin and

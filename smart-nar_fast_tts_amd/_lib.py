@@ -72,6 +72,11 @@ SIGNATURES = {
     "ns_op_postnet": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P]),
     "ns_op_ffn_conv1": (_I, [_P, _S, _P, _I, _I, _P, _P]),
     "ns_op_attention_core": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "ns_op_attention_core_mode": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _Z, _P, _I]),
+    "ns_op_gemm": (_I, [_P, _S, _P, _I, _I, _P, _P]),
+    "ns_plan_gemm_bf16": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ns_plan_gemm_bf16_ln": (_I, [_I, _I, _I, _I]),
+    "ns_op_attention_scratch_bytes": (_Z, [_I, _I, _I, _I]),
     "ns_profile_enable": (_I, [_P, _I]),
     "ns_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ns_profile_read_slot": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -1124,9 +1124,12 @@ static int find_layer(ns_model* m, const char* prefix_c, const LayerW** L, int* 
   }
   const bool enc = starts_with(p, "txt_encoder.layer_stack."), dec = starts_with(p, "mel_decoder.layer_stack.");
   if (!enc && !dec) return fail("unknown module prefix '" + std::string(prefix_c ? prefix_c : "") + "'");
-  const int idx = atoi(p.c_str() + (enc ? strlen("txt_encoder.layer_stack.") : strlen("mel_decoder.layer_stack.")));
+  const char* num = p.c_str() + (enc ? strlen("txt_encoder.layer_stack.") : strlen("mel_decoder.layer_stack."));
+  char* end = nullptr;
+  const long idx = strtol(num, &end, 10);
+  if (end == num || *end != 0 || *num < '0' || *num > '9') return fail("no layer index in '" + std::string(prefix_c ? prefix_c : "") + "'");
   auto& v = enc ? m->enc : m->dec;
-  if (idx < 0 || idx >= (int)v.size()) return fail("layer index out of range in '" + p + "'");
+  if (idx < 0 || idx >= (long)v.size()) return fail("layer index out of range in '" + p + "'");
   *L = &v[idx];
   *d = enc ? m->cfg.d_enc : m->cfg.d_dec;
   *H = enc ? m->cfg.n_enc_head : m->cfg.n_dec_head;
@@ -1286,8 +1289,8 @@ extern "C" int ns_op_postnet(ns_model* m, const float* mel, int B, int T, float*
   NS_OP_PROLOGUE(B, T);
   return postnet(m, mel, B, T, nullptr, out, sc, st);
 }
-extern "C" int ns_op_attention_core(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
-                                    size_t scratch_bytes, void* stream) {
+extern "C" int ns_op_attention_core_mode(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
+                                         size_t scratch_bytes, void* stream, int bf16) {
   // the strip kernel's tickets are carved from the END of the caller's scratch and zeroed here (a forward's opening kernel
   // does that for its own launches)
   float* sp = (float*)scratch;
@@ -1299,7 +1302,77 @@ extern "C" int ns_op_attention_core(const float* qkv, const int64_t* lens, int B
     tickets = (int*)(sp + floats);
     NS_HIP(hipMemsetAsync(tickets, 0, tk * sizeof(int), (hipStream_t)stream));
   }
-  NS_HIP(launch_attention(qkv, (const long long*)lens, B, S, H, dk, out, sp, floats, tickets, (hipStream_t)stream));
+  NS_HIP(launch_attention(qkv, (const long long*)lens, B, S, H, dk, out, sp, floats, tickets, (hipStream_t)stream, nullptr, nullptr, bf16 != 0));
+  return 0;
+}
+extern "C" int ns_op_attention_core(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
+                                    size_t scratch_bytes, void* stream) {
+  return ns_op_attention_core_mode(qkv, lens, B, S, H, dk, out, scratch, scratch_bytes, stream, 0);
+}
+// One named contraction alone, in the model's precision mode, through the forward's own gemm() dispatch (a bf16 model's decoder /
+// mel_linear / PostNet weight takes launch_conv_gemm_bf16 with that weight's plane): bias and the layer's activation, no residual,
+// no LayerNorm, dense [B, S] grid.  For tests that bound one contraction elementwise.
+extern "C" int ns_op_gemm(ns_model* m, const char* name_c, const float* x, int B, int S, float* out, void* stream) {
+  NS_TRY(check_ready(m));
+  if (!name_c || !x || !out) return fail("ns_op_gemm: null argument");
+  if (B <= 0 || S <= 0) return fail("ns_op_gemm: empty input");
+  const ns_config& c = m->cfg;
+  const std::string name(name_c);
+  auto plane = [&](size_t off) { return off != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(off)) : nullptr; };
+  Scratch sc;
+  memset(&sc, 0, sizeof(sc));  // (a plain GEMM on the dense grid: no temporaries, no packed context)
+  hipStream_t st = (hipStream_t)stream;
+  const int M = B * S;
+  if (name == "mel_linear")
+    return gemm(sc, x, c.d_dec, m->P(m->mel_w), m->P(m->mel_b), nullptr, 0, out, c.n_mel, M, c.n_mel, c.d_dec, 1, S, ACT_NONE, st, nullptr,
+                EPI_NONE, nullptr, nullptr, plane(m->mel_bf));
+  if (starts_with(name, "postnet.convolutions.")) {
+    const char* num = name_c + strlen("postnet.convolutions.");
+    char* end = nullptr;
+    const long i = strtol(num, &end, 10);
+    if (end == num || *end != 0 || i < 0 || i >= (long)m->post.size()) return fail("ns_op_gemm: unknown contraction '" + name + "'");
+    const PostW& w = m->post[i];
+    const bool last = (size_t)i + 1 == m->post.size();
+    return gemm(sc, x, w.cin, m->P(w.w), m->P(w.b), nullptr, 0, out, w.cout, M, w.cout, w.cin, c.postnet_k, S, last ? ACT_NONE : ACT_TANH, st,
+                nullptr, EPI_NONE, plane(w.w_b3), nullptr, plane(w.w_bf));
+  }
+  static const char* kSuffix[4] = {".slf_attn.qkv", ".slf_attn.fc", ".pos_ffn.w_1", ".pos_ffn.w_2"};
+  for (int which = 0; which < 4; ++which) {
+    if (!ends_with(name, kSuffix[which])) continue;
+    const LayerW* L; int d, H;
+    NS_TRY(find_layer(m, name_c, &L, &d, &H, kSuffix[which]));
+    if (which == 0)
+      return gemm(sc, x, d, m->P(L->qkv_w), m->P(L->qkv_b), nullptr, 0, out, 3 * d, M, 3 * d, d, 1, S, ACT_NONE, st, nullptr, EPI_NONE,
+                  plane(L->qkv_b3), nullptr, plane(L->qkv_bf));
+    if (which == 1)
+      return gemm(sc, x, d, m->P(L->fc_w), m->P(L->fc_b), nullptr, 0, out, d, M, d, d, 1, S, ACT_NONE, st, nullptr, EPI_NONE,
+                  plane(L->fc_b3), nullptr, plane(L->fc_bf));
+    if (which == 2)
+      return gemm(sc, x, d, m->P(L->w1), m->P(L->w1_b), nullptr, 0, out, c.d_inner, M, c.d_inner, d, c.ffn_k1, S, ACT_RELU, st, nullptr,
+                  EPI_NONE, plane(L->w1_b3), nullptr, plane(L->w1_bf));
+    return gemm(sc, x, c.d_inner, m->P(L->w2), m->P(L->w2_b), nullptr, 0, out, d, M, d, c.d_inner, c.ffn_k2, S, ACT_NONE, st, nullptr,
+                EPI_NONE, plane(L->w2_b3), nullptr, plane(L->w2_bf));
+  }
+  return fail("ns_op_gemm: unknown contraction '" + name + "'");
+}
+// Scratch ns_op_attention_core[_mode] needs to split its keys exactly as a model's own attention of this shape does: the
+// partials carve() reserves (attention_split ranges) plus the zeroed ticket block the op takes from the end of its scratch;
+// 0 when the workspace holds no partials (the model then passes no scratch at all).
+extern "C" size_t ns_op_attention_scratch_bytes(int B, int S, int H, int dk) {
+  if (B <= 0 || S <= 0 || H <= 0 || dk <= 0) return 0;
+  const int nsp = attention_split(B, S, H, dk);
+  if (nsp <= 1) return 0;
+  const size_t M = (size_t)B * S, tk = ((size_t)attention_ticket_ints(B, S, H) + 63) & ~(size_t)63;
+  return ((size_t)nsp * (M * H * dk + 2 * M * H) + tk) * sizeof(float);
+}
+// 1 when a bf16-mode GEMM + LayerNorm of this shape takes the 64 x 256 full-row tile, 0 when it runs the plain GEMM and k_layernorm
+extern "C" int ns_plan_gemm_bf16_ln(int M, int N, int Cin, int KW) { return conv_gemm_bf16_ok(M, N, Cin, KW, EPI_LN) ? 1 : 0; }
+// the tile launch_conv_gemm_bf16 takes for a plain launch of M rows and N columns (csrc/gemm_bf16.hip conv_gemm_bf16_plan)
+extern "C" int ns_plan_gemm_bf16(int M, int N, int32_t* bm, int32_t* bn) {
+  if (M <= 0 || N <= 0 || !bm || !bn) return fail("ns_plan_gemm_bf16: bad argument");
+  int a = 0, b = 0;
+  conv_gemm_bf16_plan(M, N, &a, &b);
+  *bm = a; *bn = b;
   return 0;
 }
 extern "C" int ns_op_ffn_conv1(ns_model* m, const char* prefix, const float* x, int B, int S, float* hidden, void* stream) {

@@ -197,17 +197,68 @@ def ffn_conv1(model, prefix, x, out=None):
     return out
 
 
-def attention_core(qkv, lens, n_head: int, split_scratch: bool = True):
+def attention_core(qkv, lens, n_head: int, split_scratch=True, bf16: bool = False):
     """ScaledDotProductAttention on already-projected, head-packed q/k/v (transformer/Modules.py:14-25):
     qkv [B,S,3*d] (Q | K | V, head h at h*dk inside each) -> merged heads [B,S,d].  ``split_scratch`` hands the
-    kernel the scratch it needs to take its split-key path on small grids."""
+    kernel the scratch it needs to take its split-key path on small grids; ``"workspace"`` hands it what a model's own workspace
+    holds for this shape (sized by the library, ``ns_op_attention_scratch_bytes``), so the launch splits its keys as the model's
+    attention does.  ``bf16`` runs the "bf16" precision mode's kernels (what a bf16 model's decoder layers run): Q K^T and P V
+    from operands rounded to bf16, the softmax in fp32."""
     lib = _lib.load()
     B, S, d3 = qkv.shape
     d = d3 // 3
     qkv = qkv.contiguous()
     out = torch.empty(B, S, d, dtype=torch.float32, device=qkv.device)
     lens_p = _lib.ptr(lens.long().contiguous()) if lens is not None else _lib.ptr(None)
-    scratch = torch.empty(8 * (B * S * d + 2 * B * S * n_head), dtype=torch.float32, device=qkv.device) if split_scratch else None
-    _lib.check(lib.ns_op_attention_core(_lib.ptr(qkv), lens_p, B, S, n_head, d // n_head, _lib.ptr(out), _lib.ptr(scratch),
-                                        0 if scratch is None else scratch.numel() * 4, _st(qkv)), "attention_core")
+    if split_scratch == "workspace":
+        floats = int(lib.ns_op_attention_scratch_bytes(B, S, n_head, d // n_head)) // 4
+    else:
+        floats = 8 * (B * S * d + 2 * B * S * n_head) if split_scratch else 0
+    scratch = torch.empty(floats, dtype=torch.float32, device=qkv.device) if floats else None
+    args = (_lib.ptr(qkv), lens_p, B, S, n_head, d // n_head, _lib.ptr(out), _lib.ptr(scratch), floats * 4, _st(qkv))
+    _lib.check(lib.ns_op_attention_core_mode(*args, 1) if bf16 else lib.ns_op_attention_core(*args), "attention_core")
     return out
+
+
+def gemm(model, name: str, x):
+    """One named contraction alone, in ``model``'s precision mode, through the forward's own dispatch: bias and the layer's
+    activation (ReLU for ``w_1``, tanh for every PostNet layer but the last), no residual, no LayerNorm.  ``name`` is
+    ``<layer prefix>.slf_attn.qkv`` / ``.slf_attn.fc`` / ``.pos_ffn.w_1`` / ``.pos_ffn.w_2``, ``mel_linear`` or
+    ``postnet.convolutions.<i>``; x [B,S,Cin] -> [B,S,N] with zero padding per utterance of S rows."""
+    B, S, _ = x.shape
+    x = x.contiguous()
+    n = gemm_shape(model, name)[1]
+    out = torch.empty(B, S, n, dtype=torch.float32, device=x.device)
+    _lib.check(model._lib.ns_op_gemm(model._h, name.encode(), _lib.ptr(x), B, S, _lib.ptr(out), _st(x)), "gemm")
+    return out
+
+
+def gemm_shape(model, name: str):
+    """(Cin, N, KW) of a contraction ``gemm`` accepts (the name itself is validated by the library)."""
+    c = model._cfg
+    if name == "mel_linear":
+        return c.d_dec, c.n_mel, 1
+    if name.startswith("postnet.convolutions."):
+        i = int(name.rsplit(".", 1)[1])
+        return (c.n_mel if i == 0 else c.postnet_dim), (c.n_mel if i == c.postnet_n - 1 else c.postnet_dim), c.postnet_k
+    d = c.d_enc if name.startswith("txt_encoder.") else c.d_dec
+    for suffix, shape in ((".slf_attn.qkv", (d, 3 * d, 1)), (".slf_attn.fc", (d, d, 1)), (".pos_ffn.w_1", (d, c.d_inner, c.ffn_k1)),
+                          (".pos_ffn.w_2", (c.d_inner, d, c.ffn_k2))):
+        if name.endswith(suffix):
+            return shape
+    raise ValueError(f"unknown contraction {name!r}")
+
+
+def plan_gemm_bf16(M: int, N: int):
+    """(rows, columns) of the tile a plain bf16-mode GEMM of M rows and N output channels is launched with."""
+    import ctypes
+
+    lib = _lib.load()
+    bm, bn = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(lib.ns_plan_gemm_bf16(int(M), int(N), ctypes.byref(bm), ctypes.byref(bn)), "plan_gemm_bf16")
+    return bm.value, bn.value
+
+
+def plan_gemm_bf16_ln(M: int, N: int, Cin: int, KW: int = 1) -> bool:
+    """True when a bf16-mode GEMM + LayerNorm of this shape takes the 64 x 256 full-row tile (else plain GEMM + row kernel)."""
+    return bool(_lib.load().ns_plan_gemm_bf16_ln(int(M), int(N), int(Cin), int(KW)))

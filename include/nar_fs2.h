@@ -250,6 +250,15 @@ int ns_op_gemm(ns_model* m, const char* name, const float* x, int B, int S, floa
  * ns_plan_attention_split: key ranges per 128-query tile of a dense attention launch (1 = none; 16 = the small-grid paths' own
  * sizing, the value the workspace is reserved for). */
 int ns_plan_gemm(int M, int N, int Cin, int KW, int32_t out[8]);
+/* Every launch the fp32 Conv1D-as-GEMM dispatch (csrc/gemm_conv.hip launch_conv_gemm) makes for M rows, N output channels, kernel
+ * size KW over Cin input channels, answered by the dispatch itself with launching switched off — the planner's range, the small-grid
+ * K-split ladder, the narrow-output (N = 80) and Cin = 80 rules and the row-epilogue launches alike.  epi: 0 = plain GEMM, 1 = GEMM +
+ * LayerNorm on the full-row tile, 2 = GEMM + LayerNorm on the ticketed ladder (which of the two a model takes for a shape is its own
+ * rule: full-row from ceil(M / 32) >= 200 row tiles, ticketed below).  Returns the number of launches, 0, 1 or 2 (0: the dispatch
+ * refuses the shape; 2: main + remainder of a cut plan), and writes per launch {BM, BN, BK, KS, MF, ROWEPI, TICKET, rows}: tile rows
+ * and columns, K step, in-workgroup K groups, MFMA tile edge (32 / 16), 1 for a full-row tile, ticketed row width / 256 (0 = not
+ * ticketed), rows of the launch; unused entries are zero.  Host-side, no GPU needed; follows NS_PLAN and the other A/B switches. */
+int ns_plan_gemm_launches(int M, int N, int Cin, int KW, int epi, int32_t out[2][8]);
 int ns_plan_row_tile(int M, int N);            /* = ns_plan_row_tile_k(M, N, N): the attention output projection's contraction */
 int ns_plan_row_tile_k(int M, int N, int K);   /* contraction length K = KW * Cin: K > 256 keeps to the heights with chunked accumulation */
 /* k values per accumulation chunk of the long contractions (K > 256; csrc/gemm_conv.hip ACC2): partial sums of this many

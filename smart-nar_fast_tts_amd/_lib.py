@@ -48,6 +48,7 @@ SIGNATURES = {
 
     "ns_last_phase2_rows": (C.c_int64, [_P]),
     "ns_plan_gemm": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int32)]),
+    "ns_plan_gemm_launches": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int32)]),
     "ns_plan_row_tile": (_I, [_I, _I]),
     "ns_plan_row_tile_k": (_I, [_I, _I, _I]),
     "ns_acc_chunk": (_I, []),

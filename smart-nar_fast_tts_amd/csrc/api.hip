@@ -1218,6 +1218,14 @@ extern "C" int ns_plan_gemm(int M, int N, int Cin, int KW, int32_t out[8]) {
   if (out) for (int i = 0; i < 8; ++i) out[i] = planned ? o[i] : 0;
   return planned ? 1 : 0;
 }
+extern "C" int ns_plan_gemm_launches(int M, int N, int Cin, int KW, int epi, int32_t out[2][8]) {
+  int o[2][8];
+  const int n = conv_gemm_describe(M, N, Cin, KW, epi, o);
+  if (out)
+    for (int l = 0; l < 2; ++l)
+      for (int i = 0; i < 8; ++i) out[l][i] = o[l][i];
+  return n;
+}
 extern "C" int ns_plan_row_tile_k(int M, int N, int K) {
   if (M <= 0 || K <= 0 || (N != 256 && N != 512)) return 0;
   return conv_gemm_row_tile(M, N, K);

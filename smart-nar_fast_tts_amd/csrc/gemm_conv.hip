@@ -33,6 +33,7 @@
 // ONE ds_read_b128.
 #include <hip/hip_ext.h>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include "rowln.h"
 
@@ -547,8 +548,22 @@ static int long_k_threshold() {
 // a tile with room for the second accumulator set: <= 32 accumulator registers per lane
 static constexpr bool tile_chunks(int bm, int bn, int waves) { return bm * bn / (64 * waves) <= 32; }
 
+// "describe" recorder: while set (this thread only), launch_t — the one funnel every form of the dispatch below passes through —
+// writes its own template parameters and the launch's row count here instead of launching.  The dispatch itself answers
+// ns_plan_gemm_launches, not a second copy of its rules.
+struct LaunchRecord { int n; int out[2][8]; };
+static thread_local LaunchRecord* t_describe = nullptr;
+
 template <int BM, int BN, int BK, int KS = 1, int WGM = 2, int WGN = 2, bool ROWEPI = false, int TICKET = 0, int MF = 32>
 static hipError_t launch_t(const ConvGemm& p, hipStream_t st, const LaunchTiming* tm = nullptr) {
+  if (LaunchRecord* r = t_describe) {  // conv_gemm_describe below: name the form, launch nothing
+    if (r->n < 2) {
+      const int form[8] = {BM, BN, BK, KS, MF, ROWEPI ? 1 : 0, TICKET, p.M};
+      for (int i = 0; i < 8; ++i) r->out[r->n][i] = form[i];
+    }
+    r->n++;
+    return hipSuccess;
+  }
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
   const int fl = ((acc_chunk_k() / BK) + 1) & ~1;  // K steps per accumulation chunk, even (0: off)
   if (tm && (tm->start || tm->stop))  // the events ride on this kernel's own dispatch packet (kernels.h LaunchTiming)
@@ -967,6 +982,32 @@ static hipError_t launch_conv_gemm_impl(const ConvGemm& p_in, hipStream_t st, bo
   if (p.N >= 256 && wgs(rows64, 256) >= 1024) return launch_t<64, 256, 16, 1, 2, 4>(p, st, tm);
   if (p.N >= 128 && wgs(rows64, 128) >= 512) return launch_t<64, 128, 16, 1, 2, 4>(p, st, tm);
   return launch_t<64, 64, 16>(p, st, tm);
+}
+
+// The launches launch_conv_gemm makes for a GEMM of this shape, asked of the dispatch itself (nar_fs2.h ns_plan_gemm_launches): the
+// operand pointers are null (row_range only ever offsets them), the leading dimensions are the dense ones the dispatch validates,
+// and launch_t records instead of launching.  epi: 0 = plain, 1 = LayerNorm on the full-row tile, 2 = LayerNorm on the ticketed
+// ladder (the ticket / y_out pointers only select the form).  Returns the number of launches (0: the dispatch refuses the shape).
+int conv_gemm_describe(int M, int N, int Cin, int KW, int epi, int out[2][8]) {
+  static int ticket_tag;
+  static float y_out_tag;
+  for (int l = 0; l < 2; ++l)
+    for (int i = 0; i < 8; ++i) out[l][i] = 0;
+  if (M <= 0 || N <= 0 || Cin <= 0 || KW <= 0 || epi < 0 || epi > 2) return 0;
+  ConvGemm p;
+  memset(&p, 0, sizeof(p));
+  p.ldx = Cin; p.ldy = N; p.M = M; p.N = N; p.Cin = Cin; p.KW = KW; p.pad = (KW - 1) / 2; p.S = M;
+  p.epi = epi ? EPI_LN : EPI_NONE;
+  if (epi == 2) { p.e.ticket = &ticket_tag; p.e.y_out = &y_out_tag; }
+  LaunchRecord rec;
+  memset(&rec, 0, sizeof(rec));
+  t_describe = &rec;
+  const hipError_t e = launch_conv_gemm_impl(p, nullptr, true, nullptr);
+  t_describe = nullptr;
+  if (e != hipSuccess || rec.n > 2) return 0;
+  for (int l = 0; l < rec.n; ++l)
+    for (int i = 0; i < 8; ++i) out[l][i] = rec.out[l][i];
+  return rec.n;
 }
 
 }  // namespace ns

@@ -75,6 +75,9 @@ hipError_t launch_conv_gemm(const ConvGemm& p, hipStream_t st, const LaunchTimin
 // {bm, bn, rows} of the main launch, {bm, bn, rows} of the remainder (0 = none), the MFMA tile edge of the launch(es) (32 / 16),
 // the cost model's estimate in us
 bool conv_gemm_plan(int M, int N, int Cin, int KW, int out[8]);
+// every launch of launch_conv_gemm for this shape, recorded by the dispatch itself: {BM, BN, BK, KS, MF, ROWEPI, TICKET, rows} per launch;
+// epi 0 = plain, 1 = LayerNorm on the full-row tile, 2 = LayerNorm on the ticketed ladder; returns the number of launches (0 = refused)
+int conv_gemm_describe(int M, int N, int Cin, int KW, int epi, int out[2][8]);
 bool conv_gemm_tile16_enabled();  // the 16-row tile family is in use (planner on, NS_TILE16 != 0)
 int conv_gemm_row_tile(int M, int N, int K = 256);  // height of the full-row (LayerNorm epilogue) tile for M rows of N = 256 / 512 columns, contraction length K
 int conv_gemm_acc_chunk();  // k values per accumulation chunk of the long contractions (gemm_conv.hip ACC2; NS_ACC_CHUNK, 0 = one sequential sum)

@@ -262,3 +262,14 @@ def plan_gemm_bf16(M: int, N: int):
 def plan_gemm_bf16_ln(M: int, N: int, Cin: int, KW: int = 1) -> bool:
     """True when a bf16-mode GEMM + LayerNorm of this shape takes the 64 x 256 full-row tile (else plain GEMM + row kernel)."""
     return bool(_lib.load().ns_plan_gemm_bf16_ln(int(M), int(N), int(Cin), int(KW)))
+
+
+def plan_gemm_launches(M: int, N: int, Cin: int, KW: int = 1, epi: int = 0):
+    """The launches the fp32 Conv1D-as-GEMM dispatch makes for this shape, named by the dispatch itself (``ns_plan_gemm_launches``;
+    host-side, no GPU): a tuple of 0, 1 or 2 ``(BM, BN, BK, KS, MF, ROWEPI, TICKET, rows)``.  ``epi``: 0 plain, 1 LayerNorm on the
+    full-row tile, 2 LayerNorm on the ticketed ladder."""
+    import ctypes
+
+    o = (ctypes.c_int32 * 16)()
+    n = _lib.load().ns_plan_gemm_launches(int(M), int(N), int(Cin), int(KW), int(epi), o)
+    return tuple(tuple(o[8 * l:8 * l + 8]) for l in range(n))

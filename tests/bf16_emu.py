@@ -9,7 +9,10 @@ only by its summation, so the bound is elementwise:  |y - f64| <= REL * (conv(|b
 Contract of the attention (csrc/attention.hip, BF = true): scores from rounded Q, K, scaled by log2(e) / sqrt(d_k) in fp32,
 masked; p = exp2(s - ceil(max s)); P V from p ROUNDED to bf16 and V rounded, divided by the sum of the UNROUNDED p.  A score
 that differs in its last bits can put a p on the other side of a bf16 rounding boundary, which moves that p by one bf16 ulp; the
-attention gate budgets such flips explicitly (attention_check)."""
+attention gate budgets such flips explicitly (attention_check).
+
+The GEMM half also serves the exact-fp32 path (tests/test_fp32_ops_host.py, tests/test_gpu_fp32_ops.py): round_fn = exact takes
+the operands as they are, which with rel = FP32_REL is the contract of csrc/gemm_conv.hip."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -60,16 +63,22 @@ def conv_rows(x, w, b, dtype=torch.float64, cross_utterance=False):
     return y.reshape(B0, S0, N)
 
 
-def gemm_emu(x, w, b, KW=None, act=None, dtype=torch.float64):
-    """the contraction of the contract: both operands rounded, evaluated in dtype, the layer's activation on top"""
+def exact(t):
+    """the operand rounding of the exact-fp32 contract (csrc/gemm_conv.hip): none, the operands are taken as they are"""
+    return t
+
+
+def gemm_emu(x, w, b, KW=None, act=None, dtype=torch.float64, round_fn=bf):
+    """the contraction of the contract: both operands rounded (round_fn = exact: the fp32 path's contract, operands as they are),
+    evaluated in dtype, the layer's activation on top"""
     assert KW is None or KW == (1 if w.dim() == 2 else w.shape[2])
-    y = conv_rows(bf(x), bf(w), b, dtype)
+    y = conv_rows(round_fn(x), round_fn(w), b, dtype)
     return ACTS[act](y)
 
 
-def gemm_unit(x, w, b):
+def gemm_unit(x, w, b, round_fn=bf):
     """conv(|bf x|, |bf w|) + |bias| in float64: what one rounding of the running sum is relative to"""
-    return conv_rows(bf(x).abs(), bf(w).abs(), None if b is None else b.abs(), torch.float64)
+    return conv_rows(round_fn(x).abs(), round_fn(w).abs(), None if b is None else b.abs(), torch.float64)
 
 
 @dataclass
@@ -81,11 +90,11 @@ class GemmCheck:
         return f"worst |y - f64| / (REL * (conv(|bf x|, |bf w|) + |b|)) = {self.worst:.3g}"
 
 
-def gemm_check(got, x, w, b, act=None, rel=GEMM_REL, ref=None, unit=None):
+def gemm_check(got, x, w, b, act=None, rel=GEMM_REL, ref=None, unit=None, round_fn=bf):
     """every element of `got` against the float64 emulation.  The bound is on the pre-activation sum; ReLU and tanh are
     1-Lipschitz, so it holds for the stored output too."""
-    ref = gemm_emu(x, w, b, act=act) if ref is None else ref
-    unit = gemm_unit(x, w, b) if unit is None else unit
+    ref = gemm_emu(x, w, b, act=act, round_fn=round_fn) if ref is None else ref
+    unit = gemm_unit(x, w, b, round_fn=round_fn) if unit is None else unit
     got = got.reshape(ref.shape).double()
     err = (got - ref).abs()
     bound = rel * unit
@@ -110,13 +119,13 @@ class LnCheck:
         return f"worst |y - f64| / bound = {self.worst:.3g}"
 
 
-def gemm_ln_check(got, x, w, b, resid, g, beta, rel=GEMM_REL):
+def gemm_ln_check(got, x, w, b, resid, g, beta, rel=GEMM_REL, round_fn=bf):
     """got = LayerNorm(gemm(x) + resid) against float64, the GEMM's bound e = rel * unit propagated through the LayerNorm to
     first order: with yhat = (z - mean) / sigma, d y_n = g_n / sigma * (d z_n - mean(d z) - yhat_n * mean(yhat d z)) and
     |mean(yhat d z)| <= rms(yhat) rms(d z) = rms(e); plus FP32_REL * (|ref| + |ln_b|) for the fp32 row arithmetic."""
-    z = gemm_emu(x, w, b) + resid.double()
+    z = gemm_emu(x, w, b, round_fn=round_fn) + resid.double()
     ref = layernorm_emu(z, g, beta)
-    e = rel * gemm_unit(x, w, b)
+    e = rel * gemm_unit(x, w, b, round_fn=round_fn)
     mean = z.mean(-1, keepdim=True)
     sigma = torch.sqrt(((z - mean) ** 2).mean(-1, keepdim=True) + LN_EPS)
     yhat = (z - mean) / sigma

@@ -13,6 +13,7 @@ typedef void (*destroy_fn)(ns_model*);
 typedef size_t (*arena_fn)(const ns_model*);
 typedef size_t (*ws_fn)(const ns_model*, int, int);
 typedef int (*plan_fn)(int, int, int, int, int32_t*);
+typedef int (*launches_fn)(int, int, int, int, int, int32_t (*)[8]);
 typedef int (*split_fn)(int, int, int, int);
 typedef int (*version_fn)(void);
 
@@ -21,12 +22,14 @@ int main(int argc, char** argv) {
   ns_config c;
   ns_model* m = 0;
   int32_t plan[8];
+  int32_t forms[2][8];
   if (argc < 2) return 2;
   so = dlopen(argv[1], RTLD_NOW | RTLD_LOCAL);
   if (!so) { printf("dlopen: %s\n", dlerror()); return 3; }
   {
     /* (POSIX idiom: ISO C has no conversion from void* to a function pointer) */
-    last_error_fn last_error; create_fn create; destroy_fn destroy; arena_fn arena; ws_fn enc_ws; plan_fn plan_gemm; split_fn att_split; version_fn abi_version;
+    last_error_fn last_error; create_fn create; destroy_fn destroy; arena_fn arena; ws_fn enc_ws; plan_fn plan_gemm; split_fn att_split; version_fn abi_version; launches_fn plan_launches;
+    *(void**)(&plan_launches) = dlsym(so, "ns_plan_gemm_launches");
     *(void**)(&last_error) = dlsym(so, "ns_last_error");
     *(void**)(&create) = dlsym(so, "ns_create");
     *(void**)(&destroy) = dlsym(so, "ns_destroy");
@@ -53,6 +56,9 @@ int main(int argc, char** argv) {
     { ns_model* bad = 0; if (create(&c, &bad) == 0 || strlen(last_error()) == 0) return 7; }
     if (plan_gemm(16160, 1024, 256, 9, plan) != 1 || plan[0] != 128 || plan[1] != 256 || plan[2] != 16160 || plan[5] != 0 || plan[6] != 32 || plan[7] <= 0) return 8;
     if (att_split(16, 1010, 2, 128) != 1) return 9;
+    /* the dispatch naming its own launch: the same 128 x 256 tile, K step 32, one K group, MFMA edge 32, no row epilogue, all rows */
+    if (!plan_launches || plan_launches(16160, 1024, 256, 9, 0, forms) != 1 || forms[0][0] != 128 || forms[0][1] != 256 || forms[0][2] != 32 ||
+        forms[0][3] != 1 || forms[0][4] != 32 || forms[0][5] != 0 || forms[0][6] != 0 || forms[0][7] != 16160 || forms[1][0] != 0) return 11;
     destroy(m);
   }
   printf("C caller ok\n");

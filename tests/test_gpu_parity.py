@@ -519,6 +519,11 @@ def test_planner_shapes_vs_oracle(B):
     fine = [k for k, p in plans.items() if p and p["mfma_edge"] == 16]  # a tile of the 16-row family (height chosen for the row count)
     row_tile = int(m._lib.ns_plan_row_tile(M, d))  # the full-row (GEMM + LayerNorm epilogue) tile's height
     print(f"B={B} T_pad={T} rows={M} plans={plans} full-row tile {row_tile} attention key split={nsplit}")
+    from smart_nar_fast_tts_amd import ops
+
+    forms = {k: ops.plan_gemm_launches(M, *s) for k, s in (("w_1", (di, d, k1)), ("postnet_mid", (512, 512, 5)), ("qkv", (3 * d, d, 1)))}
+    forms.update(fc_ln=ops.plan_gemm_launches(M, d, d, 1, 1), w_2_ln=ops.plan_gemm_launches(M, d, di, 1, 1))
+    print(f"B={B} launch forms (BM, BN, BK, KS, MF, ROWEPI, TICKET, rows): {forms}")
     if row_tile != 32:
         fine.append("full_row")
     assert plans["w_1"] is not None, "B*T is inside the planner's range"

@@ -368,6 +368,58 @@ int ns_voc_op_upsample(ns_vocoder* v, int i, const float* x, int B, int S, float
 size_t ns_voc_op_stage_ws_bytes(const ns_vocoder* v, int i, int B, int S);
 int ns_voc_op_stage(ns_vocoder* v, int i, const float* x, int B, int S, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ==== Reference-mel aligner (the reference's MelEncoder: transformer/Models.py:103-173, called at model/fastspeech2_align.py:56) ===
+ * A separate handle with its own weights, arena and workspace; nothing above changes (NS_ABI_VERSION stays as it is).  From the text
+ * encoder's output src_output [B, L, d] and a recording's mel frames mels [B, T, 80] it computes what
+ *   mel_encoder(src_output, mels, src_masks, mel_masks)
+ * returns in eval():
+ *   x = relu(w_2(relu(w_1(mels with frame 0 := zeros)))) + position rows           Prenet, transformer/Layers.py:11-26; Models.py:145-164
+ *   per layer (FFTBlock2, transformer/Layers.py:51-70):
+ *     attn = softmax(w_qs(x) w_ks(src)^T / sqrt(dk) + (-inf at keys l >= src_lens[b]))   every query row, padded ones included
+ *     x = masked_fill(LayerNorm(fc(attn w_vs(src)) + x));  x = masked_fill(LayerNorm(w_2(relu(w_1(x))) + x))   rows t >= mel_lens[b] := 0
+ * tgt_output [B, T, d] and the attention maps of every layer, attn_all_layers [n_layer, B, H, T, L] (the reference's list of
+ * [B, H, T, L] tensors, transformer/SubLayers.py:48-49).  Masked keys hold exactly 0; an utterance with src_lens[b] == 0 is NaN (torch's
+ * softmax over a row of -inf) and so is nothing else.  Always exact fp32, whatever ns_config.matmul_bf16x3 says: the product is a
+ * discrete decision.  Exists only for d_enc == d_dec == 256 (Prenet is hard-coded 80 -> 256 -> 256 and w_ks / w_vs take d_model
+ * inputs) with d_dec / n_dec_head in {64, 128}; ns_aln_create refuses anything else.
+ * EXTENSION beyond the reference (whose own duration extraction, _calculate_duration, is undefined: fastspeech2_align.py:57):
+ *   a[t, l] = sum over heads h (in head order, fp32) of attn_all_layers[n_layer - 1][b, h, t, l]
+ *   durations[b, i] = #{ t < mel_lens[b] : argmax over l < src_lens[b] of a[t, l] == i }, ties to the lowest l
+ * int64 [B, L]; 0 for i >= src_lens[b]; the whole row 0 when src_lens[b] or mel_lens[b] is 0, else sum_i durations[b, i] =
+ * min(mel_lens[b], T). */
+#define NS_ALN_ABI_VERSION 1
+typedef struct ns_aligner ns_aligner;
+int ns_aln_abi_version(void);
+/* reads d_enc, d_dec, n_dec_layer, n_dec_head, d_inner, ffn_k1, ffn_k2, n_mel, max_seq_len, row_epilogue of the model's config
+ * (transformer/Models.py:106-138) */
+int ns_aln_create(const ns_config* cfg, ns_aligner** out);
+void ns_aln_destroy(ns_aligner* a);
+/* 4 * (sum of numel over every mel_encoder.* tensor, position_enc [1, max_seq_len + 1, d] included): packing keeps every element
+ * (w_ks | w_vs fused to [2d, d], Conv1d [out, in, k] -> [out, k, in]) and every tensor's size is a multiple of 256 bytes. */
+size_t ns_aln_arena_bytes(const ns_aligner* a);
+int ns_aln_bind_arena(ns_aligner* a, void* dev_arena, size_t bytes);  /* 256-byte aligned */
+/* host float32, reference key names ("mel_encoder.prenet.w_1.weight", "mel_encoder.layer_stack.{i}.crs_attn.w_qs.weight", ...) and
+ * torch-native layouts; unknown keys and shape mismatches are errors.  "mel_encoder.position_enc" is optional (regenerated).
+ * check: the same validation, no side effect. */
+int ns_aln_set_weight(ns_aligner* a, const char* name, const float* host, const int64_t* shape, int ndim);
+int ns_aln_check_weight(ns_aligner* a, const char* name, const int64_t* shape, int ndim);
+int ns_aln_finalize_weights(ns_aligner* a, void* stream);
+/* Workspace of ns_aln_forward; monotone in B, L and T. */
+size_t ns_aln_ws_bytes(const ns_aligner* a, int B, int L, int T);
+/* src_output [B, L, d] (ns_op_txt_encoder's output), mels [B, T, 80] (read only), src_lens / mel_lens [B] int64 on the device;
+ * writes tgt_output [B, T, d], attn_all_layers [n_layer, B, H, T, L], durations [B, L] int64.  16-byte aligned float pointers. */
+int ns_aln_forward(ns_aligner* a, const float* src_output, const int64_t* src_lens, const float* mels, const int64_t* mel_lens,
+                   int B, int L, int T, float* tgt_output, float* attn_all_layers, int64_t* durations, void* ws, size_t ws_bytes,
+                   void* stream);
+/* ---- per-operator entry points (tests) ----
+ * cross attention alone (transformer/Modules.py:14-25 on projected heads): q [B*T, H*dk], kv [B*L, 2*H*dk] (K | V, head h at h*dk
+ * inside each) -> ctx [B*T, H*dk] (merged heads), attn [B, H, T, L]; dk in {64, 128}.
+ * durations: the extension above applied to one [B, H, T, L] map. */
+int ns_aln_op_cross_attention(const float* q, const float* kv, const int64_t* src_lens, int B, int T, int L, int H, int dk,
+                              float* ctx, float* attn, void* stream);
+int ns_aln_op_durations(const float* attn_last, const int64_t* src_lens, const int64_t* mel_lens, int B, int H, int T, int L,
+                        int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

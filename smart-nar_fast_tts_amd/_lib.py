@@ -97,6 +97,19 @@ SIGNATURES = {
     "ns_voc_op_upsample": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "ns_voc_op_stage_ws_bytes": (_Z, [_P, _I, _I, _I]),
     "ns_voc_op_stage": (_I, [_P, _I, _P, _I, _I, _P, _P, _Z, _P]),
+    # reference-mel aligner (model.FastSpeech2Align.align; the config pointer is the model's NsConfig)
+    "ns_aln_abi_version": (_I, []),
+    "ns_aln_create": (_I, [C.POINTER(NsConfig), C.POINTER(_P)]),
+    "ns_aln_destroy": (None, [_P]),
+    "ns_aln_arena_bytes": (_Z, [_P]),
+    "ns_aln_bind_arena": (_I, [_P, _P, _Z]),
+    "ns_aln_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
+    "ns_aln_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
+    "ns_aln_finalize_weights": (_I, [_P, _P]),
+    "ns_aln_ws_bytes": (_Z, [_P, _I, _I, _I]),
+    "ns_aln_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "ns_aln_op_cross_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ns_aln_op_durations": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -1,7 +1,8 @@
 """Checkpoint reader: the reference saves ``{"model": model.module.state_dict(), "optimizer": ...}``
 every ``save_step`` to ``{ckpt_path}/{step}.pth.tar`` (train.py:149-159) and restores it in ``get_model``
-(utils/model.py:11-35).  Only the inference subset is uploaded: ``mel_encoder.*`` (the training-only aligner, 12.4 M of
-the 41.3 M parameters) and the optimizer state are read from disk and dropped."""
+(utils/model.py:11-35).  The inference subset is uploaded; ``mel_encoder.*`` (the reference-mel aligner, 12.4 M of the 41.3 M
+parameters) is handed to the model as host tensors for ``align()`` (uploaded on its first call); the optimizer state is read from
+disk and dropped."""
 from __future__ import annotations
 
 import os
@@ -24,10 +25,24 @@ def inference_state_dict(ckpt):
     return out
 
 
+def aligner_state_dict(ckpt):
+    """The ``mel_encoder.*`` entries of the same checkpoint (what ``FastSpeech2Align.align()`` runs on)."""
+    sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("module."):
+            k = k[len("module."):]
+        if k.startswith("mel_encoder.") and not k.endswith("num_batches_tracked"):
+            out[k] = v
+    return out
+
+
 def load_checkpoint(model: FastSpeech2Align, path: str) -> FastSpeech2Align:
     # weights_only: a checkpoint is tensors + an optimizer state dict; do not unpickle arbitrary objects
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
-    model.load_state_dict(inference_state_dict(ckpt))
+    sd = inference_state_dict(ckpt)
+    sd.update(aligner_state_dict(ckpt))  # kept on the host by load_state_dict, outside the forward's arena
+    model.load_state_dict(sd)
     return model
 
 

@@ -212,6 +212,19 @@ size_t voc_post_lds_bytes(int C, int KW);
 hipError_t launch_voc_post(const float* x, const float* w, const float* bias, float* wav, int B, int S, int C, int KW, float slope, hipStream_t st);
 // dst [B, T, C] = src [B, C, T] transposed
 hipError_t launch_voc_transpose(const float* src, float* dst, int B, int C, int T, hipStream_t st);
+// ---- reference-mel aligner (cross_attention.hip) -----------------------------------------------
+// ScaledDotProductAttention of FFTBlock2.crs_attn with its probabilities as an output (transformer/Modules.py:14-25,
+// SubLayers.py:47-54): q [B*T, H*dk], kv [B*L, 2*H*dk] (columns [0, d) = K, [d, 2d) = V, head h at h*dk inside each) ->
+// ctx [B*T, H*dk] (merged heads) and attn [B, H, T, L] = softmax(q k^T / sqrt(dk) + (-inf at keys >= src_lens[b])).
+// Key-only mask: every query row is computed.  dk in {64, 128}; q and kv 16-byte aligned.
+bool cross_attention_ok(int H, int dk);
+hipError_t launch_cross_attention(const float* q, const float* kv, const long long* src_lens, int B, int T, int L, int H, int dk,
+                                  float* ctx, float* attn, hipStream_t st);
+// x [B*T, C] = mels with frame 0 of every utterance replaced by zeros (transformer/Models.py:145-146); C % 4 == 0, 16-byte aligned
+hipError_t launch_aln_input(const float* mels, float* x, int B, int T, int C, hipStream_t st);
+// out [B, L] int64: frames of utterance b whose head-summed last-layer alignment peaks at phoneme i (zeroes `out` first)
+hipError_t launch_aln_durations(const float* attn_last, const long long* src_lens, const long long* mel_lens, int B, int H, int T, int L,
+                                long long* out, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

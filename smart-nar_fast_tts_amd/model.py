@@ -17,6 +17,7 @@ import math
 import os
 import time
 from collections import OrderedDict
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -124,6 +125,14 @@ class ForwardOutput(tuple):
         return words
 
 
+class AlignOutput(NamedTuple):
+    """What ``FastSpeech2Align.align()`` returns: the reference's ``mel_encoder(...)`` pair (transformer/Models.py:173) and the
+    durations derived from it (an extension beyond the reference)."""
+    tgt_output: torch.Tensor
+    tgt_alignment: list
+    durations: torch.Tensor
+
+
 class FastSpeech2Align:
     """FastSpeech2 (inference) — HIP/gfx950 implementation of the reference module of the same name.
 
@@ -158,6 +167,12 @@ class FastSpeech2Align:
         self._loaded = False      # a full inference state dict was accepted (load_state_dict) ...
         self._adopted = False     # ... or the packed arena arrived as bytes (adopt_arena)
         self.training = False
+        # reference-mel aligner (align()): the checkpoint's mel_encoder.* tensors on the host, its own native handle, arena and
+        # scratch — built and uploaded on the first align(), nothing of the forward's state is shared
+        self._aln_sd = OrderedDict()
+        self._aln_h = None
+        self._aln_arena = None
+        self._aln_ready = False
         # VarianceAdaptor.__init__ opens stats.json for the bin edges (model/modules.py:41-71).  They are also
         # state-dict entries, so a checkpoint overrides them; until one is loaded they are only DEFAULTS (kept apart
         # from _sd: two of ~150 keys are not an uploadable state dict).
@@ -172,6 +187,9 @@ class FastSpeech2Align:
             if getattr(self, "_h", None):
                 self._lib.ns_destroy(self._h)
                 self._h = None
+            if getattr(self, "_aln_h", None):
+                self._lib.ns_aln_destroy(self._aln_h)
+                self._aln_h = None
         except Exception:
             pass
 
@@ -199,6 +217,7 @@ class FastSpeech2Align:
             self._device = device
             self._ws = OrderedDict()
             self._arena = None
+            self._aln_arena, self._aln_ready = None, False  # (the aligner re-uploads from its host copy on the next align())
             if old_arena is not None or self._loaded:
                 # the native handle must never keep pointing at the old device's arena: rebind first (this also marks
                 # the handle not-ready), then restore the weights on the new device
@@ -313,8 +332,9 @@ class FastSpeech2Align:
         return self._lib.ns_last_error().decode()
 
     def load_state_dict(self, state_dict, strict: bool = True, *, _internal: bool = False):
-        """Accepts the reference's checkpoint["model"] (utils/model.py:21-22).  ``mel_encoder.*`` (training-only
-        aligner) and ``num_batches_tracked`` entries are accepted and ignored.  Like ``nn.Module.load_state_dict``:
+        """Accepts the reference's checkpoint["model"] (utils/model.py:21-22).  ``mel_encoder.*`` entries (the reference-mel
+        aligner) are kept on the host for ``align()`` / ``aligner_state_dict()`` — they are no part of the forward's arena or of
+        ``state_dict()`` — and ``num_batches_tracked`` entries are accepted and ignored.  Like ``nn.Module.load_state_dict``:
         a shape mismatch always raises; an unexpected key raises when ``strict`` and is skipped (and returned)
         otherwise; keys no load has supplied so far raise when ``strict`` and keep their current (constructor-equivalent) values
         otherwise — a model that already holds a full caller-supplied state dict accepts partial updates.  Every entry is validated
@@ -325,8 +345,14 @@ class FastSpeech2Align:
             new["variance_adaptor.pitch_bins"] = pb
             new["variance_adaptor.energy_bins"] = eb
         unexpected, errors = [], []
+        aln = OrderedDict()
         for k, v in state_dict.items():
-            if k.startswith("mel_encoder.") or k.endswith("num_batches_tracked"):
+            if k.startswith("mel_encoder."):
+                if not k.endswith("num_batches_tracked"):
+                    a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+                    aln[k] = np.array(a, dtype=np.float32, order="C")
+                continue
+            if k.endswith("num_batches_tracked"):
                 continue
             a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
             a = np.ascontiguousarray(a, dtype=np.float32)
@@ -361,6 +387,9 @@ class FastSpeech2Align:
                 merged[k] = init[k]
         if not _internal:
             self._user_keys = provided
+        if aln:  # (only once the rest of the state dict has been accepted)
+            self._aln_sd.update(aln)
+            self._aln_ready = False
         for k, a in merged.items():
             self._stage(k, a)
         self._sd = merged
@@ -415,6 +444,108 @@ class FastSpeech2Align:
             _lib.check(self._lib.ns_adopt_arena(self._h), "ns_adopt_arena")
         if not self._loaded:
             self._adopted = True
+
+    # ---- reference-mel aligner ---------------------------------------------------------------------
+    def aligner_state_dict(self):
+        """The ``mel_encoder.*`` tensors the last load_state_dict() calls supplied (host copies; empty when none did)."""
+        return OrderedDict((k, torch.from_numpy(np.array(v))) for k, v in self._aln_sd.items())
+
+    def _aligner_scope(self):
+        """ValueError unless the reference's MelEncoder can exist for this config at all."""
+        t = self.model_config["transformer"]
+        if t["encoder_hidden"] != 256 or t["decoder_hidden"] != 256:
+            raise ValueError(
+                f"align(): the aligner exists only for encoder_hidden == decoder_hidden == 256, got {t['encoder_hidden']} / "
+                f"{t['decoder_hidden']}: Prenet is hard-coded 80 -> 256 -> 256 (transformer/Layers.py:18-19) and crs_attn.w_ks / w_vs "
+                "are Linear(d_model, ...) applied to the text encoder's output (transformer/SubLayers.py:19-20, Layers.py:62-64)")
+        if t["decoder_hidden"] % t["decoder_head"] or t["decoder_hidden"] // t["decoder_head"] not in (64, 128):
+            raise ValueError(f"align(): decoder_hidden / decoder_head must be 128 or 64 (transformer/Models.py:113-116), got decoder_head {t['decoder_head']}")
+
+    def _check_aligner_weights(self):
+        """Host-side half of the aligner's set-up: scope, presence and shapes of the mel_encoder.* tensors (raises before anything
+        touches the device; a rejected set leaves nothing half staged)."""
+        self._aligner_scope()
+        if not self._aln_sd:
+            raise RuntimeError("align(): no aligner weights: load_state_dict() a checkpoint that holds the mel_encoder.* tensors "
+                               "(the reference's MelEncoder, transformer/Models.py:103-138)")
+        if self._aln_h is None:
+            h = C.c_void_p()
+            _lib.check(self._lib.ns_aln_create(C.byref(self._cfg), C.byref(h)), "ns_aln_create")
+            self._aln_h = h
+        if self._aln_ready:
+            return
+        for k, a in self._aln_sd.items():
+            shape = (C.c_int64 * a.ndim)(*a.shape)
+            if self._lib.ns_aln_check_weight(self._aln_h, k.encode(), shape, a.ndim) != 0:
+                raise RuntimeError("align(): " + self._lib.ns_last_error().decode())
+
+    def _ensure_aligner(self):
+        """The aligner's arena: built and uploaded on the first align() after a load (or a move to another device)."""
+        if self._aln_ready:
+            return
+        lib = self._lib
+        with torch.cuda.device(self._device):
+            if self._aln_arena is None:
+                nbytes = lib.ns_aln_arena_bytes(self._aln_h)
+                self._aln_arena = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
+                _lib.check(lib.ns_aln_bind_arena(self._aln_h, _lib.ptr(self._aln_arena), nbytes), "ns_aln_bind_arena")
+            for k, a in self._aln_sd.items():
+                shape = (C.c_int64 * a.ndim)(*a.shape)
+                _lib.check(lib.ns_aln_set_weight(self._aln_h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim), "align()")
+            _lib.check(lib.ns_aln_finalize_weights(self._aln_h, _lib.stream_ptr(self._device)), "align()")
+        self._aln_ready = True
+
+    def align(self, texts, src_lens, max_src_len, mels, mel_lens, max_mel_len=None):
+        """What the reference's ``self.mel_encoder(txt_encoder(texts, src_masks), mels, src_masks, mel_masks)`` returns in eval()
+        (model/fastspeech2_align.py:45,56; transformer/Models.py:140-173) for a recording's mel frames ``mels`` [B, T, 80] (borrowed,
+        never written): ``tgt_output`` [B, T, 256] and ``tgt_alignment``, one [B, H, T, L] attention map per layer — slot 10 of the
+        reference's forward() tuple — plus ``durations`` [B, L] int64, an EXTENSION beyond the reference (whose own
+        ``_calculate_duration`` is undefined): the frames t < mel_len whose head-summed last-layer alignment peaks at each phoneme.
+        Always exact fp32, whatever ``model_config["matmul"]`` says.  Needs the checkpoint's ``mel_encoder.*`` weights."""
+        self._check_aligner_weights()
+        if not (torch.is_tensor(texts) and texts.is_cuda and torch.is_tensor(mels) and mels.is_cuda):
+            raise RuntimeError("inputs must live on the MI355X (cuda) device; there is no CPU path")
+        if mels.dim() != 3 or mels.shape[0] != texts.shape[0] or mels.shape[2] != self._cfg.n_mel:
+            raise ValueError(f"mels must have shape ({int(texts.shape[0])}, T, {self._cfg.n_mel}), got {tuple(mels.shape)}")
+        B, L, T = int(texts.shape[0]), int(texts.shape[1]), int(mels.shape[1])
+        if int(max_src_len) != L:
+            raise ValueError(f"max_src_len ({int(max_src_len)}) must equal texts.shape[1] ({L})")
+        if max_mel_len is not None and int(max_mel_len) != T:
+            raise ValueError(f"max_mel_len ({int(max_mel_len)}) must equal mels.shape[1] ({T})")
+        if L < 1:
+            raise ValueError("align(): texts must hold at least one phoneme column")
+        if self._device != texts.device:
+            self.to(texts.device)
+        self._ensure_weights()
+        self._ensure_aligner()
+        lib, dev = self._lib, self._device
+
+        def lens(name, v):
+            v = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+            if tuple(v.shape) != (B,):
+                raise ValueError(f"{name} must have shape ({B},), got {tuple(v.shape)}")
+            return v.to(device=dev, dtype=torch.long).contiguous()
+
+        with torch.cuda.device(dev):
+            sl, ml = lens("src_lens", src_lens), lens("mel_lens", mel_lens)
+            texts_c = texts.long().contiguous()
+            mels_c = mels.to(torch.float32).contiguous()
+            st = _lib.stream_ptr(dev)
+            n_layer, H, d = self._cfg.n_dec_layer, self._cfg.n_dec_head, self._cfg.d_dec
+            src_out = torch.empty(B, L, d, dtype=torch.float32, device=dev)
+            tgt = torch.empty(B, T, d, dtype=torch.float32, device=dev)
+            attn = torch.empty(n_layer, B, H, T, L, dtype=torch.float32, device=dev)
+            dur = torch.empty(B, L, dtype=torch.long, device=dev)
+            ws_op = self._workspace("op", lib.ns_op_ws_bytes(self._h, B, L))
+            _lib.check(lib.ns_op_txt_encoder(self._h, _lib.ptr(texts_c), _lib.ptr(sl), B, L, _lib.ptr(src_out), _lib.ptr(ws_op),
+                                             ws_op.numel(), st), "align(): txt_encoder")
+            if T > 0:
+                ws = self._workspace("aln", lib.ns_aln_ws_bytes(self._aln_h, B, L, T))
+                _lib.check(lib.ns_aln_forward(self._aln_h, _lib.ptr(src_out), _lib.ptr(sl), _lib.ptr(mels_c), _lib.ptr(ml), B, L, T,
+                                              _lib.ptr(tgt), _lib.ptr(attn), _lib.ptr(dur), _lib.ptr(ws), ws.numel(), st), "ns_aln_forward")
+            else:
+                dur.zero_()
+        return AlignOutput(tgt, [attn[i] for i in range(n_layer)], dur)
 
     # ---- measurement hook (bench.py roofline leg) ----------------------------------------------------
     def profile_dominant_kernel(self, on: bool = True):

@@ -273,3 +273,29 @@ def plan_gemm_launches(M: int, N: int, Cin: int, KW: int = 1, epi: int = 0):
     o = (ctypes.c_int32 * 16)()
     n = _lib.load().ns_plan_gemm_launches(int(M), int(N), int(Cin), int(KW), int(epi), o)
     return tuple(tuple(o[8 * l:8 * l + 8]) for l in range(n))
+
+
+def cross_attention(q, kv, src_lens, n_head: int):
+    """The aligner's ScaledDotProductAttention on already-projected heads (transformer/Modules.py:14-25, key-only mask): q [B,T,d],
+    kv [B,L,2*d] (K | V, head h at h*dk inside each) -> (merged heads [B,T,d], attention probabilities [B,H,T,L])."""
+    lib = _lib.load()
+    B, T, d = q.shape
+    L = kv.shape[1]
+    q, kv, src_lens = q.contiguous(), kv.contiguous(), src_lens.long().contiguous()
+    ctx = torch.empty(B, T, d, dtype=torch.float32, device=q.device)
+    attn = torch.empty(B, n_head, T, L, dtype=torch.float32, device=q.device)
+    _lib.check(lib.ns_aln_op_cross_attention(_lib.ptr(q), _lib.ptr(kv), _lib.ptr(src_lens), B, T, L, n_head, d // n_head, _lib.ptr(ctx),
+                                             _lib.ptr(attn), _st(q)), "cross_attention")
+    return ctx, attn
+
+
+def aligner_durations(attn_last, src_lens, mel_lens):
+    """Frames per phoneme from one [B,H,T,L] alignment (EXTENSION beyond the reference, include/nar_fs2.h): int64 [B,L]."""
+    lib = _lib.load()
+    B, H, T, L = attn_last.shape
+    attn_last = attn_last.contiguous()
+    src_lens, mel_lens = src_lens.long().contiguous(), mel_lens.long().contiguous()
+    out = torch.empty(B, L, dtype=torch.long, device=attn_last.device)
+    _lib.check(lib.ns_aln_op_durations(_lib.ptr(attn_last), _lib.ptr(src_lens), _lib.ptr(mel_lens), B, H, T, L, _lib.ptr(out),
+                                       _st(attn_last)), "aligner_durations")
+    return out

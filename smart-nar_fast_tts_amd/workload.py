@@ -451,3 +451,48 @@ def synth_vocoder_state_dict(h: dict, seed: int = 0) -> "OrderedDict[str, np.nda
                     wn(f"resblocks.{i * nk + j}.{w}.{n}", (ch, ch, kk), ch * kk)
     wn("conv_post", (1, c0 >> len(h["upsample_rates"]), 7), (c0 >> len(h["upsample_rates"])) * 7, gain=VOCODER_POST_GAIN)
     return sd
+
+
+def aligner_shapes(model_cfg: dict) -> "OrderedDict[str, tuple]":
+    """Name -> shape of every ``mel_encoder.*`` state-dict entry of the reference (MelEncoder, transformer/Models.py:106-138:
+    Prenet 80 -> 256 -> 256, the position table, ``decoder_layer`` FFTBlock2 blocks), in the module's own order."""
+    t = model_cfg["transformer"]
+    d, di, ks = t["decoder_hidden"], t["conv_filter_size"], t["conv_kernel_size"]
+    out: "OrderedDict[str, tuple]" = OrderedDict()
+    out["mel_encoder.position_enc"] = (1, model_cfg["max_seq_len"] + 1, d)
+    out["mel_encoder.prenet.w_1.weight"], out["mel_encoder.prenet.w_1.bias"] = (256, N_MEL), (256,)
+    out["mel_encoder.prenet.w_2.weight"], out["mel_encoder.prenet.w_2.bias"] = (256, 256), (256,)
+    for i in range(t["decoder_layer"]):
+        p = f"mel_encoder.layer_stack.{i}"
+        for w in ("w_qs", "w_ks", "w_vs"):
+            out[f"{p}.crs_attn.{w}.weight"], out[f"{p}.crs_attn.{w}.bias"] = (d, d), (d,)
+        out[f"{p}.crs_attn.layer_norm.weight"] = out[f"{p}.crs_attn.layer_norm.bias"] = (d,)
+        out[f"{p}.crs_attn.fc.weight"], out[f"{p}.crs_attn.fc.bias"] = (d, d), (d,)
+        out[f"{p}.pos_ffn.w_1.weight"], out[f"{p}.pos_ffn.w_1.bias"] = (di, d, ks[0]), (di,)
+        out[f"{p}.pos_ffn.w_2.weight"], out[f"{p}.pos_ffn.w_2.bias"] = (d, di, ks[1]), (d,)
+        out[f"{p}.pos_ffn.layer_norm.weight"] = out[f"{p}.pos_ffn.layer_norm.bias"] = (d,)
+    return out
+
+
+ALIGNER_QK_GAIN = 3.0
+
+
+def synth_aligner_state_dict(model_cfg: dict, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """Seeded ``mel_encoder.*`` weights with the reference's key names and shapes (``aligner_shapes``).  torch's default scales —
+    U(+-1/sqrt(fan_in)) for Linear / Conv1d weight and bias — with non-trivial LayerNorm affines, and ``w_qs`` / ``w_ks`` weights
+    scaled by ALIGNER_QK_GAIN so that the attention rows have a clear peak (a default-scale draw gives nearly flat rows, whose
+    argmax — what the durations are made of — would be decided by rounding)."""
+    rs = np.random.RandomState(seed + 7001)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for k, shape in aligner_shapes(model_cfg).items():
+        if k.endswith("position_enc"):
+            sd[k] = sinusoid_table(shape[1], shape[2])[None]
+        elif ".layer_norm." in k:
+            sd[k] = ((1.0 if k.endswith(".weight") else 0.0) + (0.1 if k.endswith(".weight") else 0.05) * rs.standard_normal(shape)).astype(np.float32)
+        elif k.endswith(".weight"):
+            gain = ALIGNER_QK_GAIN if (".w_qs." in k or ".w_ks." in k) else 1.0
+            sd[k] = _uniform(rs, shape, gain / math.sqrt(int(np.prod(shape[1:]))))
+        else:
+            w = aligner_shapes(model_cfg)[k[:-len(".bias")] + ".weight"]
+            sd[k] = _uniform(rs, shape, 1.0 / math.sqrt(int(np.prod(w[1:]))))
+    return sd

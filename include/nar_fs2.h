@@ -138,6 +138,31 @@ int ns_forward_durations_packed(ns_model* m, const int64_t* texts, const int64_t
                                 float* log_d, float* d_rounded, uint8_t* src_mask, int64_t* mel_lens, float* p_pred, float* e_pred,
                                 int64_t* mel_lens_host, void* stream);
 int64_t ns_last_phase1_rows(const ns_model* m);
+/* Phase 1 of the TEACHER-FORCED branch (model/fastspeech2_align.py:44,53-58,70-80 with mel_lens given; model/modules.py:128-130):
+ * the recording's own alignment drives the length regulator.  In this order, on `stream`:
+ *   1. TxtEncoder -> enc_out in ws_enc                                                (fastspeech2_align.py:53)
+ *   2. ns_aln_forward(aln, enc_out, src_lens, mels, mel_lens_in, ...) -> tgt_output [B,T,d], attn_all_layers [n_layer,B,H,T,L],
+ *      d_targets [B,L] int64 — the duration rule stated with ns_aln_forward below, the stand-in for the reference's undefined
+ *      _calculate_duration                                                            (fastspeech2_align.py:56-58)
+ *   3. duration predictor -> log_d [B,L] (still computed, model/modules.py:116)
+ *   4. phoneme_level pitch / energy, which add their embeddings into enc_out IN PLACE (model/modules.py:117-126): the aligner
+ *      must have read enc_out before this step — fastspeech2_align.py:53-56 hands it the encoder's output itself
+ *   5. one launch: src_mask, and from d_targets what ns_forward_mel reads out of ws_enc — the prefix sums of max(d, 0)
+ *      (model/modules.py:221-223), the float copy of d — and mel_lens[b] = sum_i max(d_targets[b,i], 0), or -1 for a token id outside
+ *      [0, n_vocab) exactly as ns_forward_durations reports it.
+ * The text encoder runs once.  Always exact fp32, whatever ns_config.matmul_bf16x3 says.  T = mels' frame axis is known up front, so
+ * ns_forward_mel(m, B, L, T, mel_lens, ...) can be enqueued right behind this call with no host read; sum d <= T, so its
+ * NS_STATUS_TRUNCATED bit is never set.  T == 0: no aligner launch, d_targets = 0 (mels, mel_lens_in, tgt_output, attn_all_layers and
+ * ws_aln may be NULL then).  Dense [B,L] grid only: packed phase-1 rows (ns_forward_durations_packed) are out of scope for this
+ * path.  There is no d_rounded output: the reference returns duration_target in that slot (model/modules.py:130), i.e. d_targets.
+ * ws_enc >= ns_encoder_ws_bytes(m, B, L), ws_aln >= ns_aln_ws_bytes(aln, B, L, T), both 256-byte aligned; mels 16-byte aligned.
+ * `aln` must have been created from the same ns_config as `m` (ns_aln_create). */
+typedef struct ns_aligner ns_aligner;
+int ns_forward_durations_teacher(ns_model* m, ns_aligner* aln, const int64_t* texts, const int64_t* src_lens, const float* mels,
+                                 const int64_t* mel_lens_in, int B, int L, int T, float p_control, float e_control,
+                                 const float* p_targets, const float* e_targets, void* ws_enc, size_t ws_enc_bytes, void* ws_aln,
+                                 size_t ws_aln_bytes, float* log_d, uint8_t* src_mask, int64_t* mel_lens, float* p_pred, float* e_pred,
+                                 float* tgt_output, float* attn_all_layers, int64_t* d_targets, void* stream);
 /* Helper for callers whose lengths live on the host: dev[i] = host[i] (int64) on `stream`, the values riding in a kernel's
  * argument block — one ~3 us launch, no copy command (a pinned-staging async copy of these 128 bytes costs a forward ~35 us of
  * blit + stream dependency, a pageable copy ~80 us).  host is read before the call returns. */
@@ -200,6 +225,12 @@ int ns_op_variance_predictor(ns_model* m, const char* prefix, const float* x, co
 int ns_op_duration_round(const float* log_d, int n, float d_control, float* d_rounded, void* stream);
 /* a10 model/modules.py:201-230 + utils/tools.py:288-306: step 1 prefix sums + mel_lens, step 2 gather to [B,T,D] */
 int ns_op_duration_scan(const float* d_rounded, int B, int L, int32_t* cum, int64_t* mel_lens, void* stream);
+/* a10 with GIVEN durations (model/modules.py:128-130, the teacher-forced branch; step 5 of ns_forward_durations_teacher alone):
+ * d_targets [B,L] int64 -> cum [B,L] int32 inclusive prefix sums of max(d, 0) (:221-223), dur_keep [B,L] = (float)d, src_mask [B,L]
+ * = l >= src_lens[b] (utils/tools.py:89-97), mel_lens[b] = the total — or -1 when texts (nullable: no check) holds an id outside
+ * [0, n_vocab) in utterance b.  One launch, one workgroup per utterance. */
+int ns_op_duration_target_scan(const int64_t* d_targets, const int64_t* src_lens, const int64_t* texts /* nullable */, int n_vocab, int B, int L,
+                               int32_t* cum, float* dur_keep, uint8_t* src_mask, int64_t* mel_lens, void* stream);
 int ns_op_length_regulate(const float* x, const int32_t* cum, int B, int L, int D, int T, float* out, void* stream);
 /* a11 model/modules.py:80-100,139-149: which = 0 pitch, 1 energy; x_out = x + embedding[bucketize(pred*control)] (unmasked add) */
 int ns_op_variance_embedding(ns_model* m, int which, const float* x, const int64_t* lens, int B, int S, float control, const float* target /* nullable */, float* pred, float* x_out, void* ws, size_t ws_bytes, void* stream);
@@ -388,7 +419,6 @@ int ns_voc_op_stage(ns_vocoder* v, int i, const float* x, int B, int S, float* o
  * int64 [B, L]; 0 for i >= src_lens[b]; the whole row 0 when src_lens[b] or mel_lens[b] is 0, else sum_i durations[b, i] =
  * min(mel_lens[b], T). */
 #define NS_ALN_ABI_VERSION 1
-typedef struct ns_aligner ns_aligner;
 int ns_aln_abi_version(void);
 /* reads d_enc, d_dec, n_dec_layer, n_dec_head, d_inner, ffn_k1, ffn_k2, n_mel, max_seq_len, row_epilogue of the model's config
  * (transformer/Models.py:106-138) */

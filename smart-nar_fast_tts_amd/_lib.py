@@ -41,6 +41,7 @@ SIGNATURES = {
     "ns_decoder_ws_bytes": (_Z, [_P, _I, _I, _I]),
     "ns_forward_durations": (_I, [_P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ns_forward_durations_packed": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ns_forward_durations_teacher": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _Z, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ns_last_phase1_rows": (C.c_int64, [_P]),
     "ns_upload_lengths": (_I, [_P, _I, _P, _P]),
     "ns_forward_mel": (_I, [_P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P, _P]),
@@ -64,6 +65,7 @@ SIGNATURES = {
     "ns_op_variance_predictor": (_I, [_P, _S, _P, _P, _I, _I, _P, _P, _Z, _P]),
     "ns_op_duration_round": (_I, [_P, _I, _F, _P, _P]),
     "ns_op_duration_scan": (_I, [_P, _I, _I, _P, _P, _P]),
+    "ns_op_duration_target_scan": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "ns_op_length_regulate": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "ns_op_variance_embedding": (_I, [_P, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _Z, _P]),
     "ns_op_bucketize": (_I, [_P, _I, _P, _I, _P, _P]),

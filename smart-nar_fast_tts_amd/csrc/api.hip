@@ -825,10 +825,24 @@ static size_t phase1_packed_extra_bytes(const ns_config& c, int B, int L) {  // 
   return bp.off;
 }
 
+// The teacher-forced branch's extra arguments (ns_forward_durations_teacher; nullptr = the inference branch): the aligner runs
+// between the encoder and the first in-place add into its output, and its durations take the rounded predictions' place.
+struct Teacher {
+  ns_aligner* aln;
+  const float* mels;
+  const int64_t* mel_lens_in;
+  int T;
+  void* ws_aln;
+  size_t ws_aln_bytes;
+  float *tgt_output, *attn;
+  int64_t* d_targets;
+};
+
 static int forward_durations(ns_model* m, const int64_t* texts, const int64_t* src_lens, const int64_t* lens_host, int B, int L, float d_control,
                              float p_control, float e_control, const float* p_targets, const float* e_targets,
                              void* ws_enc, size_t ws_bytes, float* log_d, float* d_rounded, uint8_t* src_mask,
-                             int64_t* mel_lens, float* p_pred, float* e_pred, int64_t* mel_lens_host, void* stream) {
+                             int64_t* mel_lens, float* p_pred, float* e_pred, int64_t* mel_lens_host, void* stream,
+                             const Teacher* tf = nullptr) {
   NS_TRY(check_ready(m));
   if (B <= 0 || L <= 0) return fail("ns_forward_durations: empty batch");
   if (ws_bytes < ns_encoder_ws_bytes(m, B, L)) return fail("ns_forward_durations: workspace too small");
@@ -890,6 +904,14 @@ static int forward_durations(ns_model* m, const int64_t* texts, const int64_t* s
   {
     sc.pk = packed ? &pk : nullptr;
     NS_TRY(encoder(m, (const long long*)texts, lens, B, L, enc_w, sc, st));
+    if (tf) {
+      // model/fastspeech2_align.py:53-58: the MelEncoder reads the text encoder's output as it is HERE — the phoneme-level
+      // adds below write into the same rows (model/modules.py:121,126 rebind x; this path adds in place) — and its durations
+      // replace the rounded predictions.  T == 0: no frame votes for any phoneme, and nothing to launch.
+      if (tf->T > 0) NS_TRY(ns_aln_forward(tf->aln, enc_w, src_lens, tf->mels, tf->mel_lens_in, B, L, tf->T, tf->tgt_output, tf->attn, tf->d_targets,
+                                           tf->ws_aln, tf->ws_aln_bytes, stream));
+      else NS_HIP(hipMemsetAsync(tf->d_targets, 0, (size_t)B * L * sizeof(int64_t), st));
+    }
     NS_TRY(predictor(m, m->pred[0], enc_w, lens, B, L, 1.0f, nullptr, logd_w, nullptr, nullptr, nullptr, nullptr, sc, st));
     // phoneme_level features are predicted on the encoder output, before the length regulator, pitch first, and
     // added in place (model/modules.py:117-126); the duration predictor above saw x before these adds (:116)
@@ -904,6 +926,11 @@ static int forward_durations(ns_model* m, const int64_t* texts, const int64_t* s
   }
   // src mask (utils/tools.py:89-97), duration rounding (model/modules.py:132-135), repeat counts + prefix sums + mel_len
   // (:209-223): one launch
+  if (tf) {  // model/modules.py:128-130: duration_target in the rounded predictions' place
+    NS_HIP(launch_duration_target_tail((const long long*)tf->d_targets, lens, (const long long*)texts, c.n_vocab, B, L, dur_keep, cum,
+                                       (long long*)mel_lens, src_mask, st));
+    return 0;
+  }
   NS_HIP(launch_duration_tail(log_d, lens, (const long long*)texts, c.n_vocab, B, L, d_control, d_rounded, dur_keep, cum,
                               (long long*)mel_lens, src_mask, (long long*)mel_lens_host, st));
   return 0;
@@ -915,6 +942,26 @@ extern "C" int ns_forward_durations(ns_model* m, const int64_t* texts, const int
                                     int64_t* mel_lens, float* p_pred, float* e_pred, int64_t* mel_lens_host, void* stream) {
   return forward_durations(m, texts, src_lens, nullptr, B, L, d_control, p_control, e_control, p_targets, e_targets, ws_enc, ws_bytes, log_d,
                            d_rounded, src_mask, mel_lens, p_pred, e_pred, mel_lens_host, stream);
+}
+
+extern "C" int ns_forward_durations_teacher(ns_model* m, ns_aligner* aln, const int64_t* texts, const int64_t* src_lens, const float* mels,
+                                            const int64_t* mel_lens_in, int B, int L, int T, float p_control, float e_control,
+                                            const float* p_targets, const float* e_targets, void* ws_enc, size_t ws_enc_bytes, void* ws_aln,
+                                            size_t ws_aln_bytes, float* log_d, uint8_t* src_mask, int64_t* mel_lens, float* p_pred, float* e_pred,
+                                            float* tgt_output, float* attn_all_layers, int64_t* d_targets, void* stream) {
+  if (!aln) return fail("ns_forward_durations_teacher: null aligner");
+  if (T < 0) return fail("ns_forward_durations_teacher: negative T");
+  if (!log_d || !src_mask || !mel_lens || !d_targets) return fail("ns_forward_durations_teacher: log_d, src_mask, mel_lens and d_targets are required");
+  if (T > 0 && (!mels || !mel_lens_in || !tgt_output || !attn_all_layers || !ws_aln))
+    return fail("ns_forward_durations_teacher: mels, mel_lens_in, tgt_output, attn_all_layers and ws_aln are required when T > 0");
+  // what ns_aln_forward would refuse only after the encoder's launches were enqueued
+  if (m && m->cfg.d_enc != 256) return fail("ns_forward_durations_teacher: the aligner takes a 256-wide encoder output (ns_aln_create)");
+  if (T > 0 && B > 0 && L > 0 && ws_aln_bytes < ns_aln_ws_bytes(aln, B, L, T)) return fail("ns_forward_durations_teacher: aligner workspace too small (ns_aln_ws_bytes)");
+  if (T > 0 && (((uintptr_t)ws_aln & 255) || ((uintptr_t)ws_enc & 255) || (((uintptr_t)mels | (uintptr_t)tgt_output) & 15)))
+    return fail("ns_forward_durations_teacher: workspaces must be 256-byte aligned, mels and tgt_output 16-byte aligned");
+  const Teacher tf = {aln, mels, mel_lens_in, T, ws_aln, ws_aln_bytes, tgt_output, attn_all_layers, d_targets};
+  return forward_durations(m, texts, src_lens, nullptr, B, L, 1.0f, p_control, e_control, p_targets, e_targets, ws_enc, ws_enc_bytes, log_d,
+                           nullptr, src_mask, mel_lens, p_pred, e_pred, nullptr, stream, &tf);
 }
 
 extern "C" int ns_upload_lengths(const int64_t* host, int n, int64_t* dev, void* stream) {
@@ -1194,6 +1241,14 @@ extern "C" int ns_op_variance_predictor(ns_model* m, const char* prefix, const f
 }
 extern "C" int ns_op_duration_round(const float* log_d, int n, float d_control, float* d_rounded, void* stream) {
   NS_HIP(launch_duration_round(log_d, n, d_control, d_rounded, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ns_op_duration_target_scan(const int64_t* d_targets, const int64_t* src_lens, const int64_t* texts, int n_vocab, int B, int L,
+                                          int32_t* cum, float* dur_keep, uint8_t* src_mask, int64_t* mel_lens, void* stream) {
+  if (B < 0 || L < 0) return fail("ns_op_duration_target_scan: negative size");
+  if (B > 0 && (!src_lens || !mel_lens || (L > 0 && (!d_targets || !cum || !dur_keep || !src_mask)))) return fail("ns_op_duration_target_scan: null argument");
+  NS_HIP(launch_duration_target_tail((const long long*)d_targets, (const long long*)src_lens, (const long long*)texts, n_vocab, B, L, dur_keep, cum,
+                                     (long long*)mel_lens, src_mask, (hipStream_t)stream));
   return 0;
 }
 extern "C" int ns_op_duration_scan(const float* d_rounded, int B, int L, int32_t* cum, int64_t* mel_lens, void* stream) {

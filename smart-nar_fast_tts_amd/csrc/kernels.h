@@ -151,6 +151,10 @@ hipError_t launch_length_regulate(const float* x, const int32_t* cum, int B, int
 hipError_t launch_duration_tail(const float* log_d, const long long* src_lens, const long long* texts, int n_vocab, int B, int L,
                                 float d_control, float* d_rounded, float* d_keep, int32_t* cum, long long* mel_lens, uint8_t* src_mask,
                                 long long* mel_lens_host /* nullable: device-visible host copy */, hipStream_t st);
+// the teacher-forced forward's phase-1 tail in one launch: the same from GIVEN int64 durations [B, L] (model/modules.py:128-130) —
+// src mask, d_keep = (float)d, cum = prefix sums of max(d, 0), mel_lens[b] = total (or -1 for a bad token id; texts nullable)
+hipError_t launch_duration_target_tail(const long long* d_targets, const long long* src_lens, const long long* texts, int n_vocab, int B, int L,
+                                       float* d_keep, int32_t* cum, long long* mel_lens, uint8_t* src_mask, hipStream_t st);
 // Packed variant of launch_length_regulate (kernels.h RowMap).  Builds the plan first: win[b] = min(max(mel_lens[b], 0) + guard, T),
 // off = exclusive scan, row maps for the Mp = sum(win) rows (the caller computed the same Mp from its host copy of mel_lens);
 // then gathers the encoder rows into the packed layout (frames at t >= mel_len[b] are zero).  status as launch_length_regulate.

@@ -311,15 +311,20 @@ hipError_t launch_duration_round(const float* log_d, int n, float d_control, flo
   return hipGetLastError();
 }
 
-// One body, two instantiations.  One workgroup per utterance walks its L phonemes 256 at a time:
-//   TAIL = false  (ns_op_duration_scan): LengthRegulator.expand's repeat counts (model/modules.py:221-223), max(int(d), 0)
-//                 with int() truncating toward zero, their inclusive prefix sums, mel_len[b] = total (:209-211);
-//   TAIL = true   (the forward's phase-1 tail, ONE launch): additionally produces its own input — the rounded durations
-//                 from log_d (two copies: the caller's output and the workspace copy phase 2 reads) — and the source
-//                 mask (utils/tools.py:89-97), and reports a token id outside [0, n_vocab) as mel_len[b] = -1
-//                 (nn.Embedding raises IndexError there; the host raises it after its one read of mel_lens).
-template <bool TAIL>
-__global__ __launch_bounds__(256) void k_duration_scan(const float* __restrict__ in, int L, int32_t* __restrict__ cum,
+// One body, three instantiations.  One workgroup per utterance walks its L phonemes 256 at a time:
+//   SCAN_COUNTS  (ns_op_duration_scan): LengthRegulator.expand's repeat counts (model/modules.py:221-223), max(int(d), 0)
+//                with int() truncating toward zero, their inclusive prefix sums, mel_len[b] = total (:209-211);
+//   SCAN_TAIL    (the forward's phase-1 tail, ONE launch): additionally produces its own input — the rounded durations
+//                from log_d (two copies: the caller's output and the workspace copy phase 2 reads) — and the source
+//                mask (utils/tools.py:89-97), and reports a token id outside [0, n_vocab) as mel_len[b] = -1
+//                (nn.Embedding raises IndexError there; the host raises it after its one read of mel_lens);
+//   SCAN_TARGET  (the teacher-forced forward's phase-1 tail, ns_op_duration_target_scan): the input is the aligner's int64
+//                duration_target [B, L] in the rounded predictions' place (model/modules.py:128-130): the same repeat counts
+//                max(d, 0) and prefix sums, the workspace copy (float)d, the source mask and the bad-token report — no
+//                rounded-duration output (the caller's d_rounded IS the input) and no pinned host copy (nobody reads it).
+enum { SCAN_COUNTS = 0, SCAN_TAIL = 1, SCAN_TARGET = 2 };
+template <int MODE>
+__global__ __launch_bounds__(256) void k_duration_scan(const void* __restrict__ in_v, int L, int32_t* __restrict__ cum,
                                                         long long* __restrict__ mel_lens, const long long* __restrict__ src_lens,
                                                         float d_control, float* __restrict__ d_rounded, float* __restrict__ d_keep,
                                                         uint8_t* __restrict__ src_mask, const long long* __restrict__ texts,
@@ -329,7 +334,7 @@ __global__ __launch_bounds__(256) void k_duration_scan(const float* __restrict__
   __shared__ int bad_s;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   long long len = 0;
-  if constexpr (TAIL) len = src_lens[b];
+  if constexpr (MODE != SCAN_COUNTS) len = src_lens[b];
   if (tid == 0) { carry_s = 0; bad_s = 0; }
   __syncthreads();
   for (int l0 = 0; l0 < L; l0 += 256) {
@@ -337,21 +342,30 @@ __global__ __launch_bounds__(256) void k_duration_scan(const float* __restrict__
     int v = 0;
     if (l < L) {
       const size_t i = (size_t)b * L + l;
-      float dr;
-      if constexpr (TAIL) {
-        dr = duration_round(in[i], d_control);
-        d_rounded[i] = dr;
-        d_keep[i] = dr;
+      if constexpr (MODE != SCAN_COUNTS) {
         src_mask[i] = (long long)l >= len ? 1 : 0;
         if (texts) {
           const long long tok = texts[i];
           if (tok < 0 || tok >= (long long)n_vocab) bad_s = 1;  // benign race: every writer stores 1
         }
-      } else {
-        dr = in[i];
       }
-      const int ri = (int)dr;
-      v = ri > 0 ? ri : 0;
+      if constexpr (MODE == SCAN_TARGET) {
+        const long long d = static_cast<const long long*>(in_v)[i];
+        d_keep[i] = (float)d;
+        v = d > 0 ? (int)(d < 0x7fffffffll ? d : 0x7fffffffll) : 0;
+      } else {
+        const float* in = static_cast<const float*>(in_v);
+        float dr;
+        if constexpr (MODE == SCAN_TAIL) {
+          dr = duration_round(in[i], d_control);
+          d_rounded[i] = dr;
+          d_keep[i] = dr;
+        } else {
+          dr = in[i];
+        }
+        const int ri = (int)dr;
+        v = ri > 0 ? ri : 0;
+      }
     }
     int inc = v;
 #pragma unroll
@@ -373,12 +387,14 @@ __global__ __launch_bounds__(256) void k_duration_scan(const float* __restrict__
     mel_lens[b] = n;
     // optional second copy straight into device-visible (pinned) HOST memory: the caller's one read of mel_lens then needs
     // a stream synchronisation only, no device-to-host copy behind the kernel
-    if (mel_lens_host) mel_lens_host[b] = n;
+    if constexpr (MODE != SCAN_TARGET) {
+      if (mel_lens_host) mel_lens_host[b] = n;
+    }
   }
 }
 hipError_t launch_duration_scan(const float* d_rounded, int B, int L, int32_t* cum, long long* mel_lens, hipStream_t st) {
   if (B <= 0) return hipSuccess;
-  hipLaunchKernelGGL((k_duration_scan<false>), dim3(B), dim3(256), 0, st, d_rounded, L, cum, mel_lens, nullptr, 1.0f, nullptr, nullptr,
+  hipLaunchKernelGGL((k_duration_scan<SCAN_COUNTS>), dim3(B), dim3(256), 0, st, d_rounded, L, cum, mel_lens, nullptr, 1.0f, nullptr, nullptr,
                      nullptr, nullptr, 0, nullptr);
   return hipGetLastError();
 }
@@ -386,8 +402,15 @@ hipError_t launch_duration_tail(const float* log_d, const long long* src_lens, c
                                 float d_control, float* d_rounded, float* d_keep, int32_t* cum, long long* mel_lens, uint8_t* src_mask,
                                 long long* mel_lens_host, hipStream_t st) {
   if (B <= 0) return hipSuccess;
-  hipLaunchKernelGGL((k_duration_scan<true>), dim3(B), dim3(256), 0, st, log_d, L, cum, mel_lens, src_lens, d_control, d_rounded, d_keep,
+  hipLaunchKernelGGL((k_duration_scan<SCAN_TAIL>), dim3(B), dim3(256), 0, st, log_d, L, cum, mel_lens, src_lens, d_control, d_rounded, d_keep,
                      src_mask, texts, n_vocab, mel_lens_host);
+  return hipGetLastError();
+}
+hipError_t launch_duration_target_tail(const long long* d_targets, const long long* src_lens, const long long* texts, int n_vocab, int B, int L,
+                                       float* d_keep, int32_t* cum, long long* mel_lens, uint8_t* src_mask, hipStream_t st) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL((k_duration_scan<SCAN_TARGET>), dim3(B), dim3(256), 0, st, d_targets, L, cum, mel_lens, src_lens, 1.0f, nullptr, d_keep,
+                     src_mask, texts, n_vocab, nullptr);
   return hipGetLastError();
 }
 

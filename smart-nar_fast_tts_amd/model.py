@@ -705,8 +705,9 @@ class FastSpeech2Align:
           the returned output's ``status`` tensor: call ``out.check()`` (or ``model.check_status(out)``) before trusting it."""
         if mel_lens is not None:
             raise NotImplementedError(
-                "teacher-forced / training branch is out of scope; in the reference it calls an undefined "
-                "self._calculate_duration (model/fastspeech2_align.py:57)")
+                "forward() does not take mel_lens: the reference's own teacher-forced branch calls an undefined "
+                "self._calculate_duration (model/fastspeech2_align.py:57) and cannot run; use forward_teacher_forced(), which "
+                "runs that branch with the duration rule of align() (DESIGN.md §13)")
         if not texts.is_cuda:
             raise RuntimeError("inputs must live on the MI355X (cuda) device; there is no CPU path")
         if self._device != texts.device:
@@ -867,4 +868,104 @@ class FastSpeech2Align:
         # check_status() without an argument needs the status words only: keep those, not the output blocks (a long-form batch's
         # mel / PostNet tensors would otherwise stay pinned until the next forward after the caller has dropped them)
         self._last_out = ForwardOutput((), status=status, n_vocab=self._cfg.n_vocab)
+        return out
+
+    def forward_teacher_forced(self, speakers, texts, src_lens, max_src_len, mels, mel_lens, max_mel_len=None,
+                               p_targets=None, e_targets=None, p_control=1.0, e_control=1.0, *, async_status=False):
+        """model/fastspeech2_align.py:30-100 with ``mel_lens`` given (``is_training``, :44) in eval(): the recording's mel frames
+        ``mels`` [B, T, 80] go through the MelEncoder (:56), its last alignment becomes per-phoneme durations (:57-58 — the rule
+        of ``align()``, the stand-in for the reference's undefined ``_calculate_duration``) and THOSE durations, not the
+        predicted ones, expand the encoder output (model/modules.py:128-130).  Returns the reference's 12-tuple (a
+        ``ForwardOutput``): slot 10 ``tgt_alignment`` (one [B, H, T, L] map per layer), slot 11 ``d_targets`` int64 [B, L], slot 5
+        ``d_rounded`` = the same tensor (modules.py:130), slot 4 the duration predictor's output all the same (:116), slot 9
+        ``mel_lens`` = the durations' row sums and slot 7 ``mel_masks`` = ``t >= mel_lens[b]`` (the reference masks with the INPUT
+        mel_lens; the two differ only for an utterance with src_lens == 0, whose durations are all zero — DESIGN.md §13).
+
+        A separate method because ``forward(mel_lens=...)`` keeps refusing what the reference itself cannot run.  The mel axis is
+        ``T = mels.shape[1]``, known up front, so the whole call is enqueued without a device-to-host read; by default the method
+        then calls ``out.check()`` (ONE synchronisation: a token id outside the vocabulary raises ``IndexError`` on the spot, like
+        forward()); with ``async_status=True`` nothing synchronises and the caller checks ``out.status`` later.  The truncation
+        bit cannot be set: the durations sum to at most T.  Everything up to and including the durations is exact fp32 whatever
+        ``model_config["matmul"]`` says; the decoder and PostNet run in the configured mode.  ``speakers`` is accepted and ignored."""
+        self._check_aligner_weights()
+        if not (torch.is_tensor(texts) and texts.is_cuda and torch.is_tensor(mels) and mels.is_cuda):
+            raise RuntimeError("inputs must live on the MI355X (cuda) device; there is no CPU path")
+        if mels.dim() != 3 or mels.shape[0] != texts.shape[0] or mels.shape[2] != self._cfg.n_mel:
+            raise ValueError(f"mels must have shape ({int(texts.shape[0])}, T, {self._cfg.n_mel}), got {tuple(mels.shape)}")
+        B, L, T = int(texts.shape[0]), int(texts.shape[1]), int(mels.shape[1])
+        if int(max_src_len) != L:
+            raise ValueError(f"max_src_len ({int(max_src_len)}) must equal texts.shape[1] ({L})")
+        if max_mel_len is not None and int(max_mel_len) != T:
+            raise ValueError(f"max_mel_len ({int(max_mel_len)}) must equal mels.shape[1] ({T})")
+        if L < 1:
+            raise ValueError("forward_teacher_forced(): texts must hold at least one phoneme column")
+        if self._device != texts.device:
+            self.to(texts.device)
+        self._ensure_weights()
+        self._ensure_aligner()
+        lib, dev = self._lib, self._device
+        p_frame, e_frame = bool(self._cfg.pitch_frame_level), bool(self._cfg.energy_frame_level)
+        n_mel, n_layer, H, d = self._cfg.n_mel, self._cfg.n_dec_layer, self._cfg.n_dec_head, self._cfg.d_dec
+        f32, u8, i64, i32 = torch.float32, torch.bool, torch.long, torch.int32
+
+        def lens(name, v):
+            v = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+            if tuple(v.shape) != (B,):
+                raise ValueError(f"{name} must have shape ({B},), got {tuple(v.shape)}")
+            return v.to(device=dev, dtype=torch.long).contiguous()
+
+        def target(name, t, frame):
+            if t is None:
+                return None
+            shape = (B, T) if frame else (B, L)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+            return t.to(device=dev, dtype=torch.float32).contiguous()
+
+        with (contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)):
+            sl, ml = lens("src_lens", src_lens), lens("mel_lens", mel_lens)
+            pt, et = target("p_targets", p_targets, p_frame), target("e_targets", e_targets, e_frame)
+            texts_c = texts.long().contiguous()
+            mels_c = mels.to(torch.float32).contiguous()
+            sh = torch.cuda.current_stream(dev).cuda_stream
+            st = C.c_void_p(sh)
+            o1 = [("log_d", (B, L), f32), ("d_targets", (B, L), i64), ("src_masks", (B, L), u8), ("mel_lens", (B,), i64), ("status", (B,), i32)]
+            o2 = [("mel", (B, T, n_mel), f32), ("post", (B, T, n_mel), f32), ("mel_masks", (B, T), u8)]
+            (o2 if p_frame else o1).append(("p_pred", (B, T) if p_frame else (B, L), f32))
+            (o2 if e_frame else o1).append(("e_pred", (B, T) if e_frame else (B, L), f32))
+            blk1, blk2 = _OutputBlock(o1, dev), _OutputBlock(o2, dev)
+            attn = torch.empty(n_layer, B, H, T, L, dtype=f32, device=dev)
+            ws_enc = self._workspace("enc", self._ws_bytes("enc", B, L, 0), sh)
+            ws_dec = self._workspace("dec", self._ws_bytes("dec", B, L, max(T, 1)), sh)
+            ws_aln = tgt = None
+            if T > 0:  # (the aligner's own output tgt_output is no part of the 12-tuple: scratch)
+                ws_aln = self._workspace("aln", lib.ns_aln_ws_bytes(self._aln_h, B, L, T), sh)
+                tgt = self._workspace("aln_tgt", B * T * d * 4, sh)
+            _lib.check(lib.ns_forward_durations_teacher(
+                self._h, self._aln_h, _lib.ptr(texts_c), _lib.ptr(sl), _lib.ptr(mels_c), _lib.ptr(ml), B, L, T, float(p_control), float(e_control),
+                _lib.ptr(None if p_frame else pt), _lib.ptr(None if e_frame else et), _lib.ptr(ws_enc), ws_enc.numel(),
+                _lib.ptr(ws_aln), 0 if ws_aln is None else ws_aln.numel(), blk1.ptr("log_d"), blk1.ptr("src_masks"), blk1.ptr("mel_lens"),
+                blk1.ptr("p_pred"), blk1.ptr("e_pred"), _lib.ptr(tgt), _lib.ptr(attn), blk1.ptr("d_targets"), st), "ns_forward_durations_teacher")
+            # phase 2 is the inference branch's own, on the dense grid at the caller's T, right behind phase 1: no host read
+            _lib.check(lib.ns_forward_mel(
+                self._h, B, L, T, blk1.ptr("mel_lens"), float(p_control), float(e_control), _lib.ptr(pt if p_frame else None),
+                _lib.ptr(et if e_frame else None), _lib.ptr(ws_enc), _lib.ptr(ws_dec), ws_dec.numel(), blk2.ptr("mel"), blk2.ptr("post"),
+                blk2.ptr("p_pred") if p_frame else None, blk2.ptr("e_pred") if e_frame else None, blk2.ptr("mel_masks"), blk1.ptr("status"), st),
+                "ns_forward_mel")
+            d_targets, status = blk1.view("d_targets"), blk1.view("status")
+            p_pred = (blk2 if p_frame else blk1).view("p_pred")
+            e_pred = (blk2 if e_frame else blk1).view("e_pred")
+            alignment = [attn[i] for i in range(n_layer)]
+            items = [blk2.view("mel"), blk2.view("post"), p_pred, e_pred, blk1.view("log_d"), d_targets, blk1.view("src_masks"),
+                     blk2.view("mel_masks"), src_lens, blk1.view("mel_lens"), alignment, d_targets]
+            if self.outputs == "separate":  # own storage per tensor; slots 5 and 11 stay ONE tensor (model/modules.py:130)
+                with torch.cuda.stream(torch.cuda.current_stream(dev)):
+                    items = [t.clone() if (torch.is_tensor(t) and i != 8) else t for i, t in enumerate(items)]
+                    items[10] = [a.clone() for a in alignment]
+                    items[11] = items[5]
+                    status = status.clone()
+        out = ForwardOutput(tuple(items), status=status, n_vocab=self._cfg.n_vocab)
+        self._last_out = ForwardOutput((), status=status, n_vocab=self._cfg.n_vocab)
+        if not async_status:
+            out.check()
         return out

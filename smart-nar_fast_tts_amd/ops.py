@@ -118,6 +118,25 @@ def length_regulate(x, duration, max_len=None):
     return out, mel_len
 
 
+def duration_target_scan(d_targets, src_lens, texts=None, n_vocab: int = 0):
+    """The teacher-forced forward's phase-1 tail alone (model/modules.py:128-130,221-223 with duration_target given): from int64
+    ``d_targets`` [B,L] returns (cum int32 [B,L] — inclusive prefix sums of max(d, 0) —, dur_keep float32 [B,L] = d, src_mask bool
+    [B,L], mel_lens int64 [B] = the totals).  With ``texts`` [B,L], an utterance holding an id outside [0, n_vocab) reports -1."""
+    lib = _lib.load()
+    B, L = d_targets.shape
+    d_targets, src_lens = d_targets.long().contiguous(), src_lens.long().contiguous()
+    if texts is not None:
+        texts = texts.long().contiguous()
+    dev = d_targets.device
+    cum = torch.empty(B, L, dtype=torch.int32, device=dev)
+    keep = torch.empty(B, L, dtype=torch.float32, device=dev)
+    mask = torch.empty(B, L, dtype=torch.bool, device=dev)
+    mel_len = torch.empty(B, dtype=torch.long, device=dev)
+    _lib.check(lib.ns_op_duration_target_scan(_lib.ptr(d_targets), _lib.ptr(src_lens), _lib.ptr(texts), int(n_vocab), B, L, _lib.ptr(cum),
+                                              _lib.ptr(keep), _lib.ptr(mask), _lib.ptr(mel_len), _st(d_targets)), "duration_target_scan")
+    return cum, keep, mask, mel_len
+
+
 def variance_embedding(model, which: str, x, lens, control: float = 1.0, target=None):
     """get_pitch_embedding / get_energy_embedding + the unmasked add (model/modules.py:80-100,139-149):
     returns (prediction [B,S], x + embedding).  With ``target`` the embedding comes from bucketize(target)."""

@@ -100,7 +100,9 @@ int ns_set_weight(ns_model* m, const char* name, const float* host, const int64_
  * (nn.Module.load_state_dict raises before/without corrupting the module, utils/model.py:21-22). */
 int ns_check_weight(ns_model* m, const char* name, const int64_t* shape, int ndim);
 /* After the last ns_set_weight: repack (conv [out,in,k] -> [out,k,in]; fused QKV), fold eval-mode
- * BatchNorm into the PostNet convs, upload into the arena.  Fails if an inference key is missing. */
+ * BatchNorm into the PostNet convs, upload into the arena.  Fails if an inference key is missing.
+ * Success releases the staged host copies: a second call without staging every key again returns non-zero
+ * ("missing keys: ...") and leaves the model ready on the arena it already has. */
 int ns_finalize_weights(ns_model* m, void* stream);
 /* Non-root ranks: arena bytes arrived by broadcast; mark the model ready without ns_set_weight. */
 int ns_adopt_arena(ns_model* m);

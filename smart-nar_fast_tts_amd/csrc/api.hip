@@ -1,46 +1,20 @@
 // C-ABI (include/nar_fs2.h) over the gfx950 kernels: weight registry/packing, workspace planning and the
 // launch sequence of the FastSpeech2Align inference forward (model/fastspeech2_align.py:30-100).
 // Host-side only; every byte of device memory is provided by the caller.
-#include <cmath>
 #include <cstdio>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
 
 #include "../../include/nar_fs2.h"
-#include "kernels.h"
+#include "host_core.h"
 
 using namespace ns;
 
 static thread_local std::string g_err;
 static int fail(const std::string& s) { g_err = s; return 1; }
-#define NS_HIP(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-#define NS_TRY(expr)              \
-  do {                            \
-    int rc_ = (expr);             \
-    if (rc_) return rc_;          \
-  } while (0)
 
 namespace {
 
-struct LayerW {  // *_b3: bf16x3 planes or NO_B3; *_bf: the "bf16" mode's one rounded plane or NO_B3
-  size_t qkv_w, qkv_b, fc_w, fc_b, ln1_g, ln1_b, w1, w1_b, w2, w2_b, ln2_g, ln2_b, qkv_b3, fc_b3, w1_b3, w2_b3, qkv_bf, fc_bf, w1_bf, w2_bf;
-};
-struct PredW { size_t c1, c1_b, ln1_g, ln1_b, c2, c2_b, ln2_g, ln2_b, lin_w, lin_b; int cin; };
-struct PostW { size_t w, b, w_b3, w_bf; int cin, cout; };
-constexpr size_t NO_B3 = (size_t)-1;
-
-struct Arena {
-  size_t n = 0;  // floats
-  size_t take(size_t floats) { size_t o = n; n += (floats + 63) & ~(size_t)63; return o; }
-};
-
-struct Staged { std::vector<int64_t> shape; std::vector<float> data; bool set = false; bool optional = false; };
+struct LayerW { ConvW qkv, fc, w1, w2; size_t ln1_g, ln1_b, ln2_g, ln2_b; };  // qkv: the fused projection, rows Q | K | V
+struct PredW { ConvW c1, c2; size_t ln1_g, ln1_b, ln2_g, ln2_b, lin_w, lin_b; };
 
 }  // namespace
 
@@ -49,16 +23,25 @@ struct ns_model {
   std::vector<LayerW> enc, dec;
   PredW pred[3];
   size_t hdr;  // arena header: magic, layout version, arena size, config hash (arena_header below)
-  size_t emb, enc_pos, dec_pos, pitch_bins, energy_bins, pitch_emb, energy_emb, mel_w, mel_b;
-  size_t mel_bf;                   // "bf16" mode: mel_linear's rounded plane (else NO_B3)
+  size_t emb, enc_pos, dec_pos, pitch_bins, energy_bins, pitch_emb, energy_emb;
+  ConvW mel_linear;                // ("bf16" mode: with its rounded plane)
   size_t pn_in, pn_hid, pn_const;  // derived at ns_finalize_weights: the PostNet over an all-padding utterance (packed rows, forward_mel)
   size_t pos_long;                 // derived at ns_finalize_weights: the sinusoid table regenerated for POS_LONG_ROWS positions (position_rows)
-  std::vector<PostW> post;
+  std::vector<ConvW> post;  // BatchNorm folded in (ns_finalize_weights)
   Arena ar;
   float* arena = nullptr;
   bool ready = false;
-  std::map<std::string, Staged> staged;
+  WeightRegistry weights;
   const float* P(size_t off) const { return arena + off; }
+  const unsigned short* plane(size_t off) const { return off != NO_PLANE ? reinterpret_cast<const unsigned short*>(P(off)) : nullptr; }
+  // the contraction of one weight, complete but for its activations: weight / bias / plane pointers, shape, "same" padding
+  ConvGemm conv(const ConvW& w) const {
+    ConvGemm p;
+    memset(&p, 0, sizeof(p));
+    p.W = P(w.w); p.bias = P(w.b); p.Wb3 = plane(w.b3); p.Wbf = plane(w.bf);
+    p.N = w.cout; p.Cin = w.cin; p.KW = w.kw; p.pad = (w.kw - 1) / 2;
+    return p;
+  }
   // optional HIP-event timing of the three heaviest launch groups inside the real forward (bench.py's roofline legs):
   // slot 0 = FFN w_1 (k=9 Conv1D-as-GEMM, the dominant kernel), 1 = fused attention, 2 = PostNet 512->512 k=5 layers.
   // Measurement state: the only per-call state the MODEL carries (with the two row counts below) — the packed-row context of a
@@ -101,7 +84,21 @@ constexpr int POS_LONG_ROWS = 8192;
 constexpr int PN_CONST_ROWS = 32;  // synthetic all-padding utterance: rows [10, 22) are deep padding, [22, 32) see the end of the axis
 
 static void expect(ns_model* m, const std::string& name, std::vector<int64_t> shape, bool optional = false) {
-  Staged s; s.shape = std::move(shape); s.optional = optional; m->staged[name] = std::move(s);
+  m->weights.expect(name, std::move(shape), optional);
+}
+
+// Plane offsets follow a layer's fp32 weights in the arena (never each weight: the arena layout, ARENA_LAYOUT_VERSION)
+static void take_b3(Arena& ar, ConvW& w) { w.b3 = ar.take((3 * w.elems() + 1) / 2); }
+static void take_bf(Arena& ar, ConvW& w) { w.bf = ar.take((bf16_plane_elems(w.cout, w.kw, w.cin) + 1) / 2); }
+// what ns_finalize_weights writes there, from the packed fp32 values at img[w.w]: bf16x3 splits them exactly into three planes,
+// bf16 rounds them once
+static void fill_planes(float* img, const ConvW& w) {
+  if (w.b3 != NO_PLANE) {
+    const size_t n = w.elems();
+    unsigned short* pl = reinterpret_cast<unsigned short*>(&img[w.b3]);
+    split_weights_b3(&img[w.w], n, pl, pl + n, pl + 2 * n);
+  }
+  if (w.bf != NO_PLANE) round_weights_bf16(&img[w.w], w.cout, w.kw, w.cin, reinterpret_cast<unsigned short*>(&img[w.bf]));
 }
 
 static void plan_stack(ns_model* m, const char* prefix, int n_layer, int d, std::vector<LayerW>& out, bool decoder) {
@@ -121,27 +118,19 @@ static void plan_stack(ns_model* m, const char* prefix, int n_layer, int d, std:
     expect(m, p + ".pos_ffn.layer_norm.weight", {d});
     expect(m, p + ".pos_ffn.layer_norm.bias", {d});
     LayerW L;
-    L.qkv_w = m->ar.take((size_t)3 * d * d); L.qkv_b = m->ar.take(3 * d);
-    L.fc_w = m->ar.take((size_t)d * d); L.fc_b = m->ar.take(d);
+    L.qkv = m->ar.conv(3 * d, 1, d);
+    L.fc = m->ar.conv(d, 1, d);
     L.ln1_g = m->ar.take(d); L.ln1_b = m->ar.take(d);
-    L.w1 = m->ar.take((size_t)c.d_inner * c.ffn_k1 * d); L.w1_b = m->ar.take(c.d_inner);
-    L.w2 = m->ar.take((size_t)d * c.ffn_k2 * c.d_inner); L.w2_b = m->ar.take(d);
+    L.w1 = m->ar.conv(c.d_inner, c.ffn_k1, d);
+    L.w2 = m->ar.conv(d, c.ffn_k2, c.d_inner);
     L.ln2_g = m->ar.take(d); L.ln2_b = m->ar.take(d);
     // opt-in bf16x3 mode: three bf16 planes of the (packed) k=9 weights of the DECODER stack — 1.5x their fp32 size
     // (decoder stack only: everything upstream of the duration / pitch / energy decisions stays exact fp32)
-    const bool b3 = c.matmul_bf16x3 == 1 && decoder;
-    auto planes = [&](size_t n) { return b3 ? m->ar.take((3 * n + 1) / 2) : NO_B3; };
-    L.qkv_b3 = planes((size_t)3 * d * d);
-    L.fc_b3 = planes((size_t)d * d);
-    L.w1_b3 = planes((size_t)c.d_inner * c.ffn_k1 * d);
-    L.w2_b3 = planes((size_t)d * c.ffn_k2 * c.d_inner);
+    if (c.matmul_bf16x3 == 1 && decoder)
+      for (ConvW* w : {&L.qkv, &L.fc, &L.w1, &L.w2}) take_b3(m->ar, *w);
     // opt-in bf16 mode: ONE plane per decoder weight, rounded to nearest even (gemm_bf16.hip layout: channels padded to 32)
-    const bool bf = c.matmul_bf16x3 == 2 && decoder;
-    auto plane = [&](int n, int kw, int cin) { return bf ? m->ar.take((bf16_plane_elems(n, kw, cin) + 1) / 2) : NO_B3; };
-    L.qkv_bf = plane(3 * d, 1, d);
-    L.fc_bf = plane(d, 1, d);
-    L.w1_bf = plane(c.d_inner, c.ffn_k1, d);
-    L.w2_bf = plane(d, c.ffn_k2, c.d_inner);
+    if (c.matmul_bf16x3 == 2 && decoder)
+      for (ConvW* w : {&L.qkv, &L.fc, &L.w1, &L.w2}) take_bf(m->ar, *w);
     out.push_back(L);
   }
 }
@@ -194,10 +183,9 @@ extern "C" int ns_create(const ns_config* cfg, ns_model** out) {
     expect(m, p + ".linear_layer.weight", {1, F});
     expect(m, p + ".linear_layer.bias", {1});
     PredW& w = m->pred[i];
-    w.cin = d;
-    w.c1 = m->ar.take((size_t)F * K * d); w.c1_b = m->ar.take(F);
+    w.c1 = m->ar.conv(F, K, d);
     w.ln1_g = m->ar.take(F); w.ln1_b = m->ar.take(F);
-    w.c2 = m->ar.take((size_t)F * K * F); w.c2_b = m->ar.take(F);
+    w.c2 = m->ar.conv(F, K, F);
     w.ln2_g = m->ar.take(F); w.ln2_b = m->ar.take(F);
     w.lin_w = m->ar.take(F); w.lin_b = m->ar.take(1);
   }
@@ -209,18 +197,17 @@ extern "C" int ns_create(const ns_config* cfg, ns_model** out) {
   m->pitch_emb = m->ar.take((size_t)c.n_bins * d); m->energy_emb = m->ar.take((size_t)c.n_bins * d);
   expect(m, "mel_linear.weight", {c.n_mel, c.d_dec});
   expect(m, "mel_linear.bias", {c.n_mel});
-  m->mel_w = m->ar.take((size_t)c.n_mel * c.d_dec); m->mel_b = m->ar.take(c.n_mel);
-  m->mel_bf = c.matmul_bf16x3 == 2 ? m->ar.take((bf16_plane_elems(c.n_mel, 1, c.d_dec) + 1) / 2) : NO_B3;
+  m->mel_linear = m->ar.conv(c.n_mel, 1, c.d_dec);
+  if (c.matmul_bf16x3 == 2) take_bf(m->ar, m->mel_linear);
   for (int i = 0; i < c.postnet_n; ++i) {
     const int cin = i == 0 ? c.n_mel : c.postnet_dim, cout = i == c.postnet_n - 1 ? c.n_mel : c.postnet_dim;
     std::string p = "postnet.convolutions." + std::to_string(i);
     expect(m, p + ".0.conv.weight", {cout, cin, c.postnet_k});
     expect(m, p + ".0.conv.bias", {cout});
     for (const char* s : {"weight", "bias", "running_mean", "running_var"}) expect(m, p + ".1." + s, {cout});
-    PostW w; w.cin = cin; w.cout = cout;
-    w.w = m->ar.take((size_t)cout * c.postnet_k * cin); w.b = m->ar.take(cout);
-    w.w_b3 = (c.matmul_bf16x3 == 1 && cin == c.postnet_dim && cout == c.postnet_dim) ? m->ar.take(((size_t)3 * cout * c.postnet_k * cin + 1) / 2) : NO_B3;
-    w.w_bf = c.matmul_bf16x3 == 2 ? m->ar.take((bf16_plane_elems(cout, c.postnet_k, cin) + 1) / 2) : NO_B3;  // all five layers
+    ConvW w = m->ar.conv(cout, c.postnet_k, cin);
+    if (c.matmul_bf16x3 == 1 && cin == c.postnet_dim && cout == c.postnet_dim) take_b3(m->ar, w);
+    if (c.matmul_bf16x3 == 2) take_bf(m->ar, w);  // all five layers
     m->post.push_back(w);
   }
   // PostNet constants for packed rows (forward_mel): input, ping-pong scratch and output of one PostNet run over
@@ -241,14 +228,7 @@ extern "C" void ns_destroy(ns_model* m) {
 }
 extern "C" size_t ns_arena_bytes(const ns_model* m) { return m ? m->ar.n * sizeof(float) : 0; }
 
-extern "C" int ns_bind_arena(ns_model* m, void* dev, size_t bytes) {
-  if (!m || !dev) return fail("ns_bind_arena: null argument");
-  if (bytes < ns_arena_bytes(m)) return fail("ns_bind_arena: arena too small");
-  if ((uintptr_t)dev & 255) return fail("ns_bind_arena: arena must be 256-byte aligned");
-  m->arena = (float*)dev;
-  m->ready = false;
-  return 0;
-}
+extern "C" int ns_bind_arena(ns_model* m, void* dev, size_t bytes) { return bind_arena(m, dev, bytes, ns_arena_bytes(m), "ns_bind_arena"); }
 
 extern "C" int ns_adopt_arena(ns_model* m) {
   if (!m || !m->arena) return fail("ns_adopt_arena: no arena bound");
@@ -269,7 +249,7 @@ extern "C" int ns_adopt_arena(ns_model* m) {
   if (got[2] != want[2] || got[3] != want[3]) return fail("ns_adopt_arena: arena size differs from ns_arena_bytes of this model");
   if (got[4] != want[4] || got[5] != want[5]) return fail("ns_adopt_arena: the arena was packed for a different ns_config");
   if (got[6] != 1) return fail("ns_adopt_arena: the arena was not finalized (ns_finalize_weights did not complete)");
-  for (auto& kv : m->staged) { kv.second.data.clear(); kv.second.data.shrink_to_fit(); kv.second.set = false; }
+  m->weights.release();
   m->ready = true;
   return 0;
 }
@@ -279,85 +259,36 @@ static bool ends_with(const std::string& s, const char* p) {
   size_t n = strlen(p); return s.size() >= n && s.compare(s.size() - n, n, p) == 0;
 }
 
-// name / rank / shape validation shared by ns_check_weight (no side effect) and ns_set_weight; *slot = nullptr for an ignored key
-static int lookup_weight(ns_model* m, const char* name_c, const int64_t* shape, int ndim, Staged** slot, size_t* count, const char* who) {
-  *slot = nullptr;
-  if (!m || !name_c) return fail(std::string(who) + ": null argument");
-  std::string name(name_c);
-  // training-only aligner weights live in every checkpoint; accept and ignore
-  if (starts_with(name, "mel_encoder.") || ends_with(name, ".num_batches_tracked")) return 0;
-  auto it = m->staged.find(name);
-  if (it == m->staged.end()) return fail(std::string(who) + ": unexpected key '" + name + "'");
-  Staged& s = it->second;
-  if ((int)s.shape.size() != ndim) return fail(std::string(who) + ": rank mismatch for '" + name + "'");
-  if (ndim > 0 && !shape) return fail(std::string(who) + ": null shape for '" + name + "'");
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) {
-    if (shape[i] != s.shape[i]) {
-      return fail(std::string(who) + ": size mismatch for '" + name + "': dim " + std::to_string(i) + " is " +
-                  std::to_string(shape[i]) + ", expected " + std::to_string(s.shape[i]));
-    }
-    n *= (size_t)shape[i];
-  }
-  *slot = &s;
-  *count = n;
-  return 0;
-}
+// training-only aligner weights live in every checkpoint; accept and ignore
+static bool ignored_key(const char* name) { return starts_with(name, "mel_encoder.") || ends_with(name, ".num_batches_tracked"); }
 
 extern "C" int ns_check_weight(ns_model* m, const char* name, const int64_t* shape, int ndim) {
-  Staged* s; size_t n;
-  return lookup_weight(m, name, shape, ndim, &s, &n, "ns_check_weight");
+  if (m && name && ignored_key(name)) return 0;
+  return check_weight(m, name, shape, ndim, "ns_check_weight");
 }
 
-extern "C" int ns_set_weight(ns_model* m, const char* name_c, const float* host, const int64_t* shape, int ndim) {
-  Staged* s; size_t n;
-  NS_TRY(lookup_weight(m, name_c, shape, ndim, &s, &n, "ns_set_weight"));
-  if (!s) return 0;
-  if (!host) return fail(std::string("ns_set_weight: null data for '") + name_c + "'");
-  s->data.assign(host, host + n);
-  s->set = true;
-  m->ready = false;
-  return 0;
-}
-
-// conv weight [out][in][k] (torch) -> [out][k][in] (tap-major K for the implicit GEMM), optional per-out scale
-static void pack_conv(const std::vector<float>& w, int cout, int cin, int k, float* dst, const double* scale = nullptr) {
-  for (int o = 0; o < cout; ++o)
-    for (int c = 0; c < cin; ++c)
-      for (int j = 0; j < k; ++j) {
-        double v = w[((size_t)o * cin + c) * k + j];
-        if (scale) v *= scale[o];
-        dst[((size_t)o * k + j) * cin + c] = (float)v;
-      }
-}
-
-static void host_sinusoid(int n_pos, int d, float* dst) {  // transformer/Models.py:10-30
-  for (int p = 0; p < n_pos; ++p)
-    for (int j = 0; j < d; ++j) {
-      const double ang = (double)p / std::pow(10000.0, (double)(2 * (j / 2)) / (double)d);
-      dst[(size_t)p * d + j] = (float)((j & 1) ? std::cos(ang) : std::sin(ang));
-    }
+extern "C" int ns_set_weight(ns_model* m, const char* name, const float* host, const int64_t* shape, int ndim) {
+  if (m && name && ignored_key(name)) return 0;
+  return set_weight(m, name, host, shape, ndim, "ns_set_weight");
 }
 
 static int postnet_constants(ns_model* m, hipStream_t st);  // (below, next to postnet())
 extern "C" int ns_finalize_weights(ns_model* m, void* stream) {
   if (!m) return fail("ns_finalize_weights: null model");
   if (!m->arena) return fail("ns_finalize_weights: bind an arena first (ns_bind_arena)");
-  std::string missing;
-  for (auto& kv : m->staged)
-    if (!kv.second.set && !kv.second.optional) missing += (missing.empty() ? "" : ", ") + kv.first;
-  if (!missing.empty()) return fail("ns_finalize_weights: missing keys: " + missing);
+  const std::vector<std::string> missing = m->weights.missing();
+  if (!missing.empty()) return fail("ns_finalize_weights: missing keys: " + join_names(missing));
   const ns_config& c = m->cfg;
   std::vector<float> img(m->ar.n, 0.f);
-  auto S = [&](const std::string& k) -> const std::vector<float>& { return m->staged[k].data; };
+  auto S = [&](const std::string& k) -> const std::vector<float>& { return m->weights.data(k); };
   auto cp = [&](size_t off, const std::string& k) { const auto& v = S(k); memcpy(&img[off], v.data(), v.size() * sizeof(float)); };
 
   arena_header(m, reinterpret_cast<uint32_t*>(&img[m->hdr]));
   cp(m->emb, "txt_encoder.src_word_emb.weight");
   const int npos = c.max_seq_len + 1;
-  if (m->staged["txt_encoder.position_enc"].set) cp(m->enc_pos, "txt_encoder.position_enc");
+  if (m->weights.is_set("txt_encoder.position_enc")) cp(m->enc_pos, "txt_encoder.position_enc");
   else host_sinusoid(npos, c.d_enc, &img[m->enc_pos]);
-  if (m->staged["mel_decoder.position_enc"].set) cp(m->dec_pos, "mel_decoder.position_enc");
+  if (m->weights.is_set("mel_decoder.position_enc")) cp(m->dec_pos, "mel_decoder.position_enc");
   else host_sinusoid(npos, c.d_dec, &img[m->dec_pos]);
 
   auto do_stack = [&](const char* prefix, std::vector<LayerW>& Ls, int d) {
@@ -366,32 +297,15 @@ extern "C" int ns_finalize_weights(ns_model* m, void* stream) {
       std::string p = std::string(prefix) + ".layer_stack." + std::to_string(i);
       const char* qkv[3] = {"w_qs", "w_ks", "w_vs"};
       for (int t = 0; t < 3; ++t) {  // fused projection: rows [0,d) = Q, [d,2d) = K, [2d,3d) = V
-        memcpy(&img[L.qkv_w + (size_t)t * d * d], S(p + ".slf_attn." + qkv[t] + ".weight").data(), (size_t)d * d * 4);
-        memcpy(&img[L.qkv_b + (size_t)t * d], S(p + ".slf_attn." + qkv[t] + ".bias").data(), (size_t)d * 4);
+        memcpy(&img[L.qkv.w + (size_t)t * d * d], S(p + ".slf_attn." + qkv[t] + ".weight").data(), (size_t)d * d * 4);
+        memcpy(&img[L.qkv.b + (size_t)t * d], S(p + ".slf_attn." + qkv[t] + ".bias").data(), (size_t)d * 4);
       }
-      cp(L.fc_w, p + ".slf_attn.fc.weight"); cp(L.fc_b, p + ".slf_attn.fc.bias");
+      cp(L.fc.w, p + ".slf_attn.fc.weight"); cp(L.fc.b, p + ".slf_attn.fc.bias");
       cp(L.ln1_g, p + ".slf_attn.layer_norm.weight"); cp(L.ln1_b, p + ".slf_attn.layer_norm.bias");
-      pack_conv(S(p + ".pos_ffn.w_1.weight"), c.d_inner, d, c.ffn_k1, &img[L.w1]); cp(L.w1_b, p + ".pos_ffn.w_1.bias");
+      pack_conv(S(p + ".pos_ffn.w_1.weight"), c.d_inner, d, c.ffn_k1, &img[L.w1.w]); cp(L.w1.b, p + ".pos_ffn.w_1.bias");
       cp(L.ln2_g, p + ".pos_ffn.layer_norm.weight"); cp(L.ln2_b, p + ".pos_ffn.layer_norm.bias");
-      pack_conv(S(p + ".pos_ffn.w_2.weight"), d, c.d_inner, c.ffn_k2, &img[L.w2]); cp(L.w2_b, p + ".pos_ffn.w_2.bias");
-      // opt-in bf16x3 mode: the SAME packed fp32 values, split exactly into three bf16 planes
-      auto split = [&](size_t src, size_t dst, size_t n) {
-        if (dst == NO_B3) return;
-        unsigned short* pl = reinterpret_cast<unsigned short*>(&img[dst]);
-        split_weights_b3(&img[src], n, pl, pl + n, pl + 2 * n);
-      };
-      split(L.qkv_w, L.qkv_b3, (size_t)3 * d * d);
-      split(L.fc_w, L.fc_b3, (size_t)d * d);
-      split(L.w1, L.w1_b3, (size_t)c.d_inner * c.ffn_k1 * d);
-      split(L.w2, L.w2_b3, (size_t)d * c.ffn_k2 * c.d_inner);
-      // opt-in bf16 mode: the same packed fp32 values, rounded once
-      auto round_bf = [&](size_t src, size_t dst, int n, int kw, int cin) {
-        if (dst != NO_B3) round_weights_bf16(&img[src], n, kw, cin, reinterpret_cast<unsigned short*>(&img[dst]));
-      };
-      round_bf(L.qkv_w, L.qkv_bf, 3 * d, 1, d);
-      round_bf(L.fc_w, L.fc_bf, d, 1, d);
-      round_bf(L.w1, L.w1_bf, c.d_inner, c.ffn_k1, d);
-      round_bf(L.w2, L.w2_bf, d, c.ffn_k2, c.d_inner);
+      pack_conv(S(p + ".pos_ffn.w_2.weight"), d, c.d_inner, c.ffn_k2, &img[L.w2.w]); cp(L.w2.b, p + ".pos_ffn.w_2.bias");
+      for (const ConvW* w : {&L.qkv, &L.fc, &L.w1, &L.w2}) fill_planes(img.data(), *w);  // (opt-in bf16x3 / bf16 modes)
     }
   };
   do_stack("txt_encoder", m->enc, c.d_enc);
@@ -400,22 +314,22 @@ extern "C" int ns_finalize_weights(ns_model* m, void* stream) {
   for (int i = 0; i < 3; ++i) {
     const PredW& w = m->pred[i];
     std::string p = std::string("variance_adaptor.") + kPredNames[i] + "_predictor";
-    pack_conv(S(p + ".conv_layer.conv1d_1.conv.weight"), c.vp_filter, w.cin, c.vp_kernel, &img[w.c1]);
-    cp(w.c1_b, p + ".conv_layer.conv1d_1.conv.bias");
+    pack_conv(S(p + ".conv_layer.conv1d_1.conv.weight"), c.vp_filter, w.c1.cin, c.vp_kernel, &img[w.c1.w]);
+    cp(w.c1.b, p + ".conv_layer.conv1d_1.conv.bias");
     cp(w.ln1_g, p + ".conv_layer.layer_norm_1.weight"); cp(w.ln1_b, p + ".conv_layer.layer_norm_1.bias");
-    pack_conv(S(p + ".conv_layer.conv1d_2.conv.weight"), c.vp_filter, c.vp_filter, c.vp_kernel, &img[w.c2]);
-    cp(w.c2_b, p + ".conv_layer.conv1d_2.conv.bias");
+    pack_conv(S(p + ".conv_layer.conv1d_2.conv.weight"), c.vp_filter, c.vp_filter, c.vp_kernel, &img[w.c2.w]);
+    cp(w.c2.b, p + ".conv_layer.conv1d_2.conv.bias");
     cp(w.ln2_g, p + ".conv_layer.layer_norm_2.weight"); cp(w.ln2_b, p + ".conv_layer.layer_norm_2.bias");
     cp(w.lin_w, p + ".linear_layer.weight"); cp(w.lin_b, p + ".linear_layer.bias");
   }
   cp(m->pitch_bins, "variance_adaptor.pitch_bins"); cp(m->energy_bins, "variance_adaptor.energy_bins");
   cp(m->pitch_emb, "variance_adaptor.pitch_embedding.weight"); cp(m->energy_emb, "variance_adaptor.energy_embedding.weight");
-  cp(m->mel_w, "mel_linear.weight"); cp(m->mel_b, "mel_linear.bias");
-  if (m->mel_bf != NO_B3) round_weights_bf16(&img[m->mel_w], c.n_mel, 1, c.d_dec, reinterpret_cast<unsigned short*>(&img[m->mel_bf]));
+  cp(m->mel_linear.w, "mel_linear.weight"); cp(m->mel_linear.b, "mel_linear.bias");
+  fill_planes(img.data(), m->mel_linear);
 
   // PostNet: fold eval-mode BatchNorm1d (running stats, eps 1e-5) into the conv (transformer/Layers.py:120-167)
   for (size_t i = 0; i < m->post.size(); ++i) {
-    const PostW& w = m->post[i];
+    const ConvW& w = m->post[i];
     std::string p = "postnet.convolutions." + std::to_string(i);
     const auto &g = S(p + ".1.weight"), &b = S(p + ".1.bias"), &mu = S(p + ".1.running_mean"), &var = S(p + ".1.running_var");
     const auto& cb = S(p + ".0.conv.bias");
@@ -425,53 +339,28 @@ extern "C" int ns_finalize_weights(ns_model* m, void* stream) {
       img[w.b + o] = (float)(((double)cb[o] - (double)mu[o]) * sc[o] + (double)b[o]);
     }
     pack_conv(S(p + ".0.conv.weight"), w.cout, w.cin, c.postnet_k, &img[w.w], sc.data());
-    if (w.w_b3 != NO_B3) {
-      const size_t n = (size_t)w.cout * c.postnet_k * w.cin;
-      unsigned short* pl = reinterpret_cast<unsigned short*>(&img[w.w_b3]);
-      split_weights_b3(&img[w.w], n, pl, pl + n, pl + 2 * n);
-    }
     // bf16 mode: rounded after the fp64 BatchNorm fold (the plane holds exactly the fp32 weights the fp32 path uses, rounded)
-    if (w.w_bf != NO_B3) round_weights_bf16(&img[w.w], w.cout, c.postnet_k, w.cin, reinterpret_cast<unsigned short*>(&img[w.w_bf]));
+    fill_planes(img.data(), w);
   }
   hipStream_t st = (hipStream_t)stream;
   NS_HIP(hipMemcpyAsync(m->arena, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, st));
   NS_TRY(postnet_constants(m, st));
   NS_HIP(launch_sinusoid(POS_LONG_ROWS, c.d_dec, m->arena + m->pos_long, st));
   NS_HIP(hipStreamSynchronize(st));  // img is a local; also makes load_state_dict() synchronous like the reference's
-  for (auto& kv : m->staged) { kv.second.data.clear(); kv.second.data.shrink_to_fit(); }
+  m->weights.release();
   m->ready = true;
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------- workspace
 namespace {
-struct Bump {
-  char* base; size_t off = 0, cap;
-  Bump(void* p, size_t c) : base((char*)p), cap(c) {}
-  float* f(size_t n) { return (float*)raw(n * sizeof(float)); }
-  void* raw(size_t bytes) {
-    size_t o = off; off += (bytes + 255) & ~(size_t)255;
-    return base ? base + o : nullptr;
-  }
-};
-
-// ticket counters of one forward phase (gemm_conv.hip TICKET, attention.hip): zeroed as a block by the phase's first kernel,
-// every ticketed launch then takes its own slice — no reset, no reuse inside a phase
-constexpr int TICKET_INTS = 16384;
-
 struct PackedCtx { RowMap rm; int Mp; };
 
 struct Scratch {  // per-stack temporaries for M rows
   const PackedCtx* pk;  // packed-row context of the phase this scratch serves (see cur_rm below); nullptr = dense grid
   float *xa, *xb, *qkv, *att, *t1, *x1, *hid, *vp1, *vp2, *pos_ext, *att_part;
   size_t att_part_floats;
-  int* tickets; int tickets_used;
-  int* take_tickets(int n) {  // nullptr when the block is spent (the caller then takes the two-launch form)
-    if (!tickets || tickets_used + n > TICKET_INTS) return nullptr;
-    int* t = tickets + tickets_used;
-    tickets_used += n;
-    return t;
-  }
+  Tickets tk;  // the phase's ticket block (host_core.h)
 };
 
 static size_t imax(size_t a, size_t b) { return a > b ? a : b; }
@@ -485,7 +374,6 @@ static Scratch carve(const ns_config& c, Bump& bp, size_t M, int S, bool no_spli
   s.hid = bp.f(M * imax(c.d_inner, 2 * (size_t)c.postnet_dim));
   s.vp1 = bp.f(M * c.vp_filter); s.vp2 = bp.f(M * c.vp_filter);
   s.pos_ext = S > c.max_seq_len ? bp.f((size_t)S * d) : nullptr;
-  // attention's split-key partials: only launches with few workgroups take that path (kernels.h)
   // attention's split-key partials: few workgroups (small grids), or a last round of 256 that fills badly (attention.hip
   // plan_key_split) — as many key ranges as either stack's launch of this shape will ask for
   const int hmax = c.n_enc_head > c.n_dec_head ? c.n_enc_head : c.n_dec_head;
@@ -497,23 +385,23 @@ static Scratch carve(const ns_config& c, Bump& bp, size_t M, int S, bool no_spli
   }
   s.att_part_floats = nsp > 1 ? (size_t)nsp * (M * d + 2 * M * hmax) : 0;
   s.att_part = s.att_part_floats ? bp.f(s.att_part_floats) : nullptr;
-  s.tickets = (int*)bp.raw(TICKET_INTS * sizeof(int));
-  if (c.row_epilogue == 1) s.tickets = nullptr;  // "two_launch": take_tickets() then always answers "spent" (the block stays reserved)
-  s.tickets_used = 0;
+  s.tk.base = (int*)bp.raw(TICKET_INTS * sizeof(int));
+  if (c.row_epilogue == 1) s.tk.base = nullptr;  // "two_launch": tk.take() then always answers "spent" (the block stays reserved)
+  s.tk.used = 0;
   return s;
 }
 }  // namespace
 
 extern "C" size_t ns_op_ws_bytes(const ns_model* m, int B, int S) {
   if (!m || B <= 0 || S <= 0) return 256;
-  Bump bp(nullptr, 0);
+  Bump bp(nullptr);
   carve(m->cfg, bp, (size_t)B * S, S);
   return bp.off + 256;
 }
 static size_t phase1_packed_extra_bytes(const ns_config& c, int B, int L);
 extern "C" size_t ns_encoder_ws_bytes(const ns_model* m, int B, int L) {
   if (!m || B <= 0 || L <= 0) return 256;
-  Bump bp(nullptr, 0);
+  Bump bp(nullptr);
   bp.f((size_t)B * L * m->cfg.d_enc);  // encoder output (kept for phase 2)
   bp.raw((size_t)B * L * sizeof(int32_t));  // duration prefix sums (kept for phase 2)
   bp.f((size_t)B * L);                       // rounded durations (kept for phase 2: Gaussian length regulator)
@@ -540,20 +428,38 @@ static int check_ready(const ns_model* m) {
 static const RowMap* cur_rm(const Scratch& sc) { return sc.pk ? &sc.pk->rm : nullptr; }
 static int rows_of(const Scratch& sc, int B, int S) { return sc.pk ? sc.pk->Mp : B * S; }
 
-static int gemm(const Scratch& sc, const float* X, int ldx, const float* W, const float* bias, const float* resid, int ldr, float* Y, int ldy,
-                int M, int N, int Cin, int KW, int S, int act, hipStream_t st, const RowEpilogue* epi = nullptr, int epi_mode = EPI_NONE,
-                const unsigned short* Wb3 = nullptr, const LaunchTiming* tm = nullptr, const unsigned short* Wbf = nullptr) {
-  ConvGemm p;
-  memset(&p, 0, sizeof(p));
-  p.X = X; p.ldx = ldx; p.W = W; p.bias = bias; p.resid = resid; p.ldr = ldr; p.Y = Y; p.ldy = ldy;
-  p.M = M; p.N = N; p.Cin = Cin; p.KW = KW; p.pad = (KW - 1) / 2; p.S = S; p.act = act;
-  p.epi = epi ? epi_mode : EPI_NONE;
-  if (epi) p.e = *epi;
+// The rarely used extras of a gemm(): the row epilogue of a full-row / ticketed launch, the timing events of a profiled one
+struct GemmOpts {
+  const RowEpilogue* epi = nullptr; int epi_mode = EPI_NONE;
+  const LaunchTiming* tm = nullptr;
+  static GemmOpts row(const RowEpilogue& e, int mode) { GemmOpts o; o.epi = &e; o.epi_mode = mode; return o; }
+  static GemmOpts timed(const LaunchTiming* tm) { GemmOpts o; o.tm = tm; return o; }
+};
+
+// the contraction of weight w over the M rows of X ([M, w.cin], utterances of S rows), `+ resid` ([M, w.cout], nullable), into
+// Y [M, w.cout]; packed rows when the Scratch carries them
+static ConvGemm prepare(const ns_model* m, const Scratch& sc, const ConvW& w, const float* X, const float* resid, float* Y, int M, int S, int act) {
+  ConvGemm p = m->conv(w);
+  p.X = X; p.ldx = w.cin; p.resid = resid; p.ldr = w.cout; p.Y = Y; p.ldy = w.cout;
+  p.M = M; p.S = S; p.act = act;
   if (sc.pk) { p.rm = sc.pk->rm; p.e.row_b = sc.pk->rm.row_b; p.e.row_t = sc.pk->rm.row_t; }
+  return p;
+}
+
+// Y = act(conv_w(X)) + resid in the precision the weight's planes select
+static int gemm(const ns_model* m, const Scratch& sc, const ConvW& w, const float* X, const float* resid, float* Y, int M, int S, int act,
+                hipStream_t st, const GemmOpts& o = GemmOpts()) {
+  ConvGemm p = prepare(m, sc, w, X, resid, Y, M, S, act);
+  const LaunchTiming* tm = o.tm;
+  if (o.epi) {
+    p.epi = o.epi_mode;
+    p.e = *o.epi;
+    if (sc.pk) { p.e.row_b = sc.pk->rm.row_b; p.e.row_t = sc.pk->rm.row_t; }
+  }
   // opt-in bf16 mode: this weight has a rounded plane — the bf16 contraction at every launch size (no fp32 fallback)
-  if (Wbf) {
+  if (p.Wbf) {
     if (p.epi != EPI_NONE && p.epi != EPI_LN) return fail("gemm: the bf16 path has no predictor-tail epilogue");
-    p.Wbf = Wbf;
+    p.Wb3 = nullptr;
     p.e.ticket = nullptr; p.e.y_out = nullptr;
     if (tm && tm->start) NS_HIP(hipEventRecord(tm->start, st));
     NS_HIP(launch_conv_gemm_bf16(p, st));
@@ -561,59 +467,43 @@ static int gemm(const Scratch& sc, const float* X, int ldx, const float* W, cons
     return 0;
   }
   // opt-in bf16x3 planes exist for this weight AND the launch is large enough for the 128-row tiles: split-bf16 matrix cores
-  if (Wb3 && conv_gemm_b3_ok(M, N, Cin, KW, p.epi)) {
-    p.Wb3 = Wb3;
+  if (p.Wb3 && conv_gemm_b3_ok(M, p.N, p.Cin, p.KW, p.epi)) {
     if (tm && tm->start) NS_HIP(hipEventRecord(tm->start, st));  // (the experiment mode keeps marker events around its launch)
     NS_HIP(launch_conv_gemm_b3(p, st));
     if (tm && tm->stop) NS_HIP(hipEventRecord(tm->stop, st));
     return 0;
   }
+  p.Wb3 = nullptr;
   NS_HIP(launch_conv_gemm(p, st, tm));
   return 0;
 }
 
-// A GEMM whose N columns are one whole activation row can run the row's LayerNorm in its epilogue (kernels.h
-// RowEpilogue).  The full-row tile is at least 32 rows tall (48 / 80 / 112 between the steps: gemm_conv.hip conv_gemm_row_tile), so it
-// is taken once the launch has about a workgroup per CU;
-// below that the many-small-tiles + split-K ladder followed by the row kernel is faster (tools/lab/gemm_lab_ln.hip:
-// M=16160 K=1024 93 -> 85 us, K=256 39.5 -> 31 us; M=2048 K=1024 21.6 -> 43 us).
-static bool fuse_row_epilogue(int M, int N, int Cin) {
-  return conv_gemm_row_epilogue_ok(M, N, Cin) && (M + 31) / 32 >= 200;
-}
-
-// Y = mask(LayerNorm(act(conv(X)) + resid)) in ONE launch: the full-row tile when the launch is large enough, else the
-// small-grid ladder with the ticketed row epilogue (raw rows through tmp, the last workgroup of a row block normalises it).
-// Two launches (GEMM -> tmp -> k_layernorm) only in the opt-in bf16x3 mode for widths its LayerNorm tile does not cover,
-// or when the phase's ticket block is spent.
-static int gemm_ln(const float* X, int ldx, const float* W, const float* bias, const float* resid, float* tmp, float* Y,
-                   int M, int N, int Cin, int KW, int S, int act, const float* g, const float* b, const long long* lens,
-                   Scratch& sc, hipStream_t st, const unsigned short* Wb3 = nullptr, const unsigned short* Wbf = nullptr) {
+// Y = mask(LayerNorm(act(conv_w(X)) + resid)), g / b the LayerNorm's weights.  Exact fp32: the ladder of host_core.h gemm_ln_fp32
+// (full-row tile, ticketed epilogue, or GEMM -> tmp -> k_layernorm).  The opt-in modes run their own kernels where those cover the
+// launch and fall back to that ladder where they do not.
+static int gemm_ln(const ns_model* m, Scratch& sc, const ConvW& w, const float* X, const float* resid, float* tmp, float* Y, int M, int S,
+                   int act, const float* g, const float* b, const long long* lens, hipStream_t st) {
   RowEpilogue e;
   memset(&e, 0, sizeof(e));
   e.ln_g = g; e.ln_b = b; e.lens = lens;
-  if (Wbf) {  // bf16 mode: the full-row tile on large launches, else the plain bf16 GEMM and k_layernorm (same bits either way)
-    if (conv_gemm_bf16_ok(M, N, Cin, KW, EPI_LN))
-      return gemm(sc, X, ldx, W, bias, resid, N, Y, N, M, N, Cin, KW, S, act, st, &e, EPI_LN, nullptr, nullptr, Wbf);
-    NS_TRY(gemm(sc, X, ldx, W, bias, resid, N, tmp, N, M, N, Cin, KW, S, act, st, nullptr, EPI_NONE, nullptr, nullptr, Wbf));
+  const int N = w.cout;
+  if (w.bf != NO_PLANE) {  // bf16 mode: the full-row tile on large launches, else the plain bf16 GEMM and k_layernorm (same bits either way)
+    if (conv_gemm_bf16_ok(M, N, w.cin, w.kw, EPI_LN)) return gemm(m, sc, w, X, resid, Y, M, S, act, st, GemmOpts::row(e, EPI_LN));
+    NS_TRY(gemm(m, sc, w, X, resid, tmp, M, S, act, st));
     NS_HIP(launch_layernorm(tmp, g, b, Y, M, N, S, lens, st, cur_rm(sc)));
     return 0;
   }
-  if (Wb3 && !conv_gemm_b3_ok(M, N, Cin, KW, EPI_LN) && conv_gemm_b3_ok(M, N, Cin, KW, EPI_NONE)) {
-    NS_TRY(gemm(sc, X, ldx, W, bias, resid, N, tmp, N, M, N, Cin, KW, S, act, st, nullptr, EPI_NONE, Wb3));
-    NS_HIP(launch_layernorm(tmp, g, b, Y, M, N, S, lens, st, cur_rm(sc)));
-    return 0;
+  if (w.b3 != NO_PLANE) {  // bf16x3 mode: two launches for widths its LayerNorm tile does not cover, its full-row tile where fp32 takes one
+    const bool ln_ok = conv_gemm_b3_ok(M, N, w.cin, w.kw, EPI_LN);
+    if (!ln_ok && conv_gemm_b3_ok(M, N, w.cin, w.kw, EPI_NONE)) {
+      NS_TRY(gemm(m, sc, w, X, resid, tmp, M, S, act, st));
+      NS_HIP(launch_layernorm(tmp, g, b, Y, M, N, S, lens, st, cur_rm(sc)));
+      return 0;
+    }
+    if (ln_ok && fuse_row_epilogue(M, N, w.cin)) return gemm(m, sc, w, X, resid, Y, M, S, act, st, GemmOpts::row(e, EPI_LN));
   }
-  // (64x64 tiles with the ticketed epilogue in place of the full-row tile when its steps of 256 tiles fit the row count badly
-  //  were measured in round 4 and lose: at 572 workgroups the last arrivers' row work costs +12 us for a LayerNorm and +25 us
-  //  for a predictor tail, more than the finer steps save — B = 9: conv+LN 57 vs 56 us, conv+tail 80-86 vs 62, w_2 70.7 vs 70)
-  if (fuse_row_epilogue(M, N, Cin)) return gemm(sc, X, ldx, W, bias, resid, N, Y, N, M, N, Cin, KW, S, act, st, &e, EPI_LN, Wb3);
-  if (conv_gemm_ticket_ok(M, N, Cin) && (e.ticket = sc.take_tickets(conv_gemm_ticket_ints(M))) != nullptr) {
-    e.y_out = Y;
-    return gemm(sc, X, ldx, W, bias, resid, N, tmp, N, M, N, Cin, KW, S, act, st, &e, EPI_LN);
-  }
-  NS_TRY(gemm(sc, X, ldx, W, bias, resid, N, tmp, N, M, N, Cin, KW, S, act, st));
-  NS_HIP(launch_layernorm(tmp, g, b, Y, M, N, S, lens, st, cur_rm(sc)));
-  return 0;
+  if (sc.pk) { e.row_b = sc.pk->rm.row_b; e.row_t = sc.pk->rm.row_t; }
+  return gemm_ln_fp32(prepare(m, sc, w.fp32(), X, resid, nullptr, M, S, act), e, tmp, Y, sc.tk, st, cur_rm(sc));
 }
 
 // Timing of one launch group inside the real forward; a no-op unless ns_profile_enable(1) and the forward is inside its
@@ -649,20 +539,17 @@ struct ProfScope {
 static int mha(ns_model* m, const LayerW& L, int d, int H, const float* x, const long long* lens, int B, int S,
                float* out, bool mask_rows, Scratch& sc, hipStream_t st) {
   const int M = rows_of(sc, B, S);
-  auto b3 = [&](size_t off) { return off != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(off)) : nullptr; };
-  const bool bf = L.qkv_bf != NO_B3;  // bf16 mode, decoder layer: the attention's contractions on bf16 too
-  NS_TRY(gemm(sc, x, d, m->P(L.qkv_w), m->P(L.qkv_b), nullptr, 0, sc.qkv, 3 * d, M, 3 * d, d, 1, S, ACT_NONE, st, nullptr, EPI_NONE, b3(L.qkv_b3),
-              nullptr, b3(L.qkv_bf)));
+  const bool bf = L.qkv.bf != NO_PLANE;  // bf16 mode, decoder layer: the attention's contractions on bf16 too
+  NS_TRY(gemm(m, sc, L.qkv, x, nullptr, sc.qkv, M, S, ACT_NONE, st));
   {
     ProfScope ps(m, 1, 4.0 * (double)M * (double)S * (double)d);
     NS_TRY(ps.begin());
     NS_HIP(launch_attention(sc.qkv, lens, B, S, H, d / H, sc.att, sc.att_part, sc.att_part_floats,
-                            (sc.att_part && attention_uses_tickets(B, S, H)) ? sc.take_tickets(attention_ticket_ints(B, S, H)) : nullptr, st, cur_rm(sc),
+                            (sc.att_part && attention_uses_tickets(B, S, H)) ? sc.tk.take(attention_ticket_ints(B, S, H)) : nullptr, st, cur_rm(sc),
                             ps.timing(), bf));
     ps.end();
   }
-  return gemm_ln(sc.att, d, m->P(L.fc_w), m->P(L.fc_b), x, sc.t1, out, M, d, d, 1, S, ACT_NONE, m->P(L.ln1_g), m->P(L.ln1_b),
-                 mask_rows ? lens : nullptr, sc, st, b3(L.fc_b3), b3(L.fc_bf));
+  return gemm_ln(m, sc, L.fc, sc.att, x, sc.t1, out, M, S, ACT_NONE, m->P(L.ln1_g), m->P(L.ln1_b), mask_rows ? lens : nullptr, st);
 }
 
 // PositionwiseFeedForward.forward (transformer/SubLayers.py:87-95)
@@ -673,15 +560,10 @@ static int ffn(ns_model* m, const LayerW& L, int d, const float* x, const long l
   {
     ProfScope ps(m, 0, 2.0 * (double)M * (double)c.ffn_k1 * (double)d * (double)c.d_inner);
     NS_TRY(ps.begin());
-    NS_TRY(gemm(sc, x, d, m->P(L.w1), m->P(L.w1_b), nullptr, 0, sc.hid, c.d_inner, M, c.d_inner, d, c.ffn_k1, S, ACT_RELU, st, nullptr, EPI_NONE,
-                L.w1_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w1_b3)) : nullptr, ps.timing(),
-                L.w1_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w1_bf)) : nullptr));
+    NS_TRY(gemm(m, sc, L.w1, x, nullptr, sc.hid, M, S, ACT_RELU, st, GemmOpts::timed(ps.timing())));
     ps.end();
   }
-  return gemm_ln(sc.hid, c.d_inner, m->P(L.w2), m->P(L.w2_b), x, sc.t1, out, M, d, c.d_inner, c.ffn_k2, S, ACT_NONE, m->P(L.ln2_g),
-                 m->P(L.ln2_b), mask_rows ? lens : nullptr, sc, st,
-                 L.w2_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w2_b3)) : nullptr,
-                 L.w2_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(L.w2_bf)) : nullptr);
+  return gemm_ln(m, sc, L.w2, sc.hid, x, sc.t1, out, M, S, ACT_NONE, m->P(L.ln2_g), m->P(L.ln2_b), mask_rows ? lens : nullptr, st);
 }
 
 // FFTBlock.forward (transformer/Layers.py:39-48): both masked_fill's are fused into the LayerNorm kernels
@@ -711,24 +593,22 @@ static int predictor(const ns_model* m, const PredW& w, const float* x, const lo
                      float* pred, const float* bins, const float* emb, const float* pos, float* x_out, Scratch& sc,
                      hipStream_t st) {
   const ns_config& c = m->cfg;
-  const int M = rows_of(sc, B, S), F = c.vp_filter;
+  const int M = rows_of(sc, B, S), F = c.vp_filter, D = w.c1.cin;
   // conv1d_1 -> relu -> layer_norm_1 (no mask between the layers: model/modules.py:245-274)
-  NS_TRY(gemm_ln(x, w.cin, m->P(w.c1), m->P(w.c1_b), nullptr, sc.vp1, sc.vp2, M, F, w.cin, c.vp_kernel, S, ACT_RELU, m->P(w.ln1_g),
-                 m->P(w.ln1_b), nullptr, sc, st));
+  NS_TRY(gemm_ln(m, sc, w.c1, x, nullptr, sc.vp1, sc.vp2, M, S, ACT_RELU, m->P(w.ln1_g), m->P(w.ln1_b), nullptr, st));
   // conv1d_2 -> relu -> layer_norm_2 -> linear -> mask (-> bucketize + embedding add): the whole tail rides on conv1d_2's
   // row epilogue — the full-row tile when the launch is large, the ticketed form on small grids
   RowEpilogue e;
   memset(&e, 0, sizeof(e));
   e.ln_g = m->P(w.ln2_g); e.ln_b = m->P(w.ln2_b); e.lens = lens; e.wlin = m->P(w.lin_w); e.blin = m->P(w.lin_b); e.pred = pred;
   e.control = control; e.target = target; e.bins = bins; e.n_edges = c.n_bins - 1; e.emb = emb; e.x_in = x; e.pos = pos; e.x_out = x_out;
-  e.D = w.cin;
-  if (fuse_row_epilogue(M, F, F))
-    return gemm(sc, sc.vp2, F, m->P(w.c2), m->P(w.c2_b), nullptr, 0, nullptr, F, M, F, F, c.vp_kernel, S, ACT_RELU, st, &e, EPI_LN_PRED);
-  if (conv_gemm_ticket_ok(M, F, F) && (e.ticket = sc.take_tickets(conv_gemm_ticket_ints(M))) != nullptr)
-    return gemm(sc, sc.vp2, F, m->P(w.c2), m->P(w.c2_b), nullptr, 0, sc.vp1, F, M, F, F, c.vp_kernel, S, ACT_RELU, st, &e, EPI_LN_PRED);
-  NS_TRY(gemm(sc, sc.vp2, F, m->P(w.c2), m->P(w.c2_b), nullptr, 0, sc.vp1, F, M, F, F, c.vp_kernel, S, ACT_RELU, st));
+  e.D = D;
+  if (fuse_row_epilogue(M, F, F)) return gemm(m, sc, w.c2, sc.vp2, nullptr, nullptr, M, S, ACT_RELU, st, GemmOpts::row(e, EPI_LN_PRED));
+  if (conv_gemm_ticket_ok(M, F, F) && (e.ticket = sc.tk.take(conv_gemm_ticket_ints(M))) != nullptr)
+    return gemm(m, sc, w.c2, sc.vp2, nullptr, sc.vp1, M, S, ACT_RELU, st, GemmOpts::row(e, EPI_LN_PRED));
+  NS_TRY(gemm(m, sc, w.c2, sc.vp2, nullptr, sc.vp1, M, S, ACT_RELU, st));
   NS_HIP(launch_ln_linear_embed(sc.vp1, m->P(w.ln2_g), m->P(w.ln2_b), m->P(w.lin_w), m->P(w.lin_b), pred, M, F, S, lens,
-                                control, target, bins, c.n_bins, emb, x, pos, x_out, w.cin, st, cur_rm(sc)));
+                                control, target, bins, c.n_bins, emb, x, pos, x_out, D, st, cur_rm(sc)));
   return 0;
 }
 
@@ -739,21 +619,16 @@ static int postnet(ns_model* m, const float* mel, int B, int T, const float* res
   float* ping = sc.hid;
   float* pong = sc.hid + (size_t)M * c.postnet_dim;
   const float* cur = mel;
-  int ld = c.n_mel;
   for (size_t i = 0; i < m->post.size(); ++i) {
-    const PostW& w = m->post[i];
+    const ConvW& w = m->post[i];
     const bool last = i + 1 == m->post.size();
     float* dst = last ? out : ((i & 1) ? pong : ping);
     const bool mid = w.cin == c.postnet_dim && w.cout == c.postnet_dim;
     ProfScope ps(m, 2, 2.0 * (double)M * (double)c.postnet_k * (double)w.cin * (double)w.cout);
     if (mid) NS_TRY(ps.begin());
-    NS_TRY(gemm(sc, cur, ld, m->P(w.w), m->P(w.b), last ? resid : nullptr, c.n_mel, dst, w.cout, M, w.cout, w.cin, c.postnet_k, T,
-                last ? ACT_NONE : ACT_TANH, st, nullptr, EPI_NONE,
-                w.w_b3 != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(w.w_b3)) : nullptr, mid ? ps.timing() : nullptr,
-                w.w_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(w.w_bf)) : nullptr));
+    NS_TRY(gemm(m, sc, w, cur, last ? resid : nullptr, dst, M, T, last ? ACT_NONE : ACT_TANH, st, GemmOpts::timed(mid ? ps.timing() : nullptr)));
     if (mid) ps.end();
     cur = dst;
-    ld = w.cout;
   }
   return 0;
 }
@@ -765,7 +640,7 @@ static int postnet(ns_model* m, const float* mel, int B, int T, const float* res
 static int postnet_constants(ns_model* m, hipStream_t st) {
   const ns_config& c = m->cfg;
   float* in = m->arena + m->pn_in;
-  NS_HIP(launch_broadcast_row(m->P(m->mel_b), in, PN_CONST_ROWS, c.n_mel, st));
+  NS_HIP(launch_broadcast_row(m->P(m->mel_linear.b), in, PN_CONST_ROWS, c.n_mel, st));
   Scratch sc;
   memset(&sc, 0, sizeof(sc));
   sc.hid = m->arena + m->pn_hid;
@@ -780,8 +655,8 @@ static int encoder(ns_model* m, const long long* texts, const long long* lens, i
   NS_TRY(position_rows(m, m->enc_pos, L, d, sc, &pos, st));
   float* cur = m->enc.empty() ? out : sc.xa;
   // (+ zeroes the phase's tickets)
-  if (sc.pk) NS_HIP(launch_embed_pos_packed(texts, m->P(m->emb), pos, cur, sc.pk->rm, B, M, L, d, c.n_vocab, sc.tickets, TICKET_INTS, st));
-  else NS_HIP(launch_embed_pos(texts, m->P(m->emb), pos, cur, M, L, d, c.n_vocab, sc.tickets, TICKET_INTS, st));
+  if (sc.pk) NS_HIP(launch_embed_pos_packed(texts, m->P(m->emb), pos, cur, sc.pk->rm, B, M, L, d, c.n_vocab, sc.tk.base, TICKET_INTS, st));
+  else NS_HIP(launch_embed_pos(texts, m->P(m->emb), pos, cur, M, L, d, c.n_vocab, sc.tk.base, TICKET_INTS, st));
   for (size_t i = 0; i < m->enc.size(); ++i) {
     float* dst = (i + 1 == m->enc.size()) ? out : (cur == sc.xa ? sc.xb : sc.xa);
     NS_TRY(fft_block(m, m->enc[i], d, c.n_enc_head, cur, lens, B, L, dst, sc, st));
@@ -818,7 +693,7 @@ static size_t phase1_packed_rows(const int64_t* lens_host, int B, int L) {
   return mp;
 }
 static size_t phase1_packed_extra_bytes(const ns_config& c, int B, int L) {  // plan + packed encoder output + packed log-durations
-  Bump bp(nullptr, 0);
+  Bump bp(nullptr);
   const size_t M = (size_t)B * L;
   bp.raw(pack_plan_ints(B, M) * sizeof(int));
   bp.f(M * c.d_enc); bp.f(M);
@@ -850,7 +725,7 @@ static int forward_durations(ns_model* m, const int64_t* texts, const int64_t* s
   const ns_config& c = m->cfg;
   if (!c.pitch_frame_level && !p_pred) return fail("ns_forward_durations: phoneme_level pitch needs a p_pred [B,L] output");
   if (!c.energy_frame_level && !e_pred) return fail("ns_forward_durations: phoneme_level energy needs an e_pred [B,L] output");
-  Bump bp(ws_enc, ws_bytes);
+  Bump bp(ws_enc);
   float* enc_out = bp.f((size_t)B * L * c.d_enc);
   int32_t* cum = (int32_t*)bp.raw((size_t)B * L * sizeof(int32_t));
   float* dur_keep = bp.f((size_t)B * L);
@@ -1002,7 +877,7 @@ static size_t packed_rows(const int64_t* lens_host, int B, int T) {
   return mp;
 }
 static size_t packed_extra_bytes(const ns_config& c, int B, int T) {  // on top of carve(): plan, packed outputs, PostNet constants
-  Bump bp(nullptr, 0);
+  Bump bp(nullptr);
   const size_t M = (size_t)B * T;
   bp.raw(pack_plan_ints(B, M) * sizeof(int));
   bp.f(M * c.n_mel); bp.f(M * c.n_mel); bp.f(M); bp.f(M); bp.f(M); bp.f(M);
@@ -1018,7 +893,7 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
   if (!status) return fail("ns_forward_mel: status [B] is required (a T smaller than an utterance's length must not go unnoticed)");
   if (T < 0) return fail("ns_forward_mel: negative T");
   if (T == 0) {  // all durations zero: [B,0,*] outputs; only the status words (an utterance with frames would be cut off entirely)
-    Bump be0(const_cast<void*>(ws_enc), (size_t)-1);
+    Bump be0(const_cast<void*>(ws_enc));
     be0.f((size_t)B * L * m->cfg.d_enc);
     const int32_t* cum0 = (const int32_t*)be0.raw((size_t)B * L * sizeof(int32_t));
     NS_HIP(launch_length_regulate(nullptr, cum0, B, L, m->cfg.d_enc, 0, nullptr, nullptr, (const long long*)mel_lens, status, nullptr, 0, (hipStream_t)stream));
@@ -1027,7 +902,7 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
   if (ws_bytes < ns_decoder_ws_bytes(m, B, L, T)) return fail("ns_forward_mel: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const ns_config& c = m->cfg;
-  Bump be(const_cast<void*>(ws_enc), (size_t)-1);
+  Bump be(const_cast<void*>(ws_enc));
   const float* enc_out = be.f((size_t)B * L * c.d_enc);
   const int32_t* cum = (const int32_t*)be.raw((size_t)B * L * sizeof(int32_t));
   const float* dur_keep = be.f((size_t)B * L);
@@ -1047,7 +922,7 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
   const size_t Mrows = packed ? Mp : (size_t)B * T;
   const int M = (int)Mrows;
   m->last_rows = (long long)Mrows;
-  Bump bp(ws_dec, ws_bytes);
+  Bump bp(ws_dec);
   Scratch sc = carve(c, bp, Mrows, T, packed);
   if (packed) {  // split-key partials for a work list of few workgroups (attention.hip packed launch): whatever the workspace still holds
     size_t base = 0;
@@ -1078,9 +953,9 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
     if (c.length_regulator == 1) {  // extension: GaussianUpsampling in the LengthRegulator's place, on the packed rows
       if ((size_t)B * (L + 1) > (size_t)M * c.vp_filter) return fail("ns_forward_mel: workspace too small for the Gaussian centres");
       NS_HIP(launch_pack_plan(lens, B, T, c.n_dec_head, M, plan, &pk.rm, st));
-      NS_HIP(launch_gaussian_upsampling(enc_out, dur_keep, B, L, c.d_enc, T, T, sc.xa, sc.vp2, nullptr, lens, status, sc.tickets, TICKET_INTS, st, &pk.rm));
+      NS_HIP(launch_gaussian_upsampling(enc_out, dur_keep, B, L, c.d_enc, T, T, sc.xa, sc.vp2, nullptr, lens, status, sc.tk.base, TICKET_INTS, st, &pk.rm));
     } else {
-      NS_HIP(launch_length_regulate_packed(enc_out, cum, B, L, c.d_enc, T, M, c.n_dec_head, sc.xa, lens, status, sc.tickets, TICKET_INTS, plan, &pk.rm, st));
+      NS_HIP(launch_length_regulate_packed(enc_out, cum, B, L, c.d_enc, T, M, c.n_dec_head, sc.xa, lens, status, sc.tk.base, TICKET_INTS, plan, &pk.rm, st));
     }
     for (int b = 0; b < B; ++b) {  // the attention work list's length, from the same lengths the device plan reads
       long long l = (lens_host[b] < 0 ? 0 : lens_host[b]) + PACK_GUARD;
@@ -1095,9 +970,9 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
     // extension: GaussianUpsampling (model/modules.py:166-192) in the LengthRegulator's place;
     // mel_len = sum of the rounded durations, frames past an utterance's own length are zero like pad()'s
     if ((size_t)B * (L + 1) > (size_t)M * c.vp_filter) return fail("ns_forward_mel: workspace too small for the Gaussian centres");
-    NS_HIP(launch_gaussian_upsampling(enc_out, dur_keep, B, L, c.d_enc, T, T, sc.xa, sc.vp2, nullptr, lens, status, sc.tickets, TICKET_INTS, st));
+    NS_HIP(launch_gaussian_upsampling(enc_out, dur_keep, B, L, c.d_enc, T, T, sc.xa, sc.vp2, nullptr, lens, status, sc.tk.base, TICKET_INTS, st));
   } else {
-    NS_HIP(launch_length_regulate(enc_out, cum, B, L, c.d_enc, T, sc.xa, mel_mask, lens, status, sc.tickets, TICKET_INTS, st));  // + mel mask, status, ticket zeroing
+    NS_HIP(launch_length_regulate(enc_out, cum, B, L, c.d_enc, T, sc.xa, mel_mask, lens, status, sc.tk.base, TICKET_INTS, st));  // + mel mask, status, ticket zeroing
   }
   sc.pk = packed ? &pk : nullptr;
   float* const mel_dst = packed ? mel_p : mel;
@@ -1129,13 +1004,12 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
   m->prof_active = m->prof != 0;  // time only phase 2's launches: one shape per slot (the encoder runs the same kernels at B*L rows)
   int rc = decoder_stack(m, cur, lens, B, T, sc.att, sc, st);
   // note: decoder_stack's last layer writes into sc.att only after its own attention output was consumed
-  if (!rc) rc = gemm(sc, sc.att, d, m->P(m->mel_w), m->P(m->mel_b), nullptr, 0, mel_dst, c.n_mel, M, c.n_mel, d, 1, T, ACT_NONE, st, nullptr,
-                     EPI_NONE, nullptr, nullptr, m->mel_bf != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(m->mel_bf)) : nullptr);
+  if (!rc) rc = gemm(m, sc, m->mel_linear, sc.att, nullptr, mel_dst, M, T, ACT_NONE, st);
   if (!rc) rc = postnet(m, mel_dst, B, T, mel_dst, post_dst, sc, st);
   m->prof_active = false;
   if (!rc && packed) {
     hipError_t e = launch_unpack_outputs(pk.rm, B, T, c.n_mel, lens, mel_p, post_p, c.pitch_frame_level ? pp_p : nullptr,
-                                         c.energy_frame_level ? ep_p : nullptr, m->P(m->mel_b), m->P(m->pn_const) + (size_t)21 * c.n_mel, mel, postnet_mel,
+                                         c.energy_frame_level ? ep_p : nullptr, m->P(m->mel_linear.b), m->P(m->pn_const) + (size_t)21 * c.n_mel, mel, postnet_mel,
                                          c.pitch_frame_level ? p_pred : nullptr, c.energy_frame_level ? e_pred : nullptr, mel_mask, st);
     if (e != hipSuccess) rc = fail(std::string("launch_unpack_outputs: ") + hipGetErrorString(e));
   }
@@ -1188,9 +1062,9 @@ static int find_layer(ns_model* m, const char* prefix_c, const LayerW** L, int* 
   if ((B_) <= 0 || (S_) <= 0) return fail("empty input");                             \
   if (ws_bytes < ns_op_ws_bytes(m, (B_), (S_))) return fail("workspace too small");   \
   hipStream_t st = (hipStream_t)stream;                                               \
-  Bump bp(ws, ws_bytes);                                                              \
+  Bump bp(ws);                                                                        \
   Scratch sc = carve(m->cfg, bp, (size_t)(B_) * (S_), (S_));                          \
-  if (sc.tickets) NS_HIP(hipMemsetAsync(sc.tickets, 0, TICKET_INTS * sizeof(int), st)); /* a forward's first kernel does this itself */
+  if (sc.tk.base) NS_HIP(hipMemsetAsync(sc.tk.base, 0, TICKET_INTS * sizeof(int), st)); /* a forward's first kernel does this itself */
 
 extern "C" int ns_op_mask_from_lengths(const int64_t* lens, int B, int max_len, uint8_t* mask, void* stream) {
   NS_HIP(launch_mask_from_lengths((const long long*)lens, B, max_len, mask, (hipStream_t)stream));
@@ -1340,13 +1214,43 @@ extern "C" int ns_op_mel_decoder(ns_model* m, const float* x, const int64_t* len
   NS_HIP(launch_add_pos(x, pos, sc.xa, B * T, T, m->cfg.d_dec, st));
   return decoder_stack(m, sc.xa, (const long long*)lens, B, T, out, sc, st);
 }
-extern "C" int ns_op_mel_linear(ns_model* m, const float* x, int B, int T, float* out, void* stream) {
+// name -> (weight, the activation its layer applies); the input width is the weight's cin
+static int find_conv(ns_model* m, const std::string& name, const ConvW** w, int* act) {
+  *act = ACT_NONE;
+  if (name == "mel_linear") { *w = &m->mel_linear; return 0; }
+  if (starts_with(name, "postnet.convolutions.")) {
+    const char* num = name.c_str() + strlen("postnet.convolutions.");
+    char* end = nullptr;
+    const long i = strtol(num, &end, 10);
+    if (end == num || *end != 0 || i < 0 || i >= (long)m->post.size()) return fail("ns_op_gemm: unknown contraction '" + name + "'");
+    *w = &m->post[i];
+    if ((size_t)i + 1 != m->post.size()) *act = ACT_TANH;
+    return 0;
+  }
+  static const char* kSuffix[4] = {".slf_attn.qkv", ".slf_attn.fc", ".pos_ffn.w_1", ".pos_ffn.w_2"};
+  for (int which = 0; which < 4; ++which) {
+    if (!ends_with(name, kSuffix[which])) continue;
+    const LayerW* L; int d, H;
+    NS_TRY(find_layer(m, name.c_str(), &L, &d, &H, kSuffix[which]));
+    const ConvW* of_layer[4] = {&L->qkv, &L->fc, &L->w1, &L->w2};
+    *w = of_layer[which];
+    if (which == 2) *act = ACT_RELU;
+    return 0;
+  }
+  return fail("ns_op_gemm: unknown contraction '" + name + "'");
+}
+// One named contraction alone on the dense [B, S] grid (a plain GEMM: no temporaries, no packed context): bias and the layer's
+// activation, no residual, no LayerNorm.  planes = false: on the exact-fp32 kernels whatever the model's precision mode.
+static int named_gemm(ns_model* m, const std::string& name, bool planes, const float* x, int B, int S, float* out, void* stream) {
   NS_TRY(check_ready(m));
-  const ns_config& c = m->cfg;
+  const ConvW* w; int act;
+  NS_TRY(find_conv(m, name, &w, &act));
   Scratch sc;
-  memset(&sc, 0, sizeof(sc));  // (a plain GEMM on the dense grid: no temporaries, no packed context)
-  return gemm(sc, x, c.d_dec, m->P(m->mel_w), m->P(m->mel_b), nullptr, 0, out, c.n_mel, B * T, c.n_mel, c.d_dec, 1, T, ACT_NONE,
-              (hipStream_t)stream);
+  memset(&sc, 0, sizeof(sc));
+  return gemm(m, sc, planes ? *w : w->fp32(), x, nullptr, out, B * S, S, act, (hipStream_t)stream);
+}
+extern "C" int ns_op_mel_linear(ns_model* m, const float* x, int B, int T, float* out, void* stream) {
+  return named_gemm(m, "mel_linear", false, x, B, T, out, stream);
 }
 extern "C" int ns_op_postnet(ns_model* m, const float* mel, int B, int T, float* out, void* ws, size_t ws_bytes, void* stream) {
   NS_OP_PROLOGUE(B, T);
@@ -1373,50 +1277,12 @@ extern "C" int ns_op_attention_core(const float* qkv, const int64_t* lens, int B
   return ns_op_attention_core_mode(qkv, lens, B, S, H, dk, out, scratch, scratch_bytes, stream, 0);
 }
 // One named contraction alone, in the model's precision mode, through the forward's own gemm() dispatch (a bf16 model's decoder /
-// mel_linear / PostNet weight takes launch_conv_gemm_bf16 with that weight's plane): bias and the layer's activation, no residual,
-// no LayerNorm, dense [B, S] grid.  For tests that bound one contraction elementwise.
-extern "C" int ns_op_gemm(ns_model* m, const char* name_c, const float* x, int B, int S, float* out, void* stream) {
+// mel_linear / PostNet weight takes launch_conv_gemm_bf16 with that weight's plane).  For tests that bound one contraction elementwise.
+extern "C" int ns_op_gemm(ns_model* m, const char* name, const float* x, int B, int S, float* out, void* stream) {
   NS_TRY(check_ready(m));
-  if (!name_c || !x || !out) return fail("ns_op_gemm: null argument");
+  if (!name || !x || !out) return fail("ns_op_gemm: null argument");
   if (B <= 0 || S <= 0) return fail("ns_op_gemm: empty input");
-  const ns_config& c = m->cfg;
-  const std::string name(name_c);
-  auto plane = [&](size_t off) { return off != NO_B3 ? reinterpret_cast<const unsigned short*>(m->P(off)) : nullptr; };
-  Scratch sc;
-  memset(&sc, 0, sizeof(sc));  // (a plain GEMM on the dense grid: no temporaries, no packed context)
-  hipStream_t st = (hipStream_t)stream;
-  const int M = B * S;
-  if (name == "mel_linear")
-    return gemm(sc, x, c.d_dec, m->P(m->mel_w), m->P(m->mel_b), nullptr, 0, out, c.n_mel, M, c.n_mel, c.d_dec, 1, S, ACT_NONE, st, nullptr,
-                EPI_NONE, nullptr, nullptr, plane(m->mel_bf));
-  if (starts_with(name, "postnet.convolutions.")) {
-    const char* num = name_c + strlen("postnet.convolutions.");
-    char* end = nullptr;
-    const long i = strtol(num, &end, 10);
-    if (end == num || *end != 0 || i < 0 || i >= (long)m->post.size()) return fail("ns_op_gemm: unknown contraction '" + name + "'");
-    const PostW& w = m->post[i];
-    const bool last = (size_t)i + 1 == m->post.size();
-    return gemm(sc, x, w.cin, m->P(w.w), m->P(w.b), nullptr, 0, out, w.cout, M, w.cout, w.cin, c.postnet_k, S, last ? ACT_NONE : ACT_TANH, st,
-                nullptr, EPI_NONE, plane(w.w_b3), nullptr, plane(w.w_bf));
-  }
-  static const char* kSuffix[4] = {".slf_attn.qkv", ".slf_attn.fc", ".pos_ffn.w_1", ".pos_ffn.w_2"};
-  for (int which = 0; which < 4; ++which) {
-    if (!ends_with(name, kSuffix[which])) continue;
-    const LayerW* L; int d, H;
-    NS_TRY(find_layer(m, name_c, &L, &d, &H, kSuffix[which]));
-    if (which == 0)
-      return gemm(sc, x, d, m->P(L->qkv_w), m->P(L->qkv_b), nullptr, 0, out, 3 * d, M, 3 * d, d, 1, S, ACT_NONE, st, nullptr, EPI_NONE,
-                  plane(L->qkv_b3), nullptr, plane(L->qkv_bf));
-    if (which == 1)
-      return gemm(sc, x, d, m->P(L->fc_w), m->P(L->fc_b), nullptr, 0, out, d, M, d, d, 1, S, ACT_NONE, st, nullptr, EPI_NONE,
-                  plane(L->fc_b3), nullptr, plane(L->fc_bf));
-    if (which == 2)
-      return gemm(sc, x, d, m->P(L->w1), m->P(L->w1_b), nullptr, 0, out, c.d_inner, M, c.d_inner, d, c.ffn_k1, S, ACT_RELU, st, nullptr,
-                  EPI_NONE, plane(L->w1_b3), nullptr, plane(L->w1_bf));
-    return gemm(sc, x, c.d_inner, m->P(L->w2), m->P(L->w2_b), nullptr, 0, out, d, M, d, c.d_inner, c.ffn_k2, S, ACT_NONE, st, nullptr,
-                EPI_NONE, plane(L->w2_b3), nullptr, plane(L->w2_bf));
-  }
-  return fail("ns_op_gemm: unknown contraction '" + name + "'");
+  return named_gemm(m, name, true, x, B, S, out, stream);
 }
 // Scratch ns_op_attention_core[_mode] needs to split its keys exactly as a model's own attention of this shape does: the
 // partials carve() reserves (attention_split ranges) plus the zeroed ticket block the op takes from the end of its scratch;
@@ -1439,12 +1305,5 @@ extern "C" int ns_plan_gemm_bf16(int M, int N, int32_t* bm, int32_t* bn) {
   return 0;
 }
 extern "C" int ns_op_ffn_conv1(ns_model* m, const char* prefix, const float* x, int B, int S, float* hidden, void* stream) {
-  NS_TRY(check_ready(m));
-  const LayerW* L; int d, H;
-  NS_TRY(find_layer(m, prefix, &L, &d, &H, ".pos_ffn"));
-  const ns_config& c = m->cfg;
-  Scratch sc;
-  memset(&sc, 0, sizeof(sc));
-  return gemm(sc, x, d, m->P(L->w1), m->P(L->w1_b), nullptr, 0, hidden, c.d_inner, B * S, c.d_inner, d, c.ffn_k1, S, ACT_RELU,
-              (hipStream_t)stream);
+  return named_gemm(m, std::string(prefix ? prefix : "") + ".w_1", false, x, B, S, hidden, stream);
 }

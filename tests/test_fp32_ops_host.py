@@ -220,7 +220,7 @@ def _lens(Bn, Sn):
 
 
 # LayerNorm forms: (op, config, B, S, form).  op "mha" = ops.multi_head_attention (fc + LayerNorm, K = d), "ffn" =
-# ops.positionwise_ffn (w_2 + LayerNorm, K = 1024).  Which form a model takes is api.hip's rule (fuse_row_epilogue /
+# ops.positionwise_ffn (w_2 + LayerNorm, K = 1024).  Which form a model takes is host_core.h's rule (fuse_row_epilogue /
 # conv_gemm_ticket_ok): the full-row tile from ceil(M / 32) >= 200 row tiles, the ticketed ladder below; ln_epi restates it and
 # test_layernorm_cases_take_their_forms asks ns_plan_gemm_launches for the form under that epilogue.  Every M leaves a partial last
 # tile; lens are ragged (_lens).
@@ -255,7 +255,7 @@ SCAN_ROWS = 70000
 
 
 def ln_epi(M):
-    """api.hip fuse_row_epilogue: 1 (full-row tile) from ceil(M / 32) >= 200, else 2 (ticketed ladder)"""
+    """host_core.h fuse_row_epilogue: 1 (full-row tile) from ceil(M / 32) >= 200, else 2 (ticketed ladder)"""
     return 1 if (M + 31) // 32 >= 200 else 2
 
 

@@ -873,6 +873,47 @@ def test_rejected_state_dict_leaves_the_loaded_model_usable():
     assert torch.allclose(moved[0], before[0] + 1.0, atol=1e-5)
 
 
+@pytest.mark.parametrize("handle,text", [("model", "missing keys"), ("aligner", "missing keys"), ("vocoder", "missing key '")])
+def test_second_finalize_without_restaging_is_refused_and_keeps_the_weights(handle, text):
+    """include/nar_fs2.h ns_finalize_weights (and its ns_aln_ / ns_voc_ twins): finalizing releases the staged host copies, so a
+    second finalize with nothing staged again names what is missing instead of packing empty vectors, and the handle stays ready on
+    its existing arena — the next forward carries the same bits."""
+    import smart_nar_fast_tts_amd.workload as wl
+    from smart_nar_fast_tts_amd import _lib
+    from smart_nar_fast_tts_amd.model import FastSpeech2Align
+
+    if handle == "vocoder":
+        from smart_nar_fast_tts_amd.vocoder import Generator
+
+        h = dict(wl.hifigan_config("v1"), upsample_initial_channel=128, upsample_rates=[4, 4], upsample_kernel_sizes=[8, 8],
+                 resblock_kernel_sizes=[3, 5], resblock_dilation_sizes=[[1, 3, 5], [1, 2, 3]])
+        g = Generator(h).to("cuda").eval()
+        g.load_state_dict(wl.synth_vocoder_state_dict(h, seed=0))
+        mel = torch.randn(2, 80, 9, generator=torch.Generator().manual_seed(3)).cuda()
+        lib, run = g._lib, lambda: g(mel)
+        finalize = lambda: lib.ns_voc_finalize_weights(g._h, _lib.stream_ptr(g._device))  # noqa: E731
+    elif handle == "aligner":
+        from tests import aligner_cpu as ac
+
+        meta, z = load_golden("aligner_tiny")
+        cfg, sd = ac.fixture_weights(meta)
+        m = FastSpeech2Align(wl.preprocess_config(), cfg).to("cuda").eval()
+        m.load_state_dict(sd)
+        lib, run = m._lib, lambda: m.align(dev(z["texts"]), dev(z["src_lens"]), int(meta["L"]), dev(z["mels"]), dev(z["mel_lens"])).tgt_output
+        finalize = lambda: lib.ns_aln_finalize_weights(m._aln_h, _lib.stream_ptr(m._device))  # noqa: E731
+    else:
+        meta, z = load_golden("e2e_tiny_padded_src")
+        cfg, sd = weights_for(meta)
+        m = FastSpeech2Align(wl.preprocess_config(), cfg).to("cuda").eval()
+        m.load_state_dict(sd)
+        lib, run = m._lib, lambda: run_gpu(m, z, meta)[1]
+        finalize = lambda: lib.ns_finalize_weights(m._h, _lib.stream_ptr(m._device))  # noqa: E731
+    first = run().cpu().numpy()
+    assert finalize() != 0 and text in lib.ns_last_error().decode()
+    again = run().cpu().numpy()
+    assert np.isfinite(first).all() and np.array_equal(first, again)
+
+
 def test_random_shapes_vs_oracle():
     """Fuzz over batch shapes (tile tails of every GEMM variant, ragged lengths, tiny and >128-row utterances,
     1..3 frames per phoneme): HIP path vs the oracle on the same seeded inputs, discrete decisions pinned with targets."""

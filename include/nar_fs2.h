@@ -452,6 +452,55 @@ int ns_aln_op_cross_attention(const float* q, const float* kv, const int64_t* sr
 int ns_aln_op_durations(const float* attn_last, const int64_t* src_lens, const int64_t* mel_lens, int B, int H, int T, int L,
                         int64_t* out, void* stream);
 
+/* ==== Validation loss (the reference's FastSpeech2Loss.forward, model/loss.py:149-250, in eval(): the forward VALUE only) ==========
+ * A handle-less family: the loss has no weights.  Nothing above changes (NS_ABI_VERSION, NS_VOC_ABI_VERSION and NS_ALN_ABI_VERSION
+ * stay as they are).  From the reference's 12-tuple of a teacher-forced batch (ns_forward_durations_teacher + ns_forward_mel) and the
+ * batch's targets it computes, in two launches on `stream`, with no host read and no float atomic:
+ *   mel, postnet   mean |pred - mel_targets[:, :T]| over the n_mel columns of the frames with mel_masks == 0     model/loss.py:189-191,219-227
+ *   pitch, energy  mean (pred - target)^2 over the frames with mel_masks == 0 (frame_level) or the phonemes with
+ *                  src_masks == 0 (phoneme_level)                                                                  model/loss.py:199-211,229-230
+ *   duration       mean (log_d - log((float)d_targets[:, :L] + 1))^2 over the phonemes with src_masks == 0       model/loss.py:190,213-217,231
+ *   attn           sum over k = 0..3 of 10 * mean over {t < olen_b, l < ilen_b} of W[b,t,l] * attn[k][b, 0, t, l],
+ *                  W = 1 - exp(-((l / ilen_b - t / olen_b)^2) / (2 * 0.2^2)) in fp32, ilen = src_lens, olen = the
+ *                  batch's INPUT mel_lens; head 0 only, layers 0-3 hard-coded                                     model/loss.py:60-65,104-108,144-146,233-236
+ *   total          mel + postnet + duration + pitch + energy + attn, in fp32                                     model/loss.py:238-240
+ * A masked-out element is selected away, never multiplied by zero: padded positions may hold NaN (an utterance with src_lens == 0)
+ * and do not reach the sums.  An empty selection gives NaN (torch.mean of nothing), and the total is then NaN.  Equal inputs give
+ * equal bits: the summation order is a function of the shapes alone.
+ * DEVIATION: the reference fails on a broadcast when T != max(mel_lens) or L != max(src_lens) (model/loss.py:60, 69-71); here ilen is
+ * clamped to [0, L] and olen to [0, T], and the selected region is what _make_masks would give if the shapes agreed. */
+#define NS_LOSS_ABI_VERSION 1
+int ns_loss_abi_version(void);
+typedef struct ns_loss_args {
+  int32_t B, L, T, H, n_mel;                          /* attn[k] is [B, H, T, L]; n_mel a multiple of 4 */
+  int32_t pitch_frame_level, energy_frame_level;      /* preprocessing.{pitch,energy}.feature == "frame_level" (model/loss.py:154-159) */
+  int64_t mel_targets_stride;                         /* floats between utterances of mel_targets: T' * n_mel with T' >= T (model/loss.py:191) */
+  int64_t d_targets_stride;                           /* elements between rows of d_targets: L' >= L (model/loss.py:214-216) */
+  const float* mel;                                   /* predictions[0]  [B, T, n_mel]                          model/loss.py:175,219 */
+  const float* postnet;                               /* predictions[1]  [B, T, n_mel]                          model/loss.py:176,220 */
+  const float* mel_targets;                           /* inputs[6]       [B, T', n_mel]                         model/loss.py:168,191,224 */
+  const uint8_t* mel_masks;                           /* predictions[7]  [B, T] bool, nonzero = padded          model/loss.py:182,189 */
+  const float* pitch;                                 /* predictions[2]  [B, T] or [B, L]                       model/loss.py:177,199-204 */
+  const float* pitch_targets;                         /* inputs[9]       same shape                             model/loss.py:171 */
+  const float* energy;                                /* predictions[3]  [B, T] or [B, L]                       model/loss.py:178,206-211 */
+  const float* energy_targets;                        /* inputs[10]      same shape                             model/loss.py:172 */
+  const float* log_d;                                 /* predictions[4]  [B, L]                                 model/loss.py:179,213 */
+  const int64_t* d_targets;                           /* predictions[11] [B, L'] int64                          model/loss.py:186,190 */
+  const uint8_t* src_masks;                           /* predictions[6]  [B, L] bool, nonzero = padded          model/loss.py:181,188 */
+  const int64_t* src_lens;                            /* inputs[4]       [B] int64                              model/loss.py:166,233 */
+  const int64_t* mel_lens;                            /* inputs[7]       [B] int64 — NOT predictions[9]         model/loss.py:169,233 */
+  const float* attn[4];                               /* predictions[10][0..3], read in place at head 0         model/loss.py:233-236 */
+} ns_loss_args;
+/* Bytes of the partial-sum workspace of ns_loss_forward (one 64-byte slot per workgroup); positive, monotone in B, L and T.  The
+ * workspace needs no initialisation. */
+size_t ns_loss_ws_bytes(int B, int L, int T);
+/* Every pointer in `a` is a device pointer; mel, postnet and mel_targets 16-byte aligned, ws 16-byte aligned; out7 <- total, mel,
+ * postnet, pitch, energy, duration, attn (the reference's return order, model/loss.py:242-250) as 7 device floats.  Validation
+ * happens before any HIP call: null pointers (of the tensors the shape makes non-empty), negative sizes, n_mel not a multiple of 4,
+ * strides below the tensor's own extent and ws_bytes < ns_loss_ws_bytes(B, L, T) return nonzero with ns_last_error().  B == 0,
+ * L == 0 or T == 0 is legal and yields NaNs. */
+int ns_loss_forward(const ns_loss_args* a, void* ws, size_t ws_bytes, float* out7, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

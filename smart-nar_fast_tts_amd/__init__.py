@@ -3,5 +3,13 @@
 
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
-when it is missing."""
-__all__ = ["workload"]
+when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "evaluate"]
+
+
+def __getattr__(name):
+    if name in ("FastSpeech2Loss", "evaluate"):
+        from . import loss
+
+        return getattr(loss, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -24,6 +24,15 @@ class NsConfig(C.Structure):
         "matmul_bf16x3", "row_epilogue", "phase1_packing")]
 
 
+class NsLossArgs(C.Structure):
+    """``ns_loss_args`` (include/nar_fs2.h): sizes, the two feature levels, the two strides, then the device pointers."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "L", "T", "H", "n_mel", "pitch_frame_level", "energy_frame_level")]
+                + [(n, C.c_int64) for n in ("mel_targets_stride", "d_targets_stride")]
+                + [(n, C.c_void_p) for n in ("mel", "postnet", "mel_targets", "mel_masks", "pitch", "pitch_targets", "energy", "energy_targets",
+                                             "log_d", "d_targets", "src_masks", "src_lens", "mel_lens")]
+                + [("attn", C.c_void_p * 4)])
+
+
 _P, _I, _F, _Z, _S = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
 
 # name -> (restype, argtypes); must list every symbol include/nar_fs2.h declares
@@ -112,6 +121,10 @@ SIGNATURES = {
     "ns_aln_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ns_aln_op_cross_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ns_aln_op_durations": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    # validation loss (loss.FastSpeech2Loss; handle-less)
+    "ns_loss_abi_version": (_I, []),
+    "ns_loss_ws_bytes": (_Z, [_I, _I, _I]),
+    "ns_loss_forward": (_I, [C.POINTER(NsLossArgs), _P, _Z, _P, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -229,6 +229,25 @@ hipError_t launch_aln_input(const float* mels, float* x, int B, int T, int C, hi
 // out [B, L] int64: frames of utterance b whose head-summed last-layer alignment peaks at phoneme i (zeroes `out` first)
 hipError_t launch_aln_durations(const float* attn_last, const long long* src_lens, const long long* mel_lens, int B, int H, int T, int L,
                                 long long* out, hipStream_t st);
+// ---- FastSpeech2Loss (loss.hip; model/loss.py:149-250).  The device-side mirror of ns_loss_args (include/nar_fs2.h).
+struct LossArgs {
+  int B, L, T, H, n_mel, pitch_frame_level, energy_frame_level;
+  long long mel_targets_stride, d_targets_stride;  // floats between utterances of mel_targets; elements between rows of d_targets
+  const float *mel, *postnet, *mel_targets;        // [B, T, n_mel] x 2, [B, T' >= T, n_mel]
+  const unsigned char* mel_masks;                  // [B, T], nonzero = padded
+  const float *pitch, *pitch_targets, *energy, *energy_targets;  // [B, T] at frame_level, [B, L] at phoneme_level
+  const float* log_d; const long long* d_targets; const unsigned char* src_masks;  // [B, L], [B, L' >= L], [B, L]
+  const long long *src_lens, *mel_lens;            // [B]; mel_lens = the batch's INPUT lengths
+  const float* attn[4];                            // [B, H, T, L] each; head 0 is read in place
+};
+constexpr int LOSS_FRAME_ROWS = 64;      // frame rows per workgroup
+constexpr int LOSS_PHONEME_ROWS = 1024;  // phoneme rows per workgroup
+constexpr int LOSS_ATTN_ROWS = 16;       // query rows (of one utterance, four maps) per workgroup
+constexpr int LOSS_SLOT_SUMS = 6, LOSS_SLOT_WORDS = 8, LOSS_SLOT_BYTES = 64;  // six float64 sums + two int64 counts
+// slots of the partial workspace = workgroups of k_loss_partial; a function of (B, L, T) alone
+long long loss_slots(int B, int L, int T, int* n_frame_wgs, int* n_phoneme_wgs);
+// requires what ns_loss_forward (loss_api.hip) validates; ws >= loss_slots(...) * LOSS_SLOT_BYTES, uninitialised
+hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

@@ -501,6 +501,66 @@ size_t ns_loss_ws_bytes(int B, int L, int T);
  * L == 0 or T == 0 is legal and yields NaNs. */
 int ns_loss_forward(const ns_loss_args* a, void* ws, size_t ws_bytes, float* out7, void* stream);
 
+/* ==== Wave-to-mel front end (the reference's TacotronSTFT.mel_spectrogram + Audio.tools.get_mel_from_wav: audio/stft.py:52-81,
+ * 159-178, audio/tools.py:8-15, audio/audio_processing.py:85-91) ===============================================================
+ * A separate handle with its own weights, arena and workspace; nothing above changes (every other ABI version stays as it is).  For a
+ * batch of variable-length waves wav [B, ld_wav] (utterance b holds n_b = clamp(wav_lens[b], 0, n_max) samples) it computes, in three
+ * launches on `stream`, with no host read and no device allocation:
+ *   x = clip(wav, -1, 1), reflect-padded by filter_length / 2 on both sides (torch's "reflect": the edge sample is not repeated)
+ *   frame t = x[t hop .. t hop + filter_length), spectrum = frame . forward_basis rows           F.conv1d(stride = hop), stft.py:67-72
+ *   mag_k = sqrtf(re_k^2 + im_k^2), k = 0 .. filter_length / 2                                   stft.py:78
+ *   energy[b, t] = sqrtf(sum_k mag_k^2)                                                          torch.norm, stft.py:176
+ *   mel[b, t, m] = (float)log((double)max(sum_k mel_basis[m, k] mag_k, clip_val))                stft.py:174-175, audio_processing.py:91
+ * mel is TIME-major [B, T, n_mel] (the layout ns_aln_forward and ns_forward_durations_teacher take), energy [B, T].  Frames
+ * t >= mel_lens[b] = n_b / hop + 1 hold zeros in both (what pad_2D / pad_1D give a collated batch); mel_lens_out[b] is that count, not
+ * clamped to T.  An utterance with n_b <= filter_length / 2 (which the reference's reflect pad refuses) has ZERO frames.  Samples at
+ * and beyond n_b are never read; a NaN sample stays a NaN and reaches exactly the frames whose window covers it.  Equal inputs give
+ * equal bits, and replicas of one utterance inside a batch are bit-identical: every reduction order is a function of the shapes alone.
+ * The STFT is one fp32 Conv1D-as-GEMM over the padded wave cut into rows of hop samples (Cin = hop, KW = filter_length / hop, pad 0);
+ * the imaginary basis rows of bins 0 and filter_length / 2 are identically zero and are dropped, which leaves filter_length columns.
+ * The mel basis is consumed in band form (per filter: first to last non-zero bin), summed in bin order; any dense matrix is legal.
+ * DEVIATION: the reference asserts min >= -1 and max <= 1 (a host read, stft.py:169-170); here the samples are clipped instead, the
+ * identity on everything the assertion lets through (and what get_mel_from_wav does ahead of the call, tools.py:9). */
+#define NS_MEL_ABI_VERSION 1
+typedef struct ns_melfront ns_melfront;
+typedef struct ns_mel_config {
+  int32_t filter_length, hop_length, win_length, n_mel;   /* 1024, 256, 1024, 80 */
+  float clip_val;                                         /* dynamic_range_compression's clip_val: 1e-5 */
+} ns_mel_config;
+int ns_mel_abi_version(void);
+/* Rejects (nonzero, ns_last_error): filter_length % hop_length != 0, hop_length % 32 != 0, win_length > filter_length (or < 1),
+ * n_mel % 4 != 0, and a filter_length outside what the GEMM dispatch accepts for N = KW * Cin = filter_length (and above 4096, the
+ * magnitude row a workgroup stages on chip). */
+int ns_mel_create(const ns_mel_config* cfg, ns_melfront** out);
+void ns_mel_destroy(ns_melfront* h);
+size_t ns_mel_arena_bytes(const ns_melfront* h);
+int ns_mel_bind_arena(ns_melfront* h, void* dev_arena, size_t bytes);  /* 256-byte aligned */
+/* host float32, the reference module's buffer names and torch-native shapes: "stft_fn.forward_basis" [filter_length + 2, 1,
+ * filter_length], "mel_basis" [n_mel, filter_length / 2 + 1]; "stft_fn.inverse_basis" is accepted and ignored.  finalize refuses a
+ * forward_basis whose imaginary rows of bins 0 or filter_length / 2 hold an entry of magnitude above 1e-6 (not a real DFT basis). */
+int ns_mel_set_weight(ns_melfront* h, const char* name, const float* host, const int64_t* shape, int ndim);
+int ns_mel_check_weight(ns_melfront* h, const char* name, const int64_t* shape, int ndim);
+int ns_mel_finalize_weights(ns_melfront* h, void* stream);
+/* frames of a wave of n samples: n / hop + 1 (0 for n < 0 or hop < 1) */
+int64_t ns_mel_frames(int64_t n, int32_t hop);
+/* Workspace of ns_mel_forward for B waves of at most n_max samples (hop rows + packed spectrum); monotone in B and n_max.  Needs no
+ * initialisation: every word that is read is written first. */
+size_t ns_mel_ws_bytes(const ns_melfront* h, int B, int64_t n_max);
+/* wav [B, ld_wav] fp32 (ld_wav >= n_max), wav_lens [B] int64, both on the device; T >= 1 is the caller's choice: frames beyond it
+ * are dropped, frames up to it zero-filled.  Writes mel [B, T, n_mel], energy [B, T], mel_lens_out [B] int64. */
+int ns_mel_forward(ns_melfront* h, const float* wav, int64_t ld_wav, const int64_t* wav_lens, int B, int64_t n_max, int T, float* mel,
+                   float* energy, int64_t* mel_lens_out, void* ws, size_t ws_bytes, void* stream);
+/* ---- per-operator entry points (tests); S = Tc + filter_length / hop - 1 hop rows per utterance for Tc computed frames ----
+ * frame_rows: rows [B, S, hop] from the waves (mel_lens_out nullable)
+ * stft:       rows [B, S, hop] -> packed spectrum [B * S, filter_length]: column 0 = re_0, 1 = re_{filter_length/2}, 2k = re_k,
+ *             2k + 1 = im_k; rows t >= Tc of an utterance are computed from partial taps and mean nothing
+ * project:    packed spectrum -> mel [B, T, n_mel], energy [B, T] */
+int ns_mel_op_frame_rows(ns_melfront* h, const float* wav, int64_t ld_wav, const int64_t* wav_lens, int B, int64_t n_max, int S,
+                         float* rows, int64_t* mel_lens_out, void* stream);
+int ns_mel_op_stft(ns_melfront* h, const float* rows, int B, int S, float* spec, void* stream);
+int ns_mel_op_project(ns_melfront* h, const float* spec, const int64_t* wav_lens, int B, int S, int64_t n_max, int T, float* mel,
+                      float* energy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

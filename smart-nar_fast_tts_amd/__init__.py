@@ -3,8 +3,9 @@
 
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
-when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "evaluate"]
+when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``), ``TacotronSTFT`` and ``get_mel_from_wav``
+(``audio``) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav"]
 
 
 def __getattr__(name):
@@ -12,4 +13,8 @@ def __getattr__(name):
         from . import loss
 
         return getattr(loss, name)
+    if name in ("TacotronSTFT", "get_mel_from_wav"):
+        from . import audio
+
+        return getattr(audio, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -33,6 +33,11 @@ class NsLossArgs(C.Structure):
                 + [("attn", C.c_void_p * 4)])
 
 
+class NsMelConfig(C.Structure):
+    """``ns_mel_config`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
+
+
 _P, _I, _F, _Z, _S = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
 
 # name -> (restype, argtypes); must list every symbol include/nar_fs2.h declares
@@ -125,6 +130,21 @@ SIGNATURES = {
     "ns_loss_abi_version": (_I, []),
     "ns_loss_ws_bytes": (_Z, [_I, _I, _I]),
     "ns_loss_forward": (_I, [C.POINTER(NsLossArgs), _P, _Z, _P, _P]),
+    # wave-to-mel front end (audio.TacotronSTFT)
+    "ns_mel_abi_version": (_I, []),
+    "ns_mel_create": (_I, [C.POINTER(NsMelConfig), C.POINTER(_P)]),
+    "ns_mel_destroy": (None, [_P]),
+    "ns_mel_arena_bytes": (_Z, [_P]),
+    "ns_mel_bind_arena": (_I, [_P, _P, _Z]),
+    "ns_mel_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
+    "ns_mel_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
+    "ns_mel_finalize_weights": (_I, [_P, _P]),
+    "ns_mel_frames": (C.c_int64, [C.c_int64, C.c_int32]),
+    "ns_mel_ws_bytes": (_Z, [_P, _I, C.c_int64]),
+    "ns_mel_forward": (_I, [_P, _P, C.c_int64, _P, _I, C.c_int64, _I, _P, _P, _P, _P, _Z, _P]),
+    "ns_mel_op_frame_rows": (_I, [_P, _P, C.c_int64, _P, _I, C.c_int64, _I, _P, _P, _P]),
+    "ns_mel_op_stft": (_I, [_P, _P, _I, _I, _P, _P]),
+    "ns_mel_op_project": (_I, [_P, _P, _P, _I, _I, C.c_int64, _I, _P, _P, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

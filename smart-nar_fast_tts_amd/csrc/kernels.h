@@ -248,6 +248,16 @@ constexpr int LOSS_SLOT_SUMS = 6, LOSS_SLOT_WORDS = 8, LOSS_SLOT_BYTES = 64;  //
 long long loss_slots(int B, int L, int T, int* n_frame_wgs, int* n_phoneme_wgs);
 // requires what ns_loss_forward (loss_api.hip) validates; ws >= loss_slots(...) * LOSS_SLOT_BYTES, uninitialised
 hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st);
+// ---- wave-to-mel front end (melfront.hip; audio/stft.py:52-81,159-178, audio/tools.py:8-15) ----------------------------------
+// rows [B, S, hop]: the clipped, reflect-padded wave of utterance b (n_b = clamp(wav_lens[b], 0, n_max) samples) laid out as S * hop
+// consecutive samples; zeros from sample n_b + fl on, all zeros when n_b <= fl / 2.  mel_lens_out (nullable) [B] = n_b / hop + 1 or 0.
+hipError_t launch_mel_frame_rows(const float* wav, long long ld, const long long* wav_lens, int B, long long n_max, int fl, int hop, int S,
+                                 float* rows, long long* mel_lens_out, hipStream_t st);
+// packed spectrum [B * S, fl] (column 0 = re_0, 1 = re_{fl/2}, 2k = re_k, 2k + 1 = im_k) -> mel [B, T, n_mel] = log(max(band sums, clip)) (taken in double, rounded once),
+// energy [B, T]; zeros at frames t >= mel_lens[b].  band [n_mel][3] = {first bin, bins, offset into bw}; fl <= MEL_MAX_FILTER.
+constexpr int MEL_MAX_FILTER = 4096;
+hipError_t launch_mel_project(const float* spec, const long long* wav_lens, int B, int S, long long n_max, int T, int fl, int hop, int n_mel,
+                              float clip, const int* band, const float* bw, float* mel, float* energy, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

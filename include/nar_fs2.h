@@ -394,9 +394,17 @@ int ns_voc_forward(ns_vocoder* v, const float* mel, int mel_layout, int B, int T
  * conv:     name = "resblocks.{r}.convs{1,2}.{n}": out = conv(lrelu(x, 0.1)) + bias, [B, S, ch] -> [B, S, ch];
  *           "conv_pre": out = conv(x) + bias, [B, S, n_mel] -> [B, S, C0];
  *           "conv_post": out = tanh(conv(lrelu(x, 0.01)) + bias), [B, S, C_last] -> [B, S].
+ * conv_form: one resblock launch in any form the stage gives it, name = "resblocks.{r}.convs{1,2}.{n}" only:
+ *           v = conv(in_act ? lrelu(x, 0.1) : x) + bias;  if out_act: v = lrelu(v, 0.1);  if resid: v = v + resid;
+ *           mrf 0: y = v;  1: y = y + v;  2: y = (y + v) / n_rb   (y is read and rewritten when mrf != 0)
+ *           The stage launches c1 as (in_act 1, out_act 1), c2 as (in_act 0, resid = the pair's input), the last c2 of resblock
+ *           j of a stage with mrf 0 / 1 / 2 for j = 0 / between / n_rb - 1.  x, resid, y: [B, S, ch]; resid may be NULL; x 16-byte
+ *           aligned.  A bad name, a null x or y, an mrf outside {0, 1, 2} or a misaligned x fails before any HIP call.
  * upsample: out = ups[i](lrelu(x, 0.1)), [B, S, 2 ch] -> [B, S u, ch]
  * stage:    upsample i followed by its n_rb resblocks and their mean, [B, S, 2 ch] -> [B, S u, ch]; ws >= ns_voc_op_stage_ws_bytes */
 int ns_voc_op_conv(ns_vocoder* v, const char* name, const float* x, int B, int S, float* out, void* stream);
+int ns_voc_op_conv_form(ns_vocoder* v, const char* name, const float* x, const float* resid, float* y, int B, int S, int in_act,
+                        int out_act, int mrf, void* stream);
 int ns_voc_op_upsample(ns_vocoder* v, int i, const float* x, int B, int S, float* out, void* stream);
 size_t ns_voc_op_stage_ws_bytes(const ns_vocoder* v, int i, int B, int S);
 int ns_voc_op_stage(ns_vocoder* v, int i, const float* x, int B, int S, float* out, void* ws, size_t ws_bytes, void* stream);

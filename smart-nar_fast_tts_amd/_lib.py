@@ -110,6 +110,7 @@ SIGNATURES = {
     "ns_voc_ws_bytes": (_Z, [_P, _I, _I]),
     "ns_voc_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "ns_voc_op_conv": (_I, [_P, _S, _P, _I, _I, _P, _P]),
+    "ns_voc_op_conv_form": (_I, [_P, _S, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ns_voc_op_upsample": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "ns_voc_op_stage_ws_bytes": (_Z, [_P, _I, _I, _I]),
     "ns_voc_op_stage": (_I, [_P, _I, _P, _I, _I, _P, _P, _Z, _P]),

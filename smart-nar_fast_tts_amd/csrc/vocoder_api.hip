@@ -207,6 +207,19 @@ static VocGemm same_conv(const ns_vocoder* v, const Conv& w, const float* x, int
   return p;
 }
 
+// one resblock launch in the form stage() gives it: same_conv() with the input / output leaky ReLU switches, the residual and the
+// multi-receptive-field step (0 store, 1 y += v, 2 y = (y + v) / n_rb) set, nothing else
+static VocGemm form_conv(const ns_vocoder* v, const Conv& w, const float* x, const float* resid, float* y, int B, int S, int in_act,
+                         int out_act, int mrf) {
+  VocGemm p = same_conv(v, w, x, B, S, y);
+  p.in_act = in_act ? 1 : 0;
+  p.out_act = out_act ? 1 : 0;
+  p.R = resid;
+  p.mrf = mrf;
+  p.mrf_div = (float)v->cfg.n_rb;
+  return p;
+}
+
 static int upsample(const ns_vocoder* v, int i, const float* x, int B, int S, float* y, hipStream_t st) {
   const Conv& w = v->ups[i];
   const int u = v->cfg.up_rates[i];
@@ -230,17 +243,10 @@ static int stage(const ns_vocoder* v, int i, const float* x, int B, int S, float
     for (int n = 0; n < N_DIL; ++n) {
       const int idx = (c.n_rb * i + j) * N_DIL + n;
       const float* in = n == 0 ? U : CUR;
-      VocGemm p1 = same_conv(v, v->c1[idx], in, B, So, H);
-      p1.out_act = 1;  // lrelu(c1(.), 0.1): c2's input
-      NS_HIP(voc_gemm(p1, st));
-      VocGemm p2 = same_conv(v, v->c2[idx], H, B, So, n == N_DIL - 1 ? xs : CUR);
-      p2.in_act = 0;
-      p2.R = in;
-      if (n == N_DIL - 1 && c.n_rb > 1) {  // xs = rb0(x); xs += rb_j(x); x = xs / n_rb
-        p2.mrf = j == 0 ? 0 : (j == c.n_rb - 1 ? 2 : 1);
-        p2.mrf_div = (float)c.n_rb;
-      }
-      NS_HIP(voc_gemm(p2, st));
+      NS_HIP(voc_gemm(form_conv(v, v->c1[idx], in, nullptr, H, B, So, 1, 1, 0), st));  // lrelu(c1(.), 0.1): c2's input
+      int mrf = 0;
+      if (n == N_DIL - 1 && c.n_rb > 1) mrf = j == 0 ? 0 : (j == c.n_rb - 1 ? 2 : 1);  // xs = rb0(x); xs += rb_j(x); x = xs / n_rb
+      NS_HIP(voc_gemm(form_conv(v, v->c2[idx], H, in, n == N_DIL - 1 ? xs : CUR, B, So, 0, 0, mrf), st));
     }
   }
   return 0;
@@ -314,6 +320,16 @@ extern "C" int ns_voc_forward(ns_vocoder* v, const float* mel, int mel_layout, i
 }
 
 // ------------------------------------------------------------------------------------------------ per-operator entry points
+// "resblocks.{r}.convs{1,2}.{n}" -> its conv, nullptr for any other name
+static const Conv* resblock_conv(const ns_vocoder* v, const char* name) {
+  int r = -1, which = 0, n = -1;
+  char tail = 0;
+  if (sscanf(name, "resblocks.%d.convs%d.%d%c", &r, &which, &n, &tail) != 3 || r < 0 || r >= v->cfg.n_up * v->cfg.n_rb ||
+      (which != 1 && which != 2) || n < 0 || n >= N_DIL)
+    return nullptr;
+  return &(which == 1 ? v->c1 : v->c2)[r * N_DIL + n];
+}
+
 extern "C" int ns_voc_op_conv(ns_vocoder* v, const char* name_c, const float* x, int B, int S, float* out, void* stream) {
   NS_TRY(check_ready(v, "ns_voc_op_conv"));
   if (!name_c || !x || !out || B <= 0 || S <= 0) return api_fail("ns_voc_op_conv: bad argument");
@@ -324,13 +340,23 @@ extern "C" int ns_voc_op_conv(ns_vocoder* v, const char* name_c, const float* x,
     NS_HIP(launch_voc_post(x, A(v, v->post.w), A(v, v->post.b), out, B, S, v->post.cin, PRE_POST_K, POST_SLOPE, st));
     return 0;
   }
-  int r = -1, which = 0, n = -1;
-  char tail = 0;
-  if (sscanf(name_c, "resblocks.%d.convs%d.%d%c", &r, &which, &n, &tail) != 3 || r < 0 || r >= v->cfg.n_up * v->cfg.n_rb ||
-      (which != 1 && which != 2) || n < 0 || n >= N_DIL)
-    return api_fail("ns_voc_op_conv: unknown module '" + name + "' (conv_pre, conv_post or resblocks.{r}.convs{1,2}.{n})");
-  const Conv& w = (which == 1 ? v->c1 : v->c2)[r * N_DIL + n];
-  NS_HIP(voc_gemm(same_conv(v, w, x, B, S, out), st));
+  const Conv* w = resblock_conv(v, name_c);
+  if (!w) return api_fail("ns_voc_op_conv: unknown module '" + name + "' (conv_pre, conv_post or resblocks.{r}.convs{1,2}.{n})");
+  NS_HIP(voc_gemm(same_conv(v, *w, x, B, S, out), st));
+  return 0;
+}
+
+extern "C" int ns_voc_op_conv_form(ns_vocoder* v, const char* name, const float* x, const float* resid, float* y, int B, int S, int in_act,
+                                   int out_act, int mrf, void* stream) {
+  // every argument is checked on the host before the handle's state: a refused call has made no HIP call
+  if (!v) return api_fail("ns_voc_op_conv_form: null vocoder");
+  if (!name || !x || !y || B <= 0 || S <= 0) return api_fail("ns_voc_op_conv_form: bad argument");
+  const Conv* w = resblock_conv(v, name);
+  if (!w) return api_fail("ns_voc_op_conv_form: unknown module '" + std::string(name) + "' (resblocks.{r}.convs{1,2}.{n})");
+  if (mrf < 0 || mrf > 2) return api_fail("ns_voc_op_conv_form: mrf must be 0 (store), 1 (y += v) or 2 (y = (y + v) / n_rb), got " + std::to_string(mrf));
+  if ((uintptr_t)x & 15) return api_fail("ns_voc_op_conv_form: x must be 16-byte aligned");
+  NS_TRY(check_ready(v, "ns_voc_op_conv_form"));
+  NS_HIP(voc_gemm(form_conv(v, *w, x, resid, y, B, S, in_act, out_act, mrf), (hipStream_t)stream));
   return 0;
 }
 

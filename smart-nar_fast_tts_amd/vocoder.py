@@ -280,10 +280,41 @@ class Generator:
                    "ns_voc_op_conv")
         return out
 
-    def op_upsample(self, i: int, x: torch.Tensor) -> torch.Tensor:
+    def op_conv_form(self, name: str, x: torch.Tensor, *, in_act: bool = True, out_act: bool = False, residual=None, mrf: int = 0,
+                     acc=None) -> torch.Tensor:
+        """One resblock launch ("resblocks.{r}.convs{1,2}.{n}") in a form the stage gives it (ns_voc_op_conv_form):
+        v = conv(lrelu(x) if in_act else x) + bias, lrelu(v) if out_act, + residual; mrf 0 returns v, 1 returns acc + v,
+        2 returns (acc + v) / n_rb.  ``acc`` (the running multi-receptive-field sum) is required when mrf != 0 and refused
+        otherwise; it is cloned into the output, never written."""
+        self._ready(x)
+        if mrf not in (0, 1, 2):
+            raise ValueError(f"mrf must be 0, 1 or 2, got {mrf!r}")
+        if (acc is None) != (mrf == 0):
+            raise ValueError("acc (the running multi-receptive-field sum) is required when mrf != 0 and refused when mrf == 0")
+        B, S, ch = x.shape
+        w = self._sd.get(name + ".weight")
+        if w is not None and w.shape[1] != ch:  # (an unknown name is the library's to refuse)
+            raise ValueError(f"{name} takes [B, S, {w.shape[1]}] activations, got {tuple(x.shape)}")
+        x = x.contiguous()
+        for t, what in ((residual, "residual"), (acc, "acc")):
+            if t is not None and (t.shape != x.shape or t.dtype != torch.float32 or t.device != x.device):
+                raise ValueError(f"{what} must be a float32 tensor of x's shape {tuple(x.shape)} on x's device")
+        residual = None if residual is None else residual.contiguous()
+        out = torch.empty_like(x) if acc is None else acc.clone(memory_format=torch.contiguous_format)
+        _lib.check(self._lib.ns_voc_op_conv_form(self._h, name.encode(), _lib.ptr(x), _lib.ptr(residual), _lib.ptr(out), B, S,
+                                                 int(bool(in_act)), int(bool(out_act)), int(mrf), _lib.stream_ptr(x.device)),
+                   "ns_voc_op_conv_form")
+        return out
+
+    def op_upsample(self, i: int, x: torch.Tensor, out=None) -> torch.Tensor:
+        """``out``: a caller's [B, S u, C / 2] float32 tensor to write into (tests pre-fill it to see every element written)"""
         self._ready(x)
         B, S, cin = x.shape
-        out = torch.empty(B, S * int(self.h["upsample_rates"][i]), cin // 2, device=x.device)
+        shape = (B, S * int(self.h["upsample_rates"][i]), cin // 2)
+        if out is None:
+            out = torch.empty(shape, device=x.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on x's device")
         x = x.contiguous()
         _lib.check(self._lib.ns_voc_op_upsample(self._h, int(i), _lib.ptr(x), B, S, _lib.ptr(out), _lib.stream_ptr(x.device)),
                    "ns_voc_op_upsample")

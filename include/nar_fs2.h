@@ -569,6 +569,79 @@ int ns_mel_op_stft(ns_melfront* h, const float* rows, int B, int S, float* spec,
 int ns_mel_op_project(ns_melfront* h, const float* spec, const int64_t* wav_lens, int B, int S, int64_t n_max, int T, float* mel,
                       float* energy, void* stream);
 
+/* ================================================================================================================================
+ * Griffin-Lim mel-to-wave: the other half of the reference's audio/ package — inv_mel_spec (audio/tools.py:18-34), griffin_lim
+ * (audio/audio_processing.py:66-82), STFT.inverse and STFT.transform (audio/stft.py:52-122), window_sumsquare
+ * (audio/audio_processing.py:7-63).  It needs no trained weights.  A separate handle over the same three buffers as ns_mel_*; all
+ * three are used here.  Per utterance, with N = filter_length, Tg_b frames and n_b = hop (Tg_b - 1) samples:
+ *   mag[t, k]  = scaling * sum_m expf(mel[t, m]) mel_basis[m, k], t < Tg_b = mel_lens[b] - 1        tools.py:20-25,28 (the last frame is dropped;
+ *                m ascending; the TRANSPOSE of mel_basis, not a pseudo-inverse: what the reference does)
+ *   X          = (mag cos(angles), mag sin(angles)) in the packed layout of ns_mel_op_stft          stft.py:84-86
+ *   frames     = X . inverse_basis rows (one fp32 GEMM, K = N = filter_length per frame)            F.conv_transpose1d, stft.py:88-93
+ *   y[s]       = (N / hop) * (sum_t frames[t, s + N/2 - t hop]) / window_sum_b[s + N/2]             stft.py:95-120
+ *                where window_sum_b > FLT_MIN; t ascending (at most N / hop terms); window_sum_b is rebuilt per sample with the
+ *                reference's arithmetic: an fp32 accumulator, each += adds a float64 squared-window value and rounds once
+ *   iteration:   signal -> reflect-padded hop rows WITHOUT a clip -> forward STFT GEMM -> X = mag * Y / |Y| per bin -> inverse
+ *                (audio_processing.py:79-81; mag * Y / |Y| is mag (cos, sin)(atan2(im, re)) without the angle: (mag, 0) where Y = 0,
+ *                +-mag at bins 0 and N/2, a NaN in either component makes both outputs of its bin NaN; the loop evaluates no atan2f, cosf or sinf)
+ * No host read, no device allocation, no atomics: equal inputs give equal bits and replicas of an utterance inside a batch are
+ * bit-identical.  Frame counts are device int64 [B], CLAMPED to [0, frames of the call] rather than validated; an utterance with
+ * n_b <= filter_length / 2 (which the reference's reflect pad refuses) gives a zero wave of length 0.  Samples at and beyond n_b and
+ * rows at and beyond Tg_b are written as zeros.
+ * DEVIATIONS: the two imaginary columns of bins 0 and N/2 are dropped (their inverse_basis rows are zero up to the 1e-18 noise of
+ * the reference's pinv; finalize refuses anything above 1e-9), and tools.py:28 reads `_stft._stft_fn`, an attribute that does not
+ * exist: the evident intent `stft_fn` is what is implemented. */
+#define NS_GL_ABI_VERSION 1
+typedef struct ns_gl ns_gl;
+typedef struct ns_gl_config {
+  int32_t filter_length, hop_length, win_length, n_mel;   /* 1024, 256, 1024, 80 */
+  float spec_from_mel_scaling;                            /* the reference's literal 1000, tools.py:22 */
+} ns_gl_config;
+int ns_gl_abi_version(void);
+/* The constraints of ns_mel_create (filter_length % hop_length, hop_length % 32, win_length, n_mel % 4, the GEMM's range for
+ * N = K = filter_length <= 4096); spec_from_mel_scaling > 0. */
+int ns_gl_create(const ns_gl_config* cfg, ns_gl** out);
+void ns_gl_destroy(ns_gl* h);
+size_t ns_gl_arena_bytes(const ns_gl* h);
+int ns_gl_bind_arena(ns_gl* h, void* dev_arena, size_t bytes);  /* 256-byte aligned */
+/* host float32, the reference module's buffer names and torch-native shapes: "stft_fn.forward_basis" and "stft_fn.inverse_basis"
+ * [filter_length + 2, 1, filter_length] (stft.py:49-50), "mel_basis" [n_mel, filter_length / 2 + 1] (stft.py:149).  mel_basis is
+ * optional (a bare STFT has none): without it ns_gl_forward and ns_gl_op_mel_to_mag refuse.  finalize refuses a missing basis. */
+int ns_gl_set_weight(ns_gl* h, const char* name, const float* host, const int64_t* shape, int ndim);
+int ns_gl_check_weight(ns_gl* h, const char* name, const int64_t* shape, int ndim);
+int ns_gl_finalize_weights(ns_gl* h, void* stream);
+/* Workspace for B utterances of at most T_max frames (mel or magnitude frames); monotone in both.  Needs no initialisation: every
+ * word that is read is written first. */
+size_t ns_gl_ws_bytes(const ns_gl* h, int B, int T_max);
+/* inv_mel_spec's batched core (tools.py:18-29): mel [B, T, n_mel] log-mel, TIME-major; mel_lens [B] int64; angles [B, T - 1,
+ * filter_length / 2 + 1] (the start of audio_processing.py:74, time-major); n_iters >= 0 (0 = the initial inverse alone).  Writes
+ * wave [B, ld_wave] (ld_wave % 4 == 0, >= hop (T - 2); 16-byte aligned) and wave_lens_out [B] = n_b. */
+int ns_gl_forward(ns_gl* h, const float* mel, const int64_t* mel_lens, int B, int T, const float* angles, int n_iters, float* wave,
+                  int64_t ld_wave, int64_t* wave_lens_out, void* ws, size_t ws_bytes, void* stream);
+/* griffin_lim (audio_processing.py:66-82) from magnitudes mag [B, Tg, filter_length / 2 + 1], frame_lens [B] int64 */
+int ns_gl_forward_mag(ns_gl* h, const float* mag, const int64_t* frame_lens, int B, int Tg, const float* angles, int n_iters, float* wave,
+                      int64_t ld_wave, int64_t* wave_lens_out, void* ws, size_t ws_bytes, void* stream);
+/* STFT.transform (stft.py:52-81) for users of the class: wav [B, ld_wav] -> magnitude, phase [B, T, filter_length / 2 + 1] =
+ * sqrtf(re^2 + im^2), atan2f(im, re); no clip; the length rules of ns_mel_forward.  Never called by the loop. */
+int ns_gl_transform(ns_gl* h, const float* wav, int64_t ld_wav, const int64_t* wav_lens, int B, int64_t n_max, int T, float* magnitude,
+                    float* phase, void* ws, size_t ws_bytes, void* stream);
+/* ---- per-operator entry points (tests); frame_lens [B] int64 are magnitude frame counts, X / Y packed rows of filter_length ----
+ * mel_to_mag: tools.py:20-25,28 -> mag [B, T - 1, filter_length / 2 + 1]
+ * recombine:  stft.py:84-86 -> X [B * Tg, filter_length]
+ * rephase:    stft.py:79 + 84-86 from the packed spectrum Y [B * S, filter_length] (S >= Tg rows per utterance) -> X
+ * inverse:    stft.py:88-120 from X -> wave, wave_lens_out
+ * frame_rows: stft.py:58-65, ns_mel_op_frame_rows without the clip
+ * step:       audio_processing.py:80-81, one iteration in place on wave (wave_lens_out is rewritten from frame_lens first) */
+int ns_gl_op_mel_to_mag(ns_gl* h, const float* mel, const int64_t* mel_lens, int B, int T, float* mag, void* stream);
+int ns_gl_op_recombine(ns_gl* h, const float* mag, const float* angles, const int64_t* frame_lens, int B, int Tg, float* X, void* stream);
+int ns_gl_op_rephase(ns_gl* h, const float* Y, const float* mag, const int64_t* frame_lens, int B, int Tg, int S, float* X, void* stream);
+int ns_gl_op_inverse(ns_gl* h, const float* X, const int64_t* frame_lens, int B, int Tg, float* wave, int64_t ld_wave,
+                     int64_t* wave_lens_out, void* ws, size_t ws_bytes, void* stream);
+int ns_gl_op_frame_rows(ns_gl* h, const float* wav, int64_t ld_wav, const int64_t* wav_lens, int B, int64_t n_max, int S, float* rows,
+                        void* stream);
+int ns_gl_op_step(ns_gl* h, const float* mag, const int64_t* frame_lens, int B, int Tg, float* wave, int64_t ld_wave,
+                  int64_t* wave_lens_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

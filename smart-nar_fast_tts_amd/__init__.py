@@ -3,9 +3,9 @@
 
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
-when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``), ``TacotronSTFT`` and ``get_mel_from_wav``
-(``audio``) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav"]
+when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
+``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec"]
 
 
 def __getattr__(name):
@@ -13,7 +13,7 @@ def __getattr__(name):
         from . import loss
 
         return getattr(loss, name)
-    if name in ("TacotronSTFT", "get_mel_from_wav"):
+    if name in ("TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec"):
         from . import audio
 
         return getattr(audio, name)

@@ -38,6 +38,11 @@ class NsMelConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
 
 
+class NsGlConfig(C.Structure):
+    """``ns_gl_config`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("spec_from_mel_scaling", C.c_float)]
+
+
 _P, _I, _F, _Z, _S = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
 
 # name -> (restype, argtypes); must list every symbol include/nar_fs2.h declares
@@ -146,6 +151,25 @@ SIGNATURES = {
     "ns_mel_op_frame_rows": (_I, [_P, _P, C.c_int64, _P, _I, C.c_int64, _I, _P, _P, _P]),
     "ns_mel_op_stft": (_I, [_P, _P, _I, _I, _P, _P]),
     "ns_mel_op_project": (_I, [_P, _P, _P, _I, _I, C.c_int64, _I, _P, _P, _P]),
+    # Griffin-Lim mel-to-wave (audio.STFT, audio.griffin_lim, audio.mel_to_wave)
+    "ns_gl_abi_version": (_I, []),
+    "ns_gl_create": (_I, [C.POINTER(NsGlConfig), C.POINTER(_P)]),
+    "ns_gl_destroy": (None, [_P]),
+    "ns_gl_arena_bytes": (_Z, [_P]),
+    "ns_gl_bind_arena": (_I, [_P, _P, _Z]),
+    "ns_gl_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
+    "ns_gl_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
+    "ns_gl_finalize_weights": (_I, [_P, _P]),
+    "ns_gl_ws_bytes": (_Z, [_P, _I, _I]),
+    "ns_gl_forward": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, C.c_int64, _P, _P, _Z, _P]),
+    "ns_gl_forward_mag": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, C.c_int64, _P, _P, _Z, _P]),
+    "ns_gl_transform": (_I, [_P, _P, C.c_int64, _P, _I, C.c_int64, _I, _P, _P, _P, _Z, _P]),
+    "ns_gl_op_mel_to_mag": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "ns_gl_op_recombine": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "ns_gl_op_rephase": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "ns_gl_op_inverse": (_I, [_P, _P, _P, _I, _I, _P, C.c_int64, _P, _P, _Z, _P]),
+    "ns_gl_op_frame_rows": (_I, [_P, _P, C.c_int64, _P, _I, C.c_int64, _I, _P, _P]),
+    "ns_gl_op_step": (_I, [_P, _P, _P, _I, _I, _P, C.c_int64, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

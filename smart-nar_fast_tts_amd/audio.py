@@ -3,6 +3,10 @@
 stream (csrc/melfront.hip around one Conv1D-as-GEMM; ``ns_mel_*`` in include/nar_fs2.h).  It produces the ``mels`` that
 ``align()``, ``forward_teacher_forced()`` and ``FastSpeech2Loss`` consume, without a host round trip.
 
+The other half of the reference's ``audio/`` package lives here too: ``STFT`` (``transform`` / ``inverse``, audio/stft.py:15-127),
+``griffin_lim`` (audio/audio_processing.py:66-82), ``mel_to_wave`` / ``inv_mel_spec`` (audio/tools.py:18-34) over ``ns_gl_*``
+(csrc/griffinlim.hip): a mel becomes a waveform without any trained weights.
+
 DEVIATIONS from the reference, both documented in DESIGN.md §15:
   * the reference asserts ``min >= -1`` and ``max <= 1`` (a host read, stft.py:169-170); here the kernel clips, which is the
     identity on anything the assertion lets through and what ``get_mel_from_wav`` does ahead of the call (tools.py:9);
@@ -42,6 +46,38 @@ def stft_forward_basis(filter_length: int, win_length: int) -> np.ndarray:
     basis = np.vstack([np.real(fourier[:cutoff]), np.imag(fourier[:cutoff])]).astype(np.float32)
     window = pad_center(hann_periodic(win_length), filter_length).astype(np.float32)
     return np.ascontiguousarray((basis * window[None, :])[:, None, :], dtype=np.float32)
+
+
+def stft_inverse_basis(filter_length: int, hop_length: int, win_length: int) -> np.ndarray:
+    """``STFT.inverse_basis`` [filter_length + 2, 1, filter_length] (stft.py:25,34-36,47).  The reference takes
+    ``pinv(scale * fourier_basis).T`` with ``scale = filter_length / hop_length`` through LAPACK, whose last bits depend on the
+    machine; here it is the closed form.  The real-DFT matrix has two zero rows (im_0, im_{N/2}) and is invertible without them, so its
+    pseudo-inverse is the inverse real DFT: row re_k = w_k cos(2 pi k n / N) / scale, row im_k = -w_k sin(2 pi k n / N) / scale,
+    w_0 = w_{N/2} = 1 / N, otherwise 2 / N, and the rows im_0 and im_{N/2} exactly zero (the reference holds ~1e-18 there).  Rounded to
+    fp32, then multiplied IN fp32 by the fp32 centre-padded window, as stft.py:43-47 does."""
+    n = filter_length
+    fourier = np.fft.fft(np.eye(n))
+    cutoff = n // 2 + 1
+    w = np.full(cutoff, 2.0 / n)
+    w[0] = w[n // 2] = 1.0 / n
+    scale = filter_length / hop_length
+    basis = np.vstack([np.real(fourier[:cutoff]), np.imag(fourier[:cutoff])]) * np.concatenate([w, w])[:, None] / scale
+    basis[cutoff] = 0.0
+    basis[cutoff + n // 2] = 0.0
+    window = pad_center(hann_periodic(win_length), n).astype(np.float32)
+    return np.ascontiguousarray((basis.astype(np.float32) * window[None, :])[:, None, :], dtype=np.float32)
+
+
+def window_sumsquare(n_frames: int, hop_length: int, win_length: int, n_fft: int) -> np.ndarray:
+    """``window_sumsquare("hann", n_frames, hop_length, win_length, n_fft, dtype=np.float32)`` (audio_processing.py:7-63) including its
+    arithmetic: an fp32 accumulator; every ``+=`` adds a float64 squared-window value and rounds once to fp32, frames ascending."""
+    n = n_fft + hop_length * (n_frames - 1)
+    x = np.zeros(n, dtype=np.float32)
+    win_sq = pad_center(hann_periodic(win_length) ** 2, n_fft)
+    for i in range(n_frames):
+        sample = i * hop_length
+        x[sample:min(n, sample + n_fft)] += win_sq[:max(0, min(n_fft, n - sample))]
+    return x
 
 
 def hz_to_mel(f):
@@ -90,54 +126,22 @@ def config_struct(filter_length, hop_length, win_length, n_mel, clip_val=CLIP_VA
     return c
 
 
-class TacotronSTFT:
-    """Drop-in for the reference's ``TacotronSTFT(filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin,
-    mel_fmax)`` on the MI355X.  ``mel_basis=`` hands in a filter bank (e.g. librosa's, from a saved ``state_dict()``) in place of the
-    Slaney restatement.
+SPEC_FROM_MEL_SCALING = 1000.0  # the literal of tools.py:22
 
-    ``mel_spectrogram(y, wav_lens=None, max_mel_len=None)`` takes a BATCH of variable-length waves and nothing in it synchronises.
-    Device-side ``wav_lens`` cannot be validated without a read; for them the kernels' rule holds: a length is clamped to
-    ``[0, n]`` and an utterance of ``filter_length / 2`` samples or fewer (which the reference's reflect pad refuses) has zero
-    frames — ``mel`` and ``energy`` all zeros, ``mel_lens`` 0.
 
-    Threading: one instance serves one host thread at a time; several HIP streams from that thread are fine (one workspace each)."""
+def gl_config_struct(filter_length, hop_length, win_length, n_mel, scaling=SPEC_FROM_MEL_SCALING) -> _lib.NsGlConfig:
+    c = _lib.NsGlConfig()
+    c.filter_length, c.hop_length, c.win_length, c.n_mel = int(filter_length), int(hop_length), int(win_length), int(n_mel)
+    c.spec_from_mel_scaling = float(scaling)
+    return c
+
+
+class _DeviceModule:
+    """The nn.Module-shaped part both front-end classes share: eval / train / to / cuda and one workspace per HIP stream.  A subclass
+    provides ``_upload()`` and sets ``_device``, ``_arena``, ``_ws``, ``training``."""
 
     MAX_WORKSPACE_STREAMS = 4
 
-    def __init__(self, filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin, mel_fmax, mel_basis=None):
-        self.filter_length, self.hop_length, self.win_length = int(filter_length), int(hop_length), int(win_length)
-        self.n_mel_channels, self.sampling_rate = int(n_mel_channels), sampling_rate
-        self.mel_fmin, self.mel_fmax = mel_fmin, mel_fmax
-        self._lib = _lib.load()
-        hd = C.c_void_p()
-        _lib.check(self._lib.ns_mel_create(C.byref(config_struct(filter_length, hop_length, win_length, n_mel_channels)), C.byref(hd)), "TacotronSTFT")
-        self._h = hd
-        if mel_basis is None:
-            mel_basis = slaney_mel_basis(sampling_rate, self.filter_length, self.n_mel_channels, mel_fmin, mel_fmax)
-        self._device = None
-        self._arena = None
-        self._ws = OrderedDict()
-        self._sd = None
-        self.mel_lens = None
-        self.training = False
-        self.load_state_dict({"stft_fn.forward_basis": stft_forward_basis(self.filter_length, self.win_length), "mel_basis": mel_basis})
-
-    @classmethod
-    def from_config(cls, preprocess_config: dict, mel_basis=None):
-        """The arguments the reference's preprocessor passes (preprocessor/preprocessor.py:39-47)."""
-        p = preprocess_config["preprocessing"]
-        return cls(p["stft"]["filter_length"], p["stft"]["hop_length"], p["stft"]["win_length"], p["mel"]["n_mel_channels"],
-                   p["audio"]["sampling_rate"], p["mel"]["mel_fmin"], p["mel"]["mel_fmax"], mel_basis=mel_basis)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ns_mel_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    # ---- nn.Module-shaped surface --------------------------------------------------------------
     def eval(self):
         self.training = False
         return self
@@ -162,6 +166,82 @@ class TacotronSTFT:
 
     def cuda(self, device=None):
         return self.to("cuda" if device is None else device)
+
+    def _workspace(self, nbytes: int, stream_handle: int) -> torch.Tensor:
+        w = self._ws.get(stream_handle)
+        if w is None or w.numel() < nbytes:
+            self._ws.pop(stream_handle, None)
+            w = torch.empty(int(nbytes), dtype=torch.uint8, device=self._device)
+            self._ws[stream_handle] = w
+        self._ws.move_to_end(stream_handle)
+        while len(self._ws) > self.MAX_WORKSPACE_STREAMS:
+            self._ws.popitem(last=False)
+        return w
+
+    def release_workspaces(self):
+        self._ws = OrderedDict()
+
+
+class TacotronSTFT(_DeviceModule):
+    """Drop-in for the reference's ``TacotronSTFT(filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin,
+    mel_fmax)`` on the MI355X.  ``mel_basis=`` hands in a filter bank (e.g. librosa's, from a saved ``state_dict()``) in place of the
+    Slaney restatement.
+
+    ``mel_spectrogram(y, wav_lens=None, max_mel_len=None)`` takes a BATCH of variable-length waves and nothing in it synchronises.
+    Device-side ``wav_lens`` cannot be validated without a read; for them the kernels' rule holds: a length is clamped to
+    ``[0, n]`` and an utterance of ``filter_length / 2`` samples or fewer (which the reference's reflect pad refuses) has zero
+    frames — ``mel`` and ``energy`` all zeros, ``mel_lens`` 0.
+
+    ``stft_fn`` is the reference's attribute of that name: an ``audio.STFT`` of the same configuration (and this mel basis), created
+    on first use; ``mel_to_wave`` / ``inv_mel_spec`` run Griffin-Lim through it.
+
+    Threading: one instance serves one host thread at a time; several HIP streams from that thread are fine (one workspace each)."""
+
+    def __init__(self, filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin, mel_fmax, mel_basis=None):
+        self.filter_length, self.hop_length, self.win_length = int(filter_length), int(hop_length), int(win_length)
+        self.n_mel_channels, self.sampling_rate = int(n_mel_channels), sampling_rate
+        self.mel_fmin, self.mel_fmax = mel_fmin, mel_fmax
+        self._lib = _lib.load()
+        hd = C.c_void_p()
+        _lib.check(self._lib.ns_mel_create(C.byref(config_struct(filter_length, hop_length, win_length, n_mel_channels)), C.byref(hd)), "TacotronSTFT")
+        self._h = hd
+        if mel_basis is None:
+            mel_basis = slaney_mel_basis(sampling_rate, self.filter_length, self.n_mel_channels, mel_fmin, mel_fmax)
+        self._device = None
+        self._arena = None
+        self._ws = OrderedDict()
+        self._sd = None
+        self._stft_fn = None
+        self.mel_lens = None
+        self.training = False
+        self.load_state_dict({"stft_fn.forward_basis": stft_forward_basis(self.filter_length, self.win_length), "mel_basis": mel_basis})
+
+    @classmethod
+    def from_config(cls, preprocess_config: dict, mel_basis=None):
+        """The arguments the reference's preprocessor passes (preprocessor/preprocessor.py:39-47)."""
+        p = preprocess_config["preprocessing"]
+        return cls(p["stft"]["filter_length"], p["stft"]["hop_length"], p["stft"]["win_length"], p["mel"]["n_mel_channels"],
+                   p["audio"]["sampling_rate"], p["mel"]["mel_fmin"], p["mel"]["mel_fmax"], mel_basis=mel_basis)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.ns_mel_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    # ---- nn.Module-shaped surface (eval / train / to / cuda: _DeviceModule) ----------------------
+    @property
+    def stft_fn(self) -> "STFT":
+        """The reference's ``TacotronSTFT.stft_fn`` (stft.py:144), with this module's forward basis and mel basis."""
+        if self._stft_fn is None:
+            self._stft_fn = STFT(self.filter_length, self.hop_length, self.win_length, n_mel_channels=self.n_mel_channels,
+                                 mel_basis=self._sd["mel_basis"], sampling_rate=self.sampling_rate)
+            self._stft_fn.load_state_dict({"forward_basis": self._sd["stft_fn.forward_basis"]})
+        if self._device is not None:
+            self._stft_fn.to(self._device)
+        return self._stft_fn
 
     @property
     def mel_basis(self) -> torch.Tensor:
@@ -189,6 +269,7 @@ class TacotronSTFT:
         if errors:
             raise RuntimeError("load_state_dict: " + "; ".join(errors))
         self._sd = new
+        self._stft_fn = None  # rebuilt from the new bases on next use
         if self._device is not None:
             self._upload()
         return [], []
@@ -203,20 +284,6 @@ class TacotronSTFT:
                 _lib.check(self._lib.ns_mel_set_weight(self._h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim), "load_state_dict")
             _lib.check(self._lib.ns_mel_finalize_weights(self._h, _lib.stream_ptr(self._device)), "load_state_dict")
             self._arena = arena
-
-    def _workspace(self, nbytes: int, stream_handle: int) -> torch.Tensor:
-        w = self._ws.get(stream_handle)
-        if w is None or w.numel() < nbytes:
-            self._ws.pop(stream_handle, None)
-            w = torch.empty(int(nbytes), dtype=torch.uint8, device=self._device)
-            self._ws[stream_handle] = w
-        self._ws.move_to_end(stream_handle)
-        while len(self._ws) > self.MAX_WORKSPACE_STREAMS:
-            self._ws.popitem(last=False)
-        return w
-
-    def release_workspaces(self):
-        self._ws = OrderedDict()
 
     # ---- forward -------------------------------------------------------------------------------
     def frames(self, n: int) -> int:
@@ -290,3 +357,279 @@ def get_mel_from_wav(audio, _stft: TacotronSTFT):
     dev = a.device if a.is_cuda else (_stft._device or torch.device("cuda", torch.cuda.current_device()))
     mel, energy = _stft.mel_spectrogram(a.to(device=dev, dtype=torch.float32).unsqueeze(0))
     return mel[0].cpu().numpy().astype(np.float32), energy[0].cpu().numpy().astype(np.float32)
+
+
+# ---- Griffin-Lim: mel -> wave without trained weights (ns_gl_*) ------------------------------------------------------
+def _as_long_lens(lens, B, T, dev, fl, hop, drop, what):
+    """Per-utterance frame counts as a device int64 [B].  Host values are validated (too short for the reflect pad of the loop's
+    transform, stft.py:60-64, or beyond the T frames given: ValueError); device values cannot be without a read and are clamped by the
+    kernels (a too-short utterance then gives a zero wave of length 0)."""
+    if lens is None:
+        lens = [T] * B
+    if torch.is_tensor(lens) and lens.is_cuda:
+        if lens.device != dev:
+            raise RuntimeError(f"{what} is on {lens.device}, the data on {dev}")
+        if lens.dtype != torch.long or tuple(lens.shape) != (B,):
+            raise ValueError(f"device {what} must be int64 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+        return lens.contiguous()
+    host = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
+    if host.dtype.kind not in "iu":
+        raise ValueError(f"{what} must hold integers, got {host.dtype}")
+    if host.shape != (B,):
+        raise ValueError(f"{what} must have shape ({B},), got {host.shape}")
+    for b, v in enumerate(host.tolist()):
+        if v > T:
+            raise ValueError(f"{what}[{b}] = {v} exceeds the {T} frames given")
+        if hop * (v - drop - 1) <= fl // 2:
+            raise ValueError(f"{what}[{b}] = {v}: too short — Griffin-Lim's signal of hop_length * (frames - 1) samples must be longer than "
+                             f"filter_length / 2 = {fl // 2} (the reflect pad, stft.py:60-64)")
+    return torch.as_tensor(host.astype(np.int64)).to(dev)
+
+
+def _check_device_f32(t, what, ndim):
+    if not torch.is_tensor(t):
+        raise ValueError(f"{what} must be a tensor, got {type(t).__name__}")
+    if t.dim() != ndim:
+        raise ValueError(f"{what} must have {ndim} dimensions, got shape {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32, got {t.dtype}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} must live on the MI355X (cuda) device; there is no CPU path")
+
+
+class STFT(_DeviceModule):
+    """The reference's ``STFT(filter_length, hop_length, win_length, window="hann")`` (audio/stft.py:15-127) on the MI355X.
+    ``transform`` and ``inverse`` take and return the reference's layouts, for batches of variable-length utterances (``lens``).
+    ``n_mel_channels`` / ``mel_basis`` (not reference arguments) give the handle the mel basis ``mel_to_wave`` needs;
+    ``TacotronSTFT.stft_fn`` passes its own.  ``state_dict()`` carries the reference module's two buffers.
+
+    DEVIATION: ``inverse_basis`` is the closed form of ``stft_inverse_basis`` rather than LAPACK's ``pinv`` (they differ by ~1e-18)."""
+
+    def __init__(self, filter_length, hop_length, win_length, window="hann", n_mel_channels=None, mel_basis=None, sampling_rate=None):
+        if window != "hann":
+            raise ValueError(f"only the reference's default window 'hann' is built, got {window!r}")
+        self.filter_length, self.hop_length, self.win_length, self.window = int(filter_length), int(hop_length), int(win_length), window
+        self.cutoff = self.filter_length // 2 + 1
+        self.sampling_rate = sampling_rate
+        if (n_mel_channels is None) != (mel_basis is None):
+            raise ValueError("n_mel_channels and mel_basis come together")
+        self._lib = _lib.load()
+        hd = C.c_void_p()
+        # a bare STFT has no mel stage: the smallest legal n_mel, and no mel_basis is ever loaded
+        cfg = gl_config_struct(filter_length, hop_length, win_length, 4 if n_mel_channels is None else n_mel_channels)
+        _lib.check(self._lib.ns_gl_create(C.byref(cfg), C.byref(hd)), "STFT")
+        self._h = hd
+        self.n_mel_channels = None if n_mel_channels is None else int(n_mel_channels)
+        self._mel_basis = None if mel_basis is None else np.ascontiguousarray(mel_basis, dtype=np.float32)
+        if self._mel_basis is not None:
+            shape = (C.c_int64 * 2)(*self._mel_basis.shape) if self._mel_basis.ndim == 2 else None
+            if shape is None or self._lib.ns_gl_check_weight(self._h, b"mel_basis", shape, 2) != 0:
+                raise RuntimeError(f"STFT: mel_basis must be [{self.n_mel_channels}, {self.cutoff}], got {self._mel_basis.shape}")
+        self._device = None
+        self._arena = None
+        self._ws = OrderedDict()
+        self._sd = None
+        self.wave_lens = None
+        self.frame_lens = None
+        self.training = False
+        self.load_state_dict({"forward_basis": stft_forward_basis(self.filter_length, self.win_length),
+                              "inverse_basis": stft_inverse_basis(self.filter_length, self.hop_length, self.win_length)})
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.ns_gl_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @property
+    def forward_basis(self) -> torch.Tensor:
+        return torch.from_numpy(self._sd["forward_basis"].copy())
+
+    @property
+    def inverse_basis(self) -> torch.Tensor:
+        return torch.from_numpy(self._sd["inverse_basis"].copy())
+
+    def state_dict(self):
+        return OrderedDict((k, torch.from_numpy(v.copy())) for k, v in self._sd.items())
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        """Keys of the reference module: ``forward_basis``, ``inverse_basis`` (either may be absent: the current one stays)."""
+        new, errors = dict(self._sd or {}), []
+        for k, t in dict(state_dict).items():
+            a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            shape = (C.c_int64 * a.ndim)(*a.shape)
+            if k not in ("forward_basis", "inverse_basis"):
+                errors.append(f"unexpected key '{k}'")
+            elif self._lib.ns_gl_check_weight(self._h, ("stft_fn." + k).encode(), shape, a.ndim) != 0:
+                errors.append(self._lib.ns_last_error().decode())
+            else:
+                new[k] = a
+        if errors:
+            raise RuntimeError("load_state_dict: " + "; ".join(errors))
+        self._sd = new
+        if self._device is not None:
+            self._upload()
+        return [], []
+
+    def _upload(self):
+        nbytes = self._lib.ns_gl_arena_bytes(self._h)
+        weights = {"stft_fn." + k: a for k, a in self._sd.items()}
+        if self._mel_basis is not None:
+            weights["mel_basis"] = self._mel_basis
+        with torch.cuda.device(self._device):
+            arena = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
+            _lib.check(self._lib.ns_gl_bind_arena(self._h, _lib.ptr(arena), nbytes), "ns_gl_bind_arena")
+            for k, a in weights.items():
+                shape = (C.c_int64 * a.ndim)(*a.shape)
+                _lib.check(self._lib.ns_gl_set_weight(self._h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim), "load_state_dict")
+            _lib.check(self._lib.ns_gl_finalize_weights(self._h, _lib.stream_ptr(self._device)), "load_state_dict")
+            self._arena = arena
+
+    def _ws_for(self, B, T, dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nbytes = int(self._lib.ns_gl_ws_bytes(self._h, B, T))
+        return self._workspace(nbytes, stream), stream
+
+    # ---- the reference's three methods -------------------------------------------------------------
+    def transform(self, input_data, lens=None):
+        """``input_data`` [B, n] fp32 on the GPU, ``lens`` the utterances' sample counts (host or device; default ``n``).  Returns
+        ``(magnitude, phase)`` [B, cutoff, T], ``T = n // hop + 1``, as transpose views of time-major storage; zeros at frames beyond an
+        utterance's own.  No clip (stft.py:52-81)."""
+        _check_device_f32(input_data, "input_data", 2)
+        B, n = int(input_data.shape[0]), int(input_data.shape[1])
+        dev, half = input_data.device, self.filter_length // 2
+        T = n // self.hop_length + 1
+        if lens is None:
+            lens = [n] * B
+        if torch.is_tensor(lens) and lens.is_cuda:
+            if lens.dtype != torch.long or tuple(lens.shape) != (B,) or lens.device != dev:
+                raise ValueError(f"device lens must be int64 [{B}] on {dev}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+            wl = lens.contiguous()
+        else:
+            host = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
+            if host.dtype.kind not in "iu" or host.shape != (B,):
+                raise ValueError(f"lens must be {B} integers, got {host.dtype} {host.shape}")
+            for b, v in enumerate(host.tolist()):
+                if v <= half or v > n:
+                    raise ValueError(f"lens[{b}] = {v}: a signal must be longer than filter_length / 2 = {half} samples (the reflect pad, "
+                                     f"stft.py:60-64) and within the {n} given")
+            wl = torch.as_tensor(host.astype(np.int64)).to(dev)
+        self.to(dev)
+        x = input_data.contiguous()
+        with torch.cuda.device(dev):
+            mag = torch.empty(B, T, self.cutoff, dtype=torch.float32, device=dev)
+            ph = torch.empty(B, T, self.cutoff, dtype=torch.float32, device=dev)
+            if B > 0:
+                ws, stream = self._ws_for(B, T, dev)
+                _lib.check(self._lib.ns_gl_transform(self._h, _lib.ptr(x), n, _lib.ptr(wl), B, n, T, _lib.ptr(mag), _lib.ptr(ph), _lib.ptr(ws),
+                                                     ws.numel(), C.c_void_p(stream)), "ns_gl_transform")
+        return mag.transpose(1, 2), ph.transpose(1, 2)
+
+    def _griffin_lim(self, mag_t, ang_t, lens, n_iters, mel=False):
+        """``mag_t`` time-major magnitudes [B, T, cutoff] (or, ``mel=True``, log-mel [B, T + 1, n_mel]); ``ang_t`` [B, T, cutoff]."""
+        B, T = int(ang_t.shape[0]), int(ang_t.shape[1])
+        dev = ang_t.device
+        self.to(dev)
+        n = self.hop_length * (T - 1)
+        with torch.cuda.device(dev):
+            wave = torch.empty(B, n, dtype=torch.float32, device=dev)
+            wl = torch.empty(B, dtype=torch.long, device=dev)
+            if B > 0:
+                ws, stream = self._ws_for(B, T + 1, dev)
+                fn, Tin = (self._lib.ns_gl_forward, T + 1) if mel else (self._lib.ns_gl_forward_mag, T)
+                _lib.check(fn(self._h, _lib.ptr(mag_t), _lib.ptr(lens), B, Tin, _lib.ptr(ang_t), int(n_iters), _lib.ptr(wave), n, _lib.ptr(wl),
+                              _lib.ptr(ws), ws.numel(), C.c_void_p(stream)), "ns_gl_forward")
+        self.wave_lens = wl
+        return wave
+
+    def inverse(self, magnitude, phase, lens=None):
+        """``magnitude``, ``phase`` [B, cutoff, T] fp32 on the GPU (a transpose view of time-major storage is taken as it is);
+        ``lens`` the utterances' frame counts.  Returns [B, 1, hop * (T - 1)] (stft.py:83-122); ``self.wave_lens``: device lengths."""
+        _check_device_f32(magnitude, "magnitude", 3)
+        _check_device_f32(phase, "phase", 3)
+        if tuple(magnitude.shape) != tuple(phase.shape) or magnitude.shape[1] != self.cutoff:
+            raise ValueError(f"magnitude and phase must both be [B, {self.cutoff}, T], got {tuple(magnitude.shape)} and {tuple(phase.shape)}")
+        B, T = int(magnitude.shape[0]), int(magnitude.shape[2])
+        if T < 2:
+            raise ValueError(f"at least 2 frames are needed, got {T}")
+        fl_lens = _as_long_lens(lens, B, T, magnitude.device, self.filter_length, self.hop_length, 0, "lens")
+        return self._griffin_lim(magnitude.transpose(1, 2).contiguous(), phase.transpose(1, 2).contiguous(), fl_lens, 0).unsqueeze(1)
+
+    def forward(self, input_data):
+        self.magnitude, self.phase = self.transform(input_data)
+        return self.inverse(self.magnitude, self.phase)
+
+    __call__ = forward
+
+
+def random_angles(shape) -> np.ndarray:
+    """The start of audio_processing.py:74-75, drawn on the host exactly as the reference draws it (``np.random.seed`` reproduces it)."""
+    return np.angle(np.exp(2j * np.pi * np.random.rand(*shape))).astype(np.float32)
+
+
+def griffin_lim(magnitudes, stft_fn: STFT, n_iters=30, angles=None, lens=None):
+    """``griffin_lim(magnitudes, stft_fn, n_iters)`` (audio_processing.py:66-82): ``magnitudes`` [B, cutoff, T] fp32 on the GPU ->
+    ``signal`` [B, hop * (T - 1)].  ``angles`` (same shape, device) replaces the host-drawn random start; ``lens``: frame counts.
+    Nothing is read back; the loop evaluates no angle."""
+    _check_device_f32(magnitudes, "magnitudes", 3)
+    if magnitudes.shape[1] != stft_fn.cutoff:
+        raise ValueError(f"magnitudes must be [B, {stft_fn.cutoff}, T], got {tuple(magnitudes.shape)}")
+    B, T = int(magnitudes.shape[0]), int(magnitudes.shape[2])
+    if T < 2:
+        raise ValueError(f"at least 2 frames are needed, got {T}")
+    if n_iters < 0:
+        raise ValueError(f"n_iters must be >= 0, got {n_iters}")
+    dev = magnitudes.device
+    fl_lens = _as_long_lens(lens, B, T, dev, stft_fn.filter_length, stft_fn.hop_length, 0, "lens")
+    if angles is None:
+        ang_t = torch.from_numpy(random_angles(tuple(magnitudes.shape))).transpose(1, 2).contiguous().to(dev)
+    else:
+        _check_device_f32(angles, "angles", 3)
+        if tuple(angles.shape) != tuple(magnitudes.shape):
+            raise ValueError(f"angles must have the shape of magnitudes {tuple(magnitudes.shape)}, got {tuple(angles.shape)}")
+        ang_t = angles.transpose(1, 2).contiguous()
+    return stft_fn._griffin_lim(magnitudes.transpose(1, 2).contiguous(), ang_t, fl_lens, n_iters)
+
+
+def mel_to_wave(mel, _stft: TacotronSTFT, griffin_iters=60, mel_lens=None, angles=None):
+    """The batched, file-less core of ``inv_mel_spec`` (tools.py:18-29): log-mel ``mel`` [B, n_mel, T] on the GPU (the transpose view
+    ``mel_spectrogram`` returns is taken without a copy) -> ``(wave [B, hop * (T - 2)], wave_lens)``.  The last frame of every
+    utterance is dropped, as tools.py:28 does; ``angles`` [B, cutoff, T - 1] (device) replaces the random start."""
+    _check_device_f32(mel, "mel", 3)
+    if mel.shape[1] != _stft.n_mel_channels:
+        raise ValueError(f"mel must be [B, {_stft.n_mel_channels}, T], got {tuple(mel.shape)}")
+    B, T = int(mel.shape[0]), int(mel.shape[2])
+    if T < 3:
+        raise ValueError(f"at least 3 mel frames are needed, got {T}")
+    if griffin_iters < 0:
+        raise ValueError(f"griffin_iters must be >= 0, got {griffin_iters}")
+    dev = mel.device
+    lens = _as_long_lens(mel_lens, B, T, dev, _stft.filter_length, _stft.hop_length, 1, "mel_lens")
+    _stft.to(dev)
+    fn = _stft.stft_fn
+    shape = (B, fn.cutoff, T - 1)
+    if angles is None:
+        ang_t = torch.from_numpy(random_angles(shape)).transpose(1, 2).contiguous().to(dev)
+    else:
+        _check_device_f32(angles, "angles", 3)
+        if tuple(angles.shape) != shape:
+            raise ValueError(f"angles must be {shape}, got {tuple(angles.shape)}")
+        ang_t = angles.transpose(1, 2).contiguous()
+    wave = fn._griffin_lim(mel.transpose(1, 2).contiguous(), ang_t, lens, griffin_iters, mel=True)
+    return wave, fn.wave_lens
+
+
+def inv_mel_spec(mel, out_filename, _stft: TacotronSTFT, griffin_iters=60):
+    """``inv_mel_spec(mel, out_filename, _stft, griffin_iters)`` (tools.py:18-34): one [n_mel, T] log-mel -> a float32 wav file.  One
+    host read at the end.  (The reference reads ``_stft._stft_fn``, which does not exist; ``stft_fn`` is what it means.)"""
+    from scipy.io.wavfile import write
+
+    m = mel if torch.is_tensor(mel) else torch.as_tensor(np.asarray(mel, dtype=np.float32))
+    if m.dim() != 2:
+        raise ValueError(f"mel must be one [n_mel, T] spectrogram, got shape {tuple(m.shape)}")
+    dev = m.device if m.is_cuda else (_stft._device or torch.device("cuda", torch.cuda.current_device()))
+    wave, _ = mel_to_wave(m.to(device=dev, dtype=torch.float32).unsqueeze(0), _stft, griffin_iters)
+    write(out_filename, _stft.sampling_rate, wave[0].cpu().numpy())

@@ -252,12 +252,34 @@ hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st)
 // rows [B, S, hop]: the clipped, reflect-padded wave of utterance b (n_b = clamp(wav_lens[b], 0, n_max) samples) laid out as S * hop
 // consecutive samples; zeros from sample n_b + fl on, all zeros when n_b <= fl / 2.  mel_lens_out (nullable) [B] = n_b / hop + 1 or 0.
 hipError_t launch_mel_frame_rows(const float* wav, long long ld, const long long* wav_lens, int B, long long n_max, int fl, int hop, int S,
-                                 float* rows, long long* mel_lens_out, hipStream_t st);
+                                 float* rows, long long* mel_lens_out, hipStream_t st, bool clip = true);  // clip = false: no clip (Griffin-Lim)
 // packed spectrum [B * S, fl] (column 0 = re_0, 1 = re_{fl/2}, 2k = re_k, 2k + 1 = im_k) -> mel [B, T, n_mel] = log(max(band sums, clip)) (taken in double, rounded once),
 // energy [B, T]; zeros at frames t >= mel_lens[b].  band [n_mel][3] = {first bin, bins, offset into bw}; fl <= MEL_MAX_FILTER.
 constexpr int MEL_MAX_FILTER = 4096;
 hipError_t launch_mel_project(const float* spec, const long long* wav_lens, int B, int S, long long n_max, int T, int fl, int hop, int n_mel,
                               float clip, const int* band, const float* bw, float* mel, float* energy, hipStream_t st);
+// ---- Griffin-Lim mel-to-wave (griffinlim.hip; audio/stft.py:83-122, audio/audio_processing.py:7-82, audio/tools.py:18-34) -------------
+// Every kernel derives an utterance's frame count the same way: Tg_b = clamp(lens[b] - drop, 0, Tg), and 0 when the wave it stands
+// for, hop (Tg_b - 1) samples, is filter_length / 2 or shorter (the reference's reflect pad refuses it).  Packed spectrum rows as in
+// launch_mel_project: column 0 = re_0, 1 = re_{fl/2}, 2k = re_k, 2k + 1 = im_k.
+// mag [B, Tg, fl/2 + 1] = scaling * sum_m expf(mel[b, t, m]) mel_basis[m, k] (m ascending) from mel [B, T_mel, n_mel]; zeros at t >= Tg_b
+hipError_t launch_gl_mel_to_mag(const float* mel, const long long* lens, int drop, int B, int T_mel, int Tg, int fl, int hop, int n_mel,
+                                float scaling, const float* mel_basis, float* mag, hipStream_t st);
+// X [B * Tg, fl] packed = mag (cos, sin)(angles), both [B, Tg, fl/2 + 1]; zero rows at t >= Tg_b
+hipError_t launch_gl_recombine(const float* mag, const float* angles, const long long* lens, int drop, int B, int Tg, int fl, int hop,
+                               float* X, hipStream_t st);
+// X [B * Tg, fl] packed = mag * Y / |Y| per bin from the packed spectrum Y [B * S, fl]; (mag, 0) where Y == 0; zero rows at t >= Tg_b
+hipError_t launch_gl_rephase(const float* Y, const float* mag, const long long* lens, int drop, int B, int Tg, int S, int fl, int hop,
+                             float* X, hipStream_t st);
+// wave [B, ld] from frames [B * Tg, fl]: overlap-add in ascending t, / window_sum (> FLT_MIN; rebuilt per sample from wsq [fl] doubles
+// in the reference's order and rounding), * fl / hop, trimmed by fl / 2; zeros at s >= n_b = hop (Tg_b - 1); wave_lens_out [B] = n_b
+hipError_t launch_gl_overlap_add(const float* frames, const long long* lens, int drop, int B, int Tg, int fl, int hop, const double* wsq,
+                                 float* wave, long long ld, long long* wave_lens_out, hipStream_t st);
+// wave_lens_out [B] = n_b alone
+hipError_t launch_gl_wave_lens(const long long* lens, int drop, int B, int Tg, int fl, int hop, long long* wave_lens_out, hipStream_t st);
+// magnitude, phase [B, T, fl/2 + 1] = sqrtf(re^2 + im^2), atan2f(im, re) of Y [B * S, fl] packed; zeros at t >= n_b / hop + 1 (or n_b <= fl/2)
+hipError_t launch_gl_polar(const float* Y, const long long* wav_lens, long long n_max, int B, int S, int T, int fl, int hop, float* magnitude,
+                           float* phase, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

@@ -10,6 +10,8 @@ namespace ns {
 // One float4 (four consecutive padded samples) per thread; blockIdx.y = utterance.  Padded sample p comes from source sample
 // p - fl/2, mirrored at both ends without repeating the edge sample (torch "reflect", stft.py:60-64).  For p < n + fl and n > fl/2
 // the mirrored index lies in [0, n): left |src| <= fl/2 <= n - 1, right 2(n-1) - src >= n - 1 - fl/2 >= 0.
+// CLIP = false is the Griffin-Lim loop's transform (stft.py:52-81 pads but does not clip; griffinlim_api.hip): pure data movement.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_mel_frame_rows(const float* __restrict__ wav, long long ld, const long long* __restrict__ wav_lens,
                                                         long long n_max, int fl, int hop, long long row_floats, float* __restrict__ rows,
                                                         long long* __restrict__ mel_lens_out) {
@@ -33,7 +35,7 @@ __global__ __launch_bounds__(256) void k_mel_frame_rows(const float* __restrict_
         if (s < 0) s = -s;
         if (s >= n) s = 2 * (n - 1) - s;
         const float x = w[s];
-        v[e] = x < -1.f ? -1.f : (x > 1.f ? 1.f : x);  // torch.clip: a NaN fails both comparisons and stays
+        v[e] = !CLIP ? x : (x < -1.f ? -1.f : (x > 1.f ? 1.f : x));  // torch.clip: a NaN fails both comparisons and stays
       }
     }
   }
@@ -41,14 +43,18 @@ __global__ __launch_bounds__(256) void k_mel_frame_rows(const float* __restrict_
 }
 
 hipError_t launch_mel_frame_rows(const float* wav, long long ld, const long long* wav_lens, int B, long long n_max, int fl, int hop, int S,
-                                 float* rows, long long* mel_lens_out, hipStream_t st) {
+                                 float* rows, long long* mel_lens_out, hipStream_t st, bool clip) {
   if (B <= 0 || S <= 0) return hipSuccess;
   if (B > 65535 || (hop & 3) || (fl & 1)) return hipErrorInvalidValue;
   const long long row_floats = (long long)S * hop;
   const long long blocks = (row_floats / 4 + 255) / 256;
   if (blocks >= (1ll << 31)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_mel_frame_rows, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, st, wav, ld, wav_lens, n_max, fl, hop, row_floats, rows,
-                     mel_lens_out);
+  if (clip)
+    hipLaunchKernelGGL(k_mel_frame_rows<true>, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, st, wav, ld, wav_lens, n_max, fl, hop, row_floats,
+                       rows, mel_lens_out);
+  else
+    hipLaunchKernelGGL(k_mel_frame_rows<false>, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, st, wav, ld, wav_lens, n_max, fl, hop, row_floats,
+                       rows, mel_lens_out);
   return hipGetLastError();
 }
 

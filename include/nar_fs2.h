@@ -642,6 +642,70 @@ int ns_gl_op_frame_rows(ns_gl* h, const float* wav, int64_t ld_wav, const int64_
 int ns_gl_op_step(ns_gl* h, const float* mag, const int64_t* frame_lens, int B, int Tg, float* wave, int64_t ld_wave,
                   int64_t* wave_lens_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ==== Pitch / energy variance targets and dataset statistics (the tail of the reference's Preprocessor.process_utterance and its
+ * build_from_path / remove_outlier / normalize: preprocessor/preprocessor.py:188-227, 61-133, 289-310) ==========================
+ * Handle-less like ns_loss_*: no weights, caller-owned workspace and state, one stream, no host read, no device allocation, no float
+ * atomic; nothing above changes (every other ABI version stays as it is).  Frame-level f0 is an INPUT: pitch extraction, resampling,
+ * TextGrid parsing and file I/O stay outside.  Per utterance b, with Ls = clamp(src_lens[b], 0, L) and d_i = durations[b, i]:
+ *   n_b = min(T, sum_{i < Ls} max(d_i, 0))  -> frame_lens[b]                                      preprocessor.py:188,194-195
+ *   valid[b] = more than one frame t < n_b has pitch != 0; an invalid utterance gets all-zero targets     preprocessor.py:189-190
+ *   frame_level feature: the values at t < n_b, zeros behind (frame-level pitch is NOT interpolated)      preprocessor.py:197,218
+ *   phoneme_level pitch: the contour interpolated linearly over unvoiced frames in float64 — slope * (t - x0) + y0 with
+ *     slope = (y1 - y0) / (x1 - x0) between voiced neighbours x0 < t < x1, the first / last voiced value outside them — then
+ *     the float64 mean over frames [c_i - d_i, c_i) within [0, n_b), c the inclusive prefix sum; 0 where d_i <= 0 or the
+ *     intersection is empty; rounded once to fp32; zeros at i >= Ls                                       preprocessor.py:199-216
+ *   phoneme_level energy: the same mean without the interpolation                                         preprocessor.py:219-227
+ * Padded input positions (frames >= n_b, phonemes >= Ls) are selected away, never multiplied: they may hold NaN.  Every word of
+ * every output is written.  Equal inputs give equal bits: every reduction order is a function of the shapes alone.
+ * DEVIATION: the reference averages IN PLACE (pitch[i] = np.mean(pitch[pos:pos+d]), preprocessor.py:208-216, 219-227): with zero
+ * durations early in an utterance (sum_{j<i} d_j < i for a phoneme with d_i > 0) it reads values it has already overwritten, and
+ * it raises IndexError once i >= sum(d).  Here every mean is over the ORIGINAL frames — the function the loop intends; the two are
+ * identical on every utterance with sum_{j<i} d_j >= i for all i with d_i > 0 and sum(d) >= Ls. */
+#define NS_VT_ABI_VERSION 1
+#define NS_VT_SORT_CAPACITY 8192 /* values of one (utterance, feature) that ns_vt_fit can sort in LDS */
+int ns_vt_abi_version(void);
+/* Device memory, 80 bytes, 8-byte aligned: the running statistics of the outlier-filtered RAW targets (float64 count / mean / M2,
+ * index 0 pitch, 1 energy) and the extrema of the NORMALISED targets.  ns_vt_state_init writes count = mean = M2 = 0,
+ * min = DBL_MAX, max = -DBL_MAX (preprocessor.py:61-62, 300-301) on `stream`. */
+typedef struct ns_vt_state {
+  double count[2], mean[2], m2[2], min[2], max[2];
+} ns_vt_state;
+typedef struct ns_vt_args {
+  int32_t B, L, T;
+  int32_t pitch_frame_level, energy_frame_level;      /* preprocessing.{pitch,energy}.feature == "frame_level" (preprocessor.py:33-38) */
+  int32_t pitch_normalization, energy_normalization;  /* preprocessing.{pitch,energy}.normalization (preprocessor.py:40-41,93-105) */
+  int64_t durations_stride;                           /* elements between rows of durations: L' >= L */
+  const float* pitch;                                 /* [B, T] frame f0, 0 = unvoiced; ns_vt_targets only      preprocessor.py:181-188 */
+  const float* energy;                                /* [B, T] frame energy; ns_vt_targets only                preprocessor.py:193-195 */
+  const int64_t* durations;                           /* [B, L'] int64; ns_vt_targets only                      preprocessor.py:163,188 */
+  const int64_t* src_lens;                            /* [B] int64 */
+  float* pitch_targets;                               /* [B, T] or [B, L]: written by targets, read by fit, rewritten by normalize */
+  float* energy_targets;                              /* [B, T] or [B, L] */
+  int64_t* frame_lens;                                /* [B]: written by targets, read by fit and normalize */
+  uint8_t* valid;                                     /* [B]: written by targets, read by fit; normalize accepts NULL = all valid */
+} ns_vt_args;
+/* Bytes of the workspace any of the three calls below needs at (B, L, T); positive, monotone.  Needs no initialisation. */
+size_t ns_vt_ws_bytes(int B, int L, int T);
+int ns_vt_state_init(ns_vt_state* state, void* stream);
+/* pitch, energy, durations -> pitch_targets, energy_targets, frame_lens, valid (raw, not normalised).  One launch, one workgroup per
+ * (utterance, feature).  Validation happens before any HIP call: null pointers (of what the shape makes non-empty), negative sizes,
+ * durations_stride < L and ws_bytes < ns_vt_ws_bytes(B, L, T) return nonzero with ns_last_error().  B, L or T == 0 is legal. */
+int ns_vt_targets(const ns_vt_args* a, void* ws, size_t ws_bytes, void* stream);
+/* remove_outlier + StandardScaler.partial_fit (preprocessor.py:84-87, 289-297) of one batch of raw targets: per (valid utterance,
+ * feature) its n = src_lens[b] (phoneme_level; the zeros of d_i = 0 phonemes included) or frame_lens[b] values are sorted in LDS,
+ * p25 / p75 are numpy's default linear percentile at q / 100 * (n - 1) in float64, the values with lower < v < upper (strict),
+ * lower = p25 - 1.5 (p75 - p25), upper = p75 + 1.5 (p75 - p25), give (count, mean, M2) in float64 in the utterance's workspace slot;
+ * a second one-workgroup launch merges the slots in utterance order into `state` (Chan's update).  n = 0 and n = 1 contribute
+ * nothing.  The sorted dimension (T at frame_level, L at phoneme_level) above NS_VT_SORT_CAPACITY is refused here, on the host. */
+int ns_vt_fit(const ns_vt_args* a, ns_vt_state* state, void* ws, size_t ws_bytes, void* stream);
+/* y = (float)(((double)x - mean) / std) in place on the selected positions (valid utterance, position < n), padding stays 0;
+ * mean / std = sqrt(M2 / count) from `state` (StandardScaler.mean_ / scale_, the population std; 0 / 1 when the feature's
+ * normalization flag is off, when nothing was fitted, or std == 0), and the min / max of the float64 quotients over ALL selected
+ * positions — not the outlier-filtered ones — folded into `state` by per-workgroup slots and a fixed-order merge
+ * (preprocessor.py:93-112, 299-310).  A NULL `valid` takes every utterance as valid: the zero rows of one that ns_vt_targets dropped
+ * become -mean / std at positions < n and enter min / max, so pass the flag unless the batch holds no dropped utterance. */
+int ns_vt_normalize(const ns_vt_args* a, ns_vt_state* state, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

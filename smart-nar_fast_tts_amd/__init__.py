@@ -4,8 +4,8 @@
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
 when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
-``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec"]
+``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets"]
 
 
 def __getattr__(name):
@@ -17,4 +17,8 @@ def __getattr__(name):
         from . import audio
 
         return getattr(audio, name)
+    if name == "VarianceTargets":
+        from . import targets
+
+        return targets.VarianceTargets
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

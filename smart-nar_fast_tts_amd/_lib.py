@@ -33,6 +33,18 @@ class NsLossArgs(C.Structure):
                 + [("attn", C.c_void_p * 4)])
 
 
+class NsVtState(C.Structure):
+    """``ns_vt_state`` (include/nar_fs2.h): index 0 pitch, 1 energy."""
+    _fields_ = [(n, C.c_double * 2) for n in ("count", "mean", "m2", "min", "max")]
+
+
+class NsVtArgs(C.Structure):
+    """``ns_vt_args`` (include/nar_fs2.h): sizes, the feature levels and normalization flags, the stride, then the device pointers."""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "L", "T", "pitch_frame_level", "energy_frame_level", "pitch_normalization", "energy_normalization")]
+                + [("durations_stride", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("pitch", "energy", "durations", "src_lens", "pitch_targets", "energy_targets", "frame_lens", "valid")])
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -170,6 +182,13 @@ SIGNATURES = {
     "ns_gl_op_inverse": (_I, [_P, _P, _P, _I, _I, _P, C.c_int64, _P, _P, _Z, _P]),
     "ns_gl_op_frame_rows": (_I, [_P, _P, C.c_int64, _P, _I, C.c_int64, _I, _P, _P]),
     "ns_gl_op_step": (_I, [_P, _P, _P, _I, _I, _P, C.c_int64, _P, _P, _Z, _P]),
+    # variance targets and dataset statistics (targets.VarianceTargets; handle-less)
+    "ns_vt_abi_version": (_I, []),
+    "ns_vt_ws_bytes": (_Z, [_I, _I, _I]),
+    "ns_vt_state_init": (_I, [_P, _P]),
+    "ns_vt_targets": (_I, [C.POINTER(NsVtArgs), _P, _Z, _P]),
+    "ns_vt_fit": (_I, [C.POINTER(NsVtArgs), _P, _P, _Z, _P]),
+    "ns_vt_normalize": (_I, [C.POINTER(NsVtArgs), _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

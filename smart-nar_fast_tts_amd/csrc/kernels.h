@@ -280,6 +280,26 @@ hipError_t launch_gl_wave_lens(const long long* lens, int drop, int B, int Tg, i
 // magnitude, phase [B, T, fl/2 + 1] = sqrtf(re^2 + im^2), atan2f(im, re) of Y [B * S, fl] packed; zeros at t >= n_b / hop + 1 (or n_b <= fl/2)
 hipError_t launch_gl_polar(const float* Y, const long long* wav_lens, long long n_max, int B, int S, int T, int fl, int hop, float* magnitude,
                            float* phase, hipStream_t st);
+// ---- variance targets and dataset statistics (vartargets.hip; preprocessor/preprocessor.py:188-227, 61-133, 289-310) -----------
+// The device-side mirror of ns_vt_args / ns_vt_state (include/nar_fs2.h).
+struct VtArgs {
+  int B, L, T, pitch_frame_level, energy_frame_level, pitch_normalization, energy_normalization;
+  long long durations_stride;
+  const float *pitch, *energy;
+  const long long *durations, *src_lens;
+  float *pitch_targets, *energy_targets;
+  long long* frame_lens;
+  uint8_t* valid;
+};
+struct VtState { double count[2], mean[2], m2[2], min[2], max[2]; };
+constexpr int VT_SORT_CAPACITY = 8192;  // floats of one (utterance, feature) sorted in LDS (32 KiB)
+constexpr int VT_SLOT_BYTES = 32;       // fit: count, mean, M2 (+ pad); normalize: min, max (+ pad) — doubles
+// workspace = [B * T] float64 contour + [B * T] int32 next-voiced index (targets), or 2 * B slots (fit, normalize)
+size_t vt_ws_bytes(int B, int L, int T);
+hipError_t launch_vt_state_init(VtState* state, hipStream_t st);
+hipError_t launch_vt_targets(const VtArgs& a, void* ws, hipStream_t st);
+hipError_t launch_vt_fit(const VtArgs& a, VtState* state, void* ws, hipStream_t st);
+hipError_t launch_vt_normalize(const VtArgs& a, VtState* state, void* ws, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

@@ -706,6 +706,77 @@ int ns_vt_fit(const ns_vt_args* a, ns_vt_state* state, void* ws, size_t ws_bytes
  * become -mean / std at positions < n and enter min / max, so pass the flag unless the batch holds no dropped utterance. */
 int ns_vt_normalize(const ns_vt_args* a, ns_vt_state* state, void* ws, size_t ws_bytes, void* stream);
 
+/* ==== The optimiser half of the training step: clip_grad_norm_, ScheduledOptim.step_and_update_lr's Adam.step() and zero_grad()
+ * (train.py:91-95; model/optimizer.py:10-15,24,28) =================================================================================
+ * Handle-less like ns_loss_* and ns_vt_*: the chunk table, the workspace, the two state arenas and the norm record are caller-owned;
+ * one stream, no device allocation, no host read, no float atomic; nothing above changes (every other ABI version stays as it is).
+ * The Noam warm-up / anneal schedule (optimizer.py:33-51) is host arithmetic: lr is an argument.  fp32 parameters only, one group,
+ * no amsgrad, no maximize.  Per element, in the order of torch/optim/adam.py _single_tensor_adam (non-capturable branch), with
+ * t = global_step - lag[tensor] the tensor's own step count and every product rounded before it is added:
+ *   g' = g * clip_coef                        (fuse_clip; the coefficient is read from the device record)      train.py:91
+ *   g' = g' + weight_decay * p                (weight_decay != 0)                                              optimizer.py:14
+ *   m  = m + (1 - beta1) * (g' - m)           exp_avg.lerp_                                                    optimizer.py:24
+ *   v  = v * beta2 + ((1 - beta2) * g') * g'  exp_avg_sq.mul_().addcmul_()
+ *   p  = p - ((lr / (1 - beta1^t)) * m) / (sqrtf(v) / sqrt(1 - beta2^t) + eps)     true division, float64 bias corrections
+ *   g  = 0                                    (zero_grads)                                                     train.py:95
+ * The parameter list is cut into chunks of NS_OPT_CHUNK elements, tensor i owning max(1, ceil(numel_i / NS_OPT_CHUNK)) of them; a
+ * workgroup finds a chunk's tensor from the per-tensor prefix `chunk_begin`, so no launch depends on the number of tensors.  p, g, m
+ * and v move as 16-byte vectors where the tensor's pointer is 16-byte aligned and element by element otherwise (the same elements
+ * per thread either way: alignment changes no bit).  Equal inputs give equal bits: the norm's reduction order is a function of the
+ * sizes alone. */
+#define NS_OPT_ABI_VERSION 1
+#define NS_OPT_CHUNK 4096
+int ns_opt_abi_version(void);
+/* One row of the chunk table (40 bytes).  Built on the host by ns_opt_build_table, uploaded by the caller. */
+typedef struct ns_opt_tensor {
+  float* param;           /* device, 4-byte aligned; a view such as base[1:] is fine */
+  float* grad;            /* device; NULL = skipped, as torch skips p.grad is None (no norm share, no update, no step) */
+  int64_t numel;
+  int64_t state_offset;   /* floats into exp_avg / exp_avg_sq; every tensor is padded to a multiple of 4 */
+  int32_t lag;            /* global_step - lag is this tensor's `step` (torch keeps it per parameter); lag < global_step */
+  int32_t chunk_begin;    /* chunks of the tensors in front */
+} ns_opt_tensor;
+typedef struct ns_opt_plan {
+  int64_t n_tensors, n_chunks;
+  int64_t table_bytes;    /* n_tensors rows */
+  int64_t ws_bytes;       /* one float64 slot per chunk; needs no initialisation */
+  int64_t state_floats;   /* of EACH of exp_avg and exp_avg_sq; zero them before the first step */
+} ns_opt_plan;
+/* Device memory, 16 bytes, 8-byte aligned, written by ns_opt_grad_norm: the float64 2-norm of all gradients, its fp32 rounding (what
+ * clip_grad_norm_ returns) and min(1, max_norm / (total_norm + 1e-6)) evaluated in fp32 as torch evaluates it (a NaN norm gives a
+ * NaN coefficient). */
+typedef struct ns_opt_record {
+  double norm64;
+  float total_norm, clip_coef;
+} ns_opt_record;
+typedef struct ns_opt_hyper {
+  double lr, beta1, beta2, eps, weight_decay;   /* param_groups[0] of torch.optim.Adam (optimizer.py:10-15,50-51) */
+  int64_t global_step;                          /* >= 1: the number of this step */
+  int32_t fuse_clip;                            /* multiply g by the record's clip_coef first (train.py:91) */
+  int32_t zero_grads;                           /* write g = 0 behind the update (train.py:95) */
+} ns_opt_hyper;
+/* Host only.  Sizes for n_tensors >= 1 tensors of numels[i] >= 0 elements: all positive, monotone in every size. */
+int ns_opt_plan_sizes(const int64_t* numels, int n_tensors, ns_opt_plan* out);
+/* Host only.  Writes plan.n_tensors rows into table_host (8-byte aligned, >= plan.table_bytes); lags NULL = all zero.  A tensor of
+ * zero elements is stored as skipped. */
+int ns_opt_build_table(const int64_t* numels, float* const* params, float* const* grads, const int32_t* lags, int n_tensors,
+                       void* table_host, size_t table_bytes);
+/* The four launching calls take the planner's output and the DEVICE copy of the table.  Before any HIP call they return nonzero with
+ * ns_last_error() on null pointers, a plan that ns_opt_plan_sizes cannot have produced (n_tensors == 0 included), a table, workspace
+ * or arena smaller than the plan says, negative sizes, betas outside [0, 1), eps < 0, lr < 0, weight_decay < 0, global_step < 1.
+ * nn.utils.clip_grad_norm_ (train.py:91), first half: two launches; writes `record`. */
+int ns_opt_grad_norm(const ns_opt_plan* plan, const void* table, size_t table_bytes, float max_norm, void* ws, size_t ws_bytes,
+                     ns_opt_record* record, void* stream);
+/* clip_grad_norm_, second half: g *= record->clip_coef in place, also when the coefficient is 1 (as torch does).  One launch. */
+int ns_opt_scale_grads(const ns_opt_plan* plan, const void* table, size_t table_bytes, const ns_opt_record* record, void* stream);
+/* optimizer.step() (optimizer.py:24), one launch.  exp_avg / exp_avg_sq: 16-byte aligned arenas of state_floats floats each.  record
+ * may be NULL unless hyper->fuse_clip.  With fuse_clip the result is bitwise that of ns_opt_scale_grads followed by this call
+ * without it (the gradients themselves stay unscaled). */
+int ns_opt_adam_step(const ns_opt_plan* plan, const void* table, size_t table_bytes, const ns_opt_hyper* hyper, float* exp_avg,
+                     float* exp_avg_sq, int64_t state_floats, const ns_opt_record* record, void* stream);
+/* optimizer.zero_grad() with set_to_none=False (optimizer.py:28, the torch default of the reference's day).  One launch. */
+int ns_opt_zero_grads(const ns_opt_plan* plan, const void* table, size_t table_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

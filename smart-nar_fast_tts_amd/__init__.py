@@ -4,8 +4,8 @@
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
 when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
-``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets"]
+``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim"]
 
 
 def __getattr__(name):
@@ -21,4 +21,8 @@ def __getattr__(name):
         from . import targets
 
         return targets.VarianceTargets
+    if name == "ScheduledOptim":
+        from . import optim
+
+        return optim.ScheduledOptim
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -45,6 +45,26 @@ class NsVtArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("pitch", "energy", "durations", "src_lens", "pitch_targets", "energy_targets", "frame_lens", "valid")])
 
 
+class NsOptTensor(C.Structure):
+    """``ns_opt_tensor`` (include/nar_fs2.h): one row of the chunk table."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("numel", C.c_int64), ("state_offset", C.c_int64), ("lag", C.c_int32), ("chunk_begin", C.c_int32)]
+
+
+class NsOptPlan(C.Structure):
+    """``ns_opt_plan`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int64) for n in ("n_tensors", "n_chunks", "table_bytes", "ws_bytes", "state_floats")]
+
+
+class NsOptRecord(C.Structure):
+    """``ns_opt_record`` (include/nar_fs2.h)."""
+    _fields_ = [("norm64", C.c_double), ("total_norm", C.c_float), ("clip_coef", C.c_float)]
+
+
+class NsOptHyper(C.Structure):
+    """``ns_opt_hyper`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("global_step", C.c_int64), ("fuse_clip", C.c_int32), ("zero_grads", C.c_int32)]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -189,6 +209,14 @@ SIGNATURES = {
     "ns_vt_targets": (_I, [C.POINTER(NsVtArgs), _P, _Z, _P]),
     "ns_vt_fit": (_I, [C.POINTER(NsVtArgs), _P, _P, _Z, _P]),
     "ns_vt_normalize": (_I, [C.POINTER(NsVtArgs), _P, _P, _Z, _P]),
+    # clip_grad_norm_ + Adam + zero_grad (optim.Adam, optim.ScheduledOptim; handle-less)
+    "ns_opt_abi_version": (_I, []),
+    "ns_opt_plan_sizes": (_I, [C.POINTER(C.c_int64), _I, C.POINTER(NsOptPlan)]),
+    "ns_opt_build_table": (_I, [C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32), _I, _P, _Z]),
+    "ns_opt_grad_norm": (_I, [C.POINTER(NsOptPlan), _P, _Z, _F, _P, _Z, _P, _P]),
+    "ns_opt_scale_grads": (_I, [C.POINTER(NsOptPlan), _P, _Z, _P, _P]),
+    "ns_opt_adam_step": (_I, [C.POINTER(NsOptPlan), _P, _Z, C.POINTER(NsOptHyper), _P, _P, C.c_int64, _P, _P]),
+    "ns_opt_zero_grads": (_I, [C.POINTER(NsOptPlan), _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

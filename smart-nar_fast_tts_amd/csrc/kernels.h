@@ -300,6 +300,26 @@ hipError_t launch_vt_state_init(VtState* state, hipStream_t st);
 hipError_t launch_vt_targets(const VtArgs& a, void* ws, hipStream_t st);
 hipError_t launch_vt_fit(const VtArgs& a, VtState* state, void* ws, hipStream_t st);
 hipError_t launch_vt_normalize(const VtArgs& a, VtState* state, void* ws, hipStream_t st);
+// ---- ScheduledOptim's training-step tail (optim.hip; model/optimizer.py:10-15,24,28 and train.py:91-95) -------------------------
+// The device-side mirrors of ns_opt_tensor / ns_opt_record / ns_opt_hyper (include/nar_fs2.h).
+struct OptTensor {
+  float* p; float* g;      // g == nullptr: skipped, as torch skips p.grad is None
+  long long numel;
+  long long state_off;     // floats into exp_avg / exp_avg_sq, a multiple of 4
+  int lag;                 // the tensor's own step count is global_step - lag
+  int chunk_begin;         // chunks of the tensors before this one; every tensor owns max(1, ceil(numel / OPT_CHUNK)) chunks
+};
+struct OptRecord { double norm64; float total_norm; float clip_coef; };
+struct OptHyper { double lr, beta1, beta2, eps, weight_decay; long long global_step; int fuse_clip, zero_grads; };
+constexpr int OPT_THREADS = 256;
+constexpr int OPT_CHUNK = 4096;      // elements per chunk: four 16-byte groups per thread
+constexpr int OPT_MAX_GRID = 2048;   // 256 CUs x 8 workgroups; the chunks beyond are grid-strided
+// slots [n_chunks] float64, uninitialised; record written by the second launch
+hipError_t launch_opt_grad_norm(const OptTensor* table, int n_tensors, int n_chunks, float max_norm, double* slots, OptRecord* record, hipStream_t st);
+hipError_t launch_opt_scale(const OptTensor* table, int n_tensors, int n_chunks, const OptRecord* record, hipStream_t st);
+hipError_t launch_opt_adam(const OptTensor* table, int n_tensors, int n_chunks, const OptHyper& h, float* exp_avg, float* exp_avg_sq,
+                           const OptRecord* record, hipStream_t st);
+hipError_t launch_opt_zero(const OptTensor* table, int n_tensors, int n_chunks, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

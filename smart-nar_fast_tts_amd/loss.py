@@ -1,6 +1,7 @@
 """Validation loss of a teacher-forced batch: the reference's ``FastSpeech2Loss`` (model/loss.py:149-250) as two HIP launches
 (csrc/loss.hip; ``ns_loss_*`` in include/nar_fs2.h), and the arithmetic of the ``evaluate`` module the reference imports but does
-not ship (train.py:16).  The forward VALUE in ``eval()`` only: no backward, no optimiser."""
+not ship (train.py:16).  The forward VALUE in ``eval()`` only: no backward, and no optimiser here — the optimiser half of the
+training step (clip, Adam, the schedule) is ``optim.py``, which acts on gradients some other backward pass has produced."""
 from __future__ import annotations
 
 import contextlib

@@ -777,6 +777,43 @@ int ns_opt_adam_step(const ns_opt_plan* plan, const void* table, size_t table_by
 /* optimizer.zero_grad() with set_to_none=False (optimizer.py:28, the torch default of the reference's day).  One launch. */
 int ns_opt_zero_grads(const ns_opt_plan* plan, const void* table, size_t table_bytes, void* stream);
 
+/* ==== Training loss: the value AND the backward of the reference's FastSpeech2Loss (train.py:83-88, model/loss.py:149-250) ==========
+ * Handle-less like ns_loss_*, whose argument block it shares; nothing above changes (NS_LOSS_ABI_VERSION and every other ABI version
+ * stay as they are).  The forward is ns_loss_forward — the same two launches, the same seven bits — which also leaves the three counts
+ * its means divide by in a small caller-owned device record.  The backward is one launch: for grad_output g (7 device floats, in the
+ * order of out7) it writes the gradient of sum_i g[i] * out7[i] with respect to each prediction, contiguous and shaped like it:
+ *   d_mel, d_postnet   (g[0] + g[i]) / (n_mel * n_frames) * sign(pred - target) on the frames with mel_masks == 0, sign(0) = 0
+ *   d_pitch, d_energy  2 * (g[0] + g[i]) / count * (pred - target) on the unmasked frames (frame_level) or phonemes (phoneme_level)
+ *   d_log_d            2 * (g[0] + g[5]) / n_phonemes * (log_d - log((float)d_targets + 1.0f)) on the phonemes with src_masks == 0; the
+ *                      logarithm of that fp32 argument is taken in float64 and rounded to fp32 once
+ *   d_attn[k]          10 * (g[0] + g[6]) / n_attn * W[b, t, l] on head 0 at t < olen_b, l < ilen_b — the same for k = 0..3
+ * and +0.0f everywhere else, all of heads >= 1 included.  A masked-out element is selected away, never multiplied by zero: it is not
+ * read, so NaN behind a mask does not reach a gradient, and a part with an empty selection (value NaN) has an all-zero gradient, as
+ * masked_select's backward gives.  Targets, masks and lengths get no gradient.  g and the record are read on the device; the
+ * coefficients are formed in float64 and rounded once.  No atomic, no workspace, no host read; equal inputs give equal bits. */
+#define NS_LOSSG_ABI_VERSION 1
+#define NS_LOSSG_RECORD_BYTES 32   /* int64 n_frames, n_phonemes, n_attn, 0; device memory, 8-byte aligned, written by ns_lossg_forward */
+int ns_lossg_abi_version(void);
+size_t ns_lossg_record_bytes(void);
+/* The nine outputs of ns_lossg_backward: device pointers, 16-byte aligned, each as large as its prediction.  NULL = not wanted: that
+ * tensor is neither computed nor written, and a segment of the work list none of whose tensors is wanted launches no workgroup. */
+typedef struct ns_lossg_grads {
+  float* mel;                                         /* [B, T, n_mel] */
+  float* postnet;                                     /* [B, T, n_mel] */
+  float* pitch;                                       /* [B, T] or [B, L] */
+  float* energy;                                      /* [B, T] or [B, L] */
+  float* log_d;                                       /* [B, L] */
+  float* attn[4];                                     /* [B, H, T, L] each: every head is written, heads >= 1 with zeros */
+} ns_lossg_grads;
+/* ns_loss_forward with the record: the same validation, the same two launches, out7 bit for bit; `record` (NS_LOSSG_RECORD_BYTES,
+ * 8-byte aligned) is written by the second launch.  The record, not the workspace, carries the counts to the backward, so later loss
+ * calls that reuse the workspace do not disturb it. */
+int ns_lossg_forward(const ns_loss_args* a, void* ws, size_t ws_bytes, float* out7, void* record, void* stream);
+/* One launch on `stream`.  `a` as given to ns_lossg_forward (validated the same way, and B * H * T < 2^31), `record` as it wrote it,
+ * g7 = 7 device floats, 4-byte aligned.  Returns nonzero with ns_last_error(), before any HIP call, on a null a / record / g7 / grads
+ * and on an output that is not 16-byte aligned.  With every output NULL nothing is launched. */
+int ns_lossg_backward(const ns_loss_args* a, const void* record, const float* g7, const ns_lossg_grads* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

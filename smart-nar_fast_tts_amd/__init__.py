@@ -3,13 +3,13 @@
 
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
-when it is missing.  ``FastSpeech2Loss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
+when it is missing.  ``FastSpeech2Loss``, ``FastSpeech2TrainingLoss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
 ``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim"]
+__all__ = ["workload", "FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim"]
 
 
 def __getattr__(name):
-    if name in ("FastSpeech2Loss", "evaluate"):
+    if name in ("FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate"):
         from . import loss
 
         return getattr(loss, name)

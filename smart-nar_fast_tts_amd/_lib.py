@@ -33,6 +33,11 @@ class NsLossArgs(C.Structure):
                 + [("attn", C.c_void_p * 4)])
 
 
+class NsLossgGrads(C.Structure):
+    """``ns_lossg_grads`` (include/nar_fs2.h): the nine nullable outputs of ``ns_lossg_backward``."""
+    _fields_ = [(n, C.c_void_p) for n in ("mel", "postnet", "pitch", "energy", "log_d")] + [("attn", C.c_void_p * 4)]
+
+
 class NsVtState(C.Structure):
     """``ns_vt_state`` (include/nar_fs2.h): index 0 pitch, 1 energy."""
     _fields_ = [(n, C.c_double * 2) for n in ("count", "mean", "m2", "min", "max")]
@@ -217,6 +222,11 @@ SIGNATURES = {
     "ns_opt_scale_grads": (_I, [C.POINTER(NsOptPlan), _P, _Z, _P, _P]),
     "ns_opt_adam_step": (_I, [C.POINTER(NsOptPlan), _P, _Z, C.POINTER(NsOptHyper), _P, _P, C.c_int64, _P, _P]),
     "ns_opt_zero_grads": (_I, [C.POINTER(NsOptPlan), _P, _Z, _P]),
+    # training loss: value with the record of its counts, and the backward (loss.FastSpeech2TrainingLoss; handle-less)
+    "ns_lossg_abi_version": (_I, []),
+    "ns_lossg_record_bytes": (_Z, []),
+    "ns_lossg_forward": (_I, [C.POINTER(NsLossArgs), _P, _Z, _P, _P, _P]),
+    "ns_lossg_backward": (_I, [C.POINTER(NsLossArgs), _P, _P, C.POINTER(NsLossgGrads), _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -247,7 +247,21 @@ constexpr int LOSS_SLOT_SUMS = 6, LOSS_SLOT_WORDS = 8, LOSS_SLOT_BYTES = 64;  //
 // slots of the partial workspace = workgroups of k_loss_partial; a function of (B, L, T) alone
 long long loss_slots(int B, int L, int T, int* n_frame_wgs, int* n_phoneme_wgs);
 // requires what ns_loss_forward (loss_api.hip) validates; ws >= loss_slots(...) * LOSS_SLOT_BYTES, uninitialised
-hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st);
+// record (nullable): LOSSG_RECORD_WORDS int64 written by k_loss_final next to out7 — the three counts the backward divides by
+hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st, long long* record = nullptr);
+// ---- FastSpeech2Loss backward (lossgrad.hip): the gradient of sum_i g[i] * out7[i] with respect to the nine predictions.
+constexpr int LOSSG_RECORD_WORDS = 4, LOSSG_RECORD_BYTES = 32;  // n_frames, n_phonemes, n_attn, 0 (int64)
+struct LossGrads {
+  float *mel, *postnet, *pitch, *energy, *log_d;  // shaped like the predictions, contiguous, 16-byte aligned; nullptr = not written
+  float* attn[4];                                  // [B, H, T, L] each
+};
+constexpr int LOSSG_FRAME_ROWS = 64;       // frame rows per workgroup (n_mel / 4 vectors each)
+constexpr int LOSSG_PHONEME_ROWS = 1024;   // phoneme rows per workgroup: one 16-byte group per thread
+constexpr int LOSSG_ATTN_ELEMS = 4096;     // map elements per workgroup: four 16-byte groups per thread, four maps
+// workgroups of k_lossg_backward; a segment none of whose outputs is wanted has none
+long long lossg_wgs(const LossArgs& a, const LossGrads& d, int* n_frame_wgs, int* n_phoneme_wgs);
+// requires what ns_lossg_backward (lossgrad_api.hip) validates; record and g7 are read on the device only
+hipError_t launch_lossg(const LossArgs& a, const long long* record, const float* g7, const LossGrads& d, hipStream_t st);
 // ---- wave-to-mel front end (melfront.hip; audio/stft.py:52-81,159-178, audio/tools.py:8-15) ----------------------------------
 // rows [B, S, hop]: the clipped, reflect-padded wave of utterance b (n_b = clamp(wav_lens[b], 0, n_max) samples) laid out as S * hop
 // consecutive samples; zeros from sample n_b + fl on, all zeros when n_b <= fl / 2.  mel_lens_out (nullable) [B] = n_b / hop + 1 or 0.

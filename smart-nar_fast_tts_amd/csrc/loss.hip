@@ -3,12 +3,14 @@
 //   k_loss_partial  one launch over a flat work list of three segments — frame rows, phoneme rows, guided-attention row blocks; a
 //                   workgroup owns a fixed slice of one segment and writes its partial sums into its own workspace slot
 //   k_loss_final    one workgroup: sums the slots in a fixed order in float64, derives the counts as int64, divides, writes 7 floats
+//                   (and, where the caller passes a record, the three counts: what the backward of lossgrad.hip divides by)
 // Selection, not multiplication: a masked-out element never enters the arithmetic (`cond ? term : 0`).  Padded positions may
 // hold NaN (an utterance with src_lens == 0); masked_select drops them, 0 * NaN would not.
 // Reduction order: per-thread fp32 over a short fixed run, wave64 shuffle tree in fp32, the four waves of a workgroup added in
 // wave order in float64.  Which element lands in which (thread, slot) depends on (B, L, T, H, n_mel, feature levels) only — not on
 // pointer alignment, not on the stream, not on what the workspace held — so equal inputs give equal bits.
 #include "kernels.h"
+#include "loss_guide.h"
 
 namespace ns {
 
@@ -16,9 +18,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int LOSS_THREADS = 256;
-constexpr float GA_TWO_SIGMA_SQ = 0.08f;  // 2 * sigma ** 2, sigma = 0.2 (model/loss.py:19,107); torch divides the fp32 tensor by this scalar
-constexpr double GA_ALPHA = 10.0;         // model/loss.py:19,65
-
 // slot words: 0 sum|mel - tgt|, 1 sum|postnet - tgt|, 2 sum (pitch err)^2, 3 sum (energy err)^2, 4 sum (log-duration err)^2,
 // 5 sum_k sum W * attn_k (doubles); 6 unmasked frames, 7 unmasked phonemes (int64)
 __device__ __forceinline__ float wave_sum(float v) {
@@ -61,13 +60,6 @@ __device__ __forceinline__ void write_slot(const float (&acc)[LOSS_SLOT_SUMS], i
   }
 }
 
-__device__ __forceinline__ int clamp_len(long long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
-
-// W[t, l] = 1 - exp(-((l / ilen - t / olen) ** 2) / (2 * sigma ** 2)), fp32, the reference's operation order (model/loss.py:104-108)
-__device__ __forceinline__ float guide(int t, int l, float ilen, float olen) {
-  const float d = (float)l / ilen - (float)t / olen;
-  return 1.0f - expf(-(d * d) / GA_TWO_SIGMA_SQ);
-}
 }  // namespace
 
 __global__ __launch_bounds__(LOSS_THREADS) void k_loss_partial(LossArgs a, int n_frame_wgs, int n_phoneme_wgs, char* __restrict__ ws) {
@@ -189,7 +181,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_partial(LossArgs a, int n
 
 // out7 = total, mel, postnet, pitch, energy, duration, attn (model/loss.py:242-250).  A zero count divides 0 by 0: NaN, what
 // torch.mean of an empty selection gives, and the total is then NaN too.
-__global__ __launch_bounds__(LOSS_THREADS) void k_loss_final(LossArgs a, int n_slots, const char* __restrict__ ws, float* __restrict__ out7) {
+__global__ __launch_bounds__(LOSS_THREADS) void k_loss_final(LossArgs a, int n_slots, const char* __restrict__ ws, float* __restrict__ out7,
+                                                               long long* __restrict__ record) {
   __shared__ double part[LOSS_THREADS][LOSS_SLOT_SUMS];
   __shared__ long long cnt[LOSS_THREADS][3];
   const int tid = threadIdx.x;
@@ -228,6 +221,9 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_final(LossArgs a, int n_s
     const float attn = (float)(GA_ALPHA * part[0][5] / na);
     out7[0] = mel + post + dur + pitch + energy + attn;  // the reference's order (model/loss.py:238-240)
     out7[1] = mel; out7[2] = post; out7[3] = pitch; out7[4] = energy; out7[5] = dur; out7[6] = attn;
+    if (record) {  // what the backward divides by (lossgrad.hip): the caller's own words, not the shared workspace
+      record[0] = cnt[0][0]; record[1] = cnt[0][1]; record[2] = cnt[0][2]; record[3] = 0;
+    }
   }
 }
 
@@ -240,7 +236,7 @@ long long loss_slots(int B, int L, int T, int* n_frame_wgs, int* n_phoneme_wgs) 
   return nf + np + na;
 }
 
-hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st) {
+hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st, long long* record) {
   int nf = 0, np = 0;
   const long long slots = loss_slots(a.B, a.L, a.T, &nf, &np);
   if (slots >= (1ll << 31)) return hipErrorInvalidValue;
@@ -249,7 +245,7 @@ hipError_t launch_loss(const LossArgs& a, void* ws, float* out7, hipStream_t st)
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LOSS_THREADS), 0, st, a, (int)slots, (const char*)ws, out7);
+  hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LOSS_THREADS), 0, st, a, (int)slots, (const char*)ws, out7, record);
   return hipGetLastError();
 }
 

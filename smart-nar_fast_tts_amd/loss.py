@@ -1,7 +1,13 @@
-"""Validation loss of a teacher-forced batch: the reference's ``FastSpeech2Loss`` (model/loss.py:149-250) as two HIP launches
-(csrc/loss.hip; ``ns_loss_*`` in include/nar_fs2.h), and the arithmetic of the ``evaluate`` module the reference imports but does
-not ship (train.py:16).  The forward VALUE in ``eval()`` only: no backward, and no optimiser here — the optimiser half of the
-training step (clip, Adam, the schedule) is ``optim.py``, which acts on gradients some other backward pass has produced."""
+"""The loss of a teacher-forced batch: the reference's ``FastSpeech2Loss`` (model/loss.py:149-250) in HIP (csrc/loss.hip, csrc/lossgrad.hip;
+``ns_loss_*`` and ``ns_lossg_*`` in include/nar_fs2.h), and the arithmetic of the ``evaluate`` module the reference imports but does
+not ship (train.py:16).
+
+``FastSpeech2Loss``           the forward VALUE in ``eval()`` only, two launches: no backward; it refuses ``train()`` and ``requires_grad``
+``FastSpeech2TrainingLoss``   the same value plus ``total_loss.backward()`` (train.py:88) as a ``torch.autograd.Function``: one more
+                              launch writes the gradients of the five predictions and the four alignment maps
+
+No optimiser here — the optimiser half of the training step (clip, Adam, the schedule) is ``optim.py``, which consumes the gradients
+that torch's backward of the model produces from these."""
 from __future__ import annotations
 
 import contextlib
@@ -14,7 +20,14 @@ import torch
 from . import _lib
 
 _TRAINING = "training is out of scope for this path (SURVEY.md §2); only eval() is supported"
+_NINE_IN_KEEP = (4, 5, 8, 10, 12, 13, 14, 15, 16)  # mel, postnet, pitch, energy, log_d, attn[0..3] in _marshal's `keep` list
+GRAD_NAMES = ("mel_predictions", "postnet_mel_predictions", "pitch_predictions", "energy_predictions", "log_duration_predictions",
+              "attn[0]", "attn[1]", "attn[2]", "attn[3]")  # what FastSpeech2TrainingLoss differentiates (model/loss.py:175-179,185)
 LOSS_NAMES = ("total", "mel", "postnet", "pitch", "energy", "duration", "attn")  # the reference's return order (model/loss.py:242-250)
+
+
+def _guard(dev):
+    return contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
 class FastSpeech2Loss:
@@ -75,6 +88,25 @@ class FastSpeech2Loss:
     def forward(self, inputs, predictions):
         if self.training:
             raise NotImplementedError(_TRAINING)
+        call = self._marshal(inputs, predictions)
+        with _guard(call.device):
+            return self._value(call)
+
+    def _value(self, call):
+        """ns_loss_forward on the current stream of the call's device: the [7] tensor's seven views."""
+        ws = self.workspace(call.device, self._lib.ns_loss_ws_bytes(call.B, call.L, call.T))
+        out = torch.empty(7, dtype=torch.float32, device=call.device)
+        _lib.check(self._lib.ns_loss_forward(C.byref(call.args), _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.stream_ptr(call.device)), "ns_loss_forward")
+        return tuple(out[i] for i in range(7))
+
+    def _refuse_grad(self, name, t):
+        """A tensor with requires_grad: this class has no backward."""
+        raise NotImplementedError(f"{name}.requires_grad: " + _TRAINING)
+
+    def _marshal(self, inputs, predictions):
+        """Checks the two tuples and lays them out for the C ABI: a ``_Call`` holding the filled ``ns_loss_args``, the tensors it points
+        into, and the nine predictions as the dense tensors the kernels read (autograd-connected to the caller's where those require
+        grad)."""
         if len(inputs) < 11:
             raise ValueError(f"inputs must be the reference's batch tuple of 11 entries (utils/tools.py:18-54), got {len(inputs)}")
         if len(predictions) != 12:
@@ -92,7 +124,7 @@ class FastSpeech2Loss:
             if not torch.is_tensor(t):
                 raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
             if t.requires_grad:
-                raise NotImplementedError(f"{name}.requires_grad: " + _TRAINING)
+                self._refuse_grad(name, t)
         for name, t in named.items():
             if not t.is_cuda:
                 raise RuntimeError(f"{name} must live on the MI355X (cuda) device; there is no CPU path")
@@ -155,7 +187,7 @@ class FastSpeech2Loss:
             t = t.contiguous()
             return t.clone() if t.data_ptr() % 16 else t
 
-        with (contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)):
+        with _guard(dev):
             sl, ml = lens("src_lens", src_lens), lens("mel_lens", mel_lens)
             # the two slices the reference takes go through the strides
             if not (mel_targets.stride(2) == 1 and mel_targets.stride(1) == n_mel and mel_targets.stride(0) % 4 == 0
@@ -192,10 +224,112 @@ class FastSpeech2Loss:
                 m = attn[k].contiguous()
                 keep.append(m)
                 a.attn[k] = m.data_ptr()
-            ws = self.workspace(dev, self._lib.ns_loss_ws_bytes(B, L, T))
-            out = torch.empty(7, dtype=torch.float32, device=dev)
-            _lib.check(self._lib.ns_loss_forward(C.byref(a), _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.stream_ptr(dev)), "ns_loss_forward")
+        call = _Call()
+        call.args, call.keep, call.device, call.B, call.L, call.T = a, keep, dev, B, L, T
+        call.nine = tuple(keep[i] for i in _NINE_IN_KEEP)
+        return call
+
+
+class _Call:
+    """One marshalled loss call (``FastSpeech2Loss._marshal``)."""
+    __slots__ = ("args", "keep", "device", "B", "L", "T", "nine")
+
+
+class _LossFunction(torch.autograd.Function):
+    """value = ns_lossg_forward (two launches, writes the record), backward = ns_lossg_backward (one launch).  The nine differentiable
+    tensors are flat arguments; everything else rides on ``call``."""
+
+    @staticmethod
+    def forward(ctx, owner, call, *nine):
+        out, record = owner._value_with_record(call)
+        ctx.owner, ctx.call, ctx.record = owner, call, record
+        ctx.save_for_backward(*nine)  # (autograd then refuses a backward after an in-place change of a prediction)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        nine = ctx.saved_tensors
+        owner, call = ctx.owner, ctx.call
+        need = ctx.needs_input_grad[2:]
+        with _guard(call.device):
+            grads = owner._backward(call, ctx.record, g, [torch.empty_like(x, memory_format=torch.contiguous_format) if n else None
+                                                          for x, n in zip(nine, need)])
+        return (None, None) + tuple(grads)
+
+
+class FastSpeech2TrainingLoss(FastSpeech2Loss):
+    """``FastSpeech2Loss`` with a backward: the criterion of the reference's training step (train.py:43,83-88).
+
+        Loss = FastSpeech2TrainingLoss(preprocess_config, model_config).to(device)          # train.py:43
+        losses = Loss(batch, output)                                                        # train.py:83
+        (losses[0] / grad_acc_step).backward()                                              # train.py:84-88
+
+    ``train()`` and ``eval()`` both work and change nothing.  When no prediction requires grad, or under ``torch.no_grad()``, a call is
+    the parent's: ``ns_loss_forward``, the same bits.  Otherwise the seven values are views of the ``[7]`` output of one
+    ``torch.autograd.Function`` — the same bits again — and a backward of ``total``, of ``total / grad_acc_step`` or of any mix of the
+    seven is ONE launch (csrc/lossgrad.hip) that reads autograd's ``grad_output`` and the forward's counts on the device: three
+    launches for value and gradients, no host read.  Differentiated: the five predictions and the four alignment maps
+    (``GRAD_NAMES``); a tensor of those that does not require grad gets no buffer and no write.  Targets, masks and lengths never get
+    gradients, and a target that requires grad is refused (the reference switches it off in place, model/loss.py:194-197; we do not
+    modify the caller's tensors).  Single backward only (``once_differentiable``).
+
+    A masked-out position gets the gradient +0.0 and is never read, so NaN behind a mask stays there; a part whose selection is empty
+    (value NaN) has an all-zero gradient, as ``masked_select``'s backward gives."""
+
+    def __init__(self, preprocess_config: dict, model_config: dict):
+        super().__init__(preprocess_config, model_config)
+        self.launches = 0  # kernel launches enqueued by the differentiable path (tools/lossgrad_bench.py counts them)
+
+    def train(self, mode: bool = True):
+        self.training = bool(mode)
+        return self
+
+    def _refuse_grad(self, name, t):
+        if name not in GRAD_NAMES:
+            raise ValueError(f"{name}.requires_grad: targets, masks and lengths get no gradient from the loss (model/loss.py:194-197); detach it first")
+
+    def forward(self, inputs, predictions):
+        call = self._marshal(inputs, predictions)
+        if not (torch.is_grad_enabled() and any(t.requires_grad for t in call.nine)):
+            with _guard(call.device):
+                return self._value(call)
+        out = _LossFunction.apply(self, call, *call.nine)
         return tuple(out[i] for i in range(7))
+
+    def _value_with_record(self, call):
+        """ns_lossg_forward on the current stream of the call's device: ``(out [7], record)``.  The record is a fresh tensor per call:
+        it carries the forward's counts to the backward and outlives the shared workspace."""
+        dev = call.device
+        with _guard(dev):
+            ws = self.workspace(dev, self._lib.ns_loss_ws_bytes(call.B, call.L, call.T))
+            out = torch.empty(7, dtype=torch.float32, device=dev)
+            record = torch.empty(self._lib.ns_lossg_record_bytes() // 8, dtype=torch.int64, device=dev)
+            _lib.check(self._lib.ns_lossg_forward(C.byref(call.args), _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.ptr(record), _lib.stream_ptr(dev)),
+                       "ns_lossg_forward")
+        self.launches += 2
+        return out, record
+
+    def _backward(self, call, record, g, outs):
+        """One launch on the current stream of the call's device: writes the gradient of ``(g * seven).sum()`` into every tensor of
+        ``outs`` (the order of ``GRAD_NAMES``) that is not None, and returns ``outs``."""
+        if tuple(g.shape) != (7,) or g.dtype != torch.float32 or g.device != call.device:
+            raise ValueError(f"grad_output must be a float32 [7] tensor on {call.device}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+        g = g.contiguous()
+        d = _lib.NsLossgGrads()
+        for i, (name, x, o) in enumerate(zip(GRAD_NAMES, call.nine, outs)):
+            if o is None:
+                continue
+            if o.dtype != torch.float32 or o.device != call.device or tuple(o.shape) != tuple(x.shape) or not o.is_contiguous():
+                raise ValueError(f"the gradient buffer of {name} must be a contiguous float32 tensor of shape {tuple(x.shape)} on {call.device}")
+            if i < 5:
+                setattr(d, ("mel", "postnet", "pitch", "energy", "log_d")[i], o.data_ptr())
+            else:
+                d.attn[i - 5] = o.data_ptr()
+        _lib.check(self._lib.ns_lossg_backward(C.byref(call.args), _lib.ptr(record), _lib.ptr(g), C.byref(d), _lib.stream_ptr(call.device)),
+                   "ns_lossg_backward")
+        self.launches += 1
+        return outs
 
 
 def evaluate(model, batches, loss=None):

@@ -1,7 +1,7 @@
 """The optimiser half of the reference's training step on the device: ``nn.utils.clip_grad_norm_``, ``ScheduledOptim`` (Adam under the
 Noam warm-up / anneal schedule, model/optimizer.py) and ``zero_grad()`` — train.py:91-95 — as a fixed handful of HIP launches
 (csrc/optim.hip; ``ns_opt_*`` in include/nar_fs2.h).  It acts on ordinary ``torch.nn.Parameter``s and their ``.grad``s, so it drops into
-a training loop that runs the reference model under PyTorch-ROCm; this package still owns no backward pass.
+a training loop that runs the reference model under PyTorch-ROCm; the model's backward stays torch's (the loss's own: loss.py).
 
     optimizer = ScheduledOptim(model, train_config, model_config, restore_step)          # utils/model.py:27-29
     ...

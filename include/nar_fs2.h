@@ -223,6 +223,18 @@ int ns_op_positionwise_ffn(ns_model* m, const char* prefix, const float* x, int 
 int ns_op_fft_block(ns_model* m, const char* prefix, const float* x, const int64_t* lens, int B, int S, float* out, void* ws, size_t ws_bytes, void* stream);
 /* a8  model/modules.py:278-286 */
 int ns_op_variance_predictor(ns_model* m, const char* prefix, const float* x, const int64_t* lens, int B, int S, float* out, void* ws, size_t ws_bytes, void* stream);
+/* a8 as its two launches, for tests that hold one contraction plus its row epilogue to a reference.  Both choose the full-row
+ * tile / the ticketed ladder / the two-launch form exactly as the forward does (row count and the model's row_epilogue setting).
+ * ns_op_predictor_conv1: h [B*S, filter] = layer_norm_1(relu(conv1d_1(x))), x [B*S, d].
+ * ns_op_predictor_tail: from a hidden tensor h [B*S, filter] the caller supplies, pred [B*S] = masked_fill(linear(layer_norm_2(
+ * relu(conv1d_2(h))))) (* control when target is NULL).  With x_in [B*S, d] (pitch / energy predictors only; the duration predictor
+ * refuses it) x_out = x_in + embedding[bucketize(target ? target : pred)] (unmasked), and with add_pos != 0 also + the decoder
+ * position row of each frame (the cached table up to max_seq_len, the regenerated one beyond: what the last frame-level embedding
+ * of the forward adds).  x_out / add_pos need x_in.  Unknown prefixes and null arguments are refused before any device work. */
+int ns_op_predictor_conv1(ns_model* m, const char* prefix, const float* x, int B, int S, float* h, void* ws, size_t ws_bytes, void* stream);
+int ns_op_predictor_tail(ns_model* m, const char* prefix, const float* h, const int64_t* lens, int B, int S, float control,
+                         const float* target /* nullable */, const float* x_in /* nullable: no embedding */, int add_pos, float* pred,
+                         float* x_out /* with x_in */, void* ws, size_t ws_bytes, void* stream);
 /* a9  model/modules.py:132-135 */
 int ns_op_duration_round(const float* log_d, int n, float d_control, float* d_rounded, void* stream);
 /* a10 model/modules.py:201-230 + utils/tools.py:288-306: step 1 prefix sums + mel_lens, step 2 gather to [B,T,D] */

@@ -119,6 +119,8 @@ SIGNATURES = {
     "ns_op_positionwise_ffn": (_I, [_P, _S, _P, _I, _I, _P, _P, _Z, _P]),
     "ns_op_fft_block": (_I, [_P, _S, _P, _P, _I, _I, _P, _P, _Z, _P]),
     "ns_op_variance_predictor": (_I, [_P, _S, _P, _P, _I, _I, _P, _P, _Z, _P]),
+    "ns_op_predictor_conv1": (_I, [_P, _S, _P, _I, _I, _P, _P, _Z, _P]),
+    "ns_op_predictor_tail": (_I, [_P, _S, _P, _P, _I, _I, _F, _P, _P, _I, _P, _P, _P, _Z, _P]),
     "ns_op_duration_round": (_I, [_P, _I, _F, _P, _P]),
     "ns_op_duration_scan": (_I, [_P, _I, _I, _P, _P, _P]),
     "ns_op_duration_target_scan": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -587,29 +587,38 @@ static int position_rows(const ns_model* m, size_t cached_off, int S, int d, Scr
   return 0;
 }
 
-// VariancePredictor.forward (model/modules.py:278-286) with the optional fused embedding add
+// VariancePredictor.forward (model/modules.py:278-286) with the optional fused embedding add, as its two launches.
+// Stage 1: h [M, F] = layer_norm_1(relu(conv1d_1(x)))  (no mask between the layers: model/modules.py:245-274)
+static int predictor_conv1(const ns_model* m, const PredW& w, const float* x, int B, int S, float* h, Scratch& sc, hipStream_t st) {
+  const int M = rows_of(sc, B, S);
+  return gemm_ln(m, sc, w.c1, x, nullptr, sc.vp1, h, M, S, ACT_RELU, m->P(w.ln1_g), m->P(w.ln1_b), nullptr, st);
+}
+// Stage 2, from the hidden rows h: conv1d_2 -> relu -> layer_norm_2 -> linear -> mask (-> bucketize + embedding add onto x_in):
+// the whole tail rides on conv1d_2's row epilogue — the full-row tile when the launch is large, the ticketed form on small grids
+static int predictor_tail(const ns_model* m, const PredW& w, const float* h, const long long* lens, int B, int S, float control,
+                          const float* target, float* pred, const float* bins, const float* emb, const float* x_in, const float* pos,
+                          float* x_out, Scratch& sc, hipStream_t st) {
+  const ns_config& c = m->cfg;
+  const int M = rows_of(sc, B, S), F = c.vp_filter, D = w.c1.cin;
+  RowEpilogue e;
+  memset(&e, 0, sizeof(e));
+  e.ln_g = m->P(w.ln2_g); e.ln_b = m->P(w.ln2_b); e.lens = lens; e.wlin = m->P(w.lin_w); e.blin = m->P(w.lin_b); e.pred = pred;
+  e.control = control; e.target = target; e.bins = bins; e.n_edges = c.n_bins - 1; e.emb = emb; e.x_in = x_in; e.pos = pos; e.x_out = x_out;
+  e.D = D;
+  if (fuse_row_epilogue(M, F, F)) return gemm(m, sc, w.c2, h, nullptr, nullptr, M, S, ACT_RELU, st, GemmOpts::row(e, EPI_LN_PRED));
+  if (conv_gemm_ticket_ok(M, F, F) && (e.ticket = sc.tk.take(conv_gemm_ticket_ints(M))) != nullptr)
+    return gemm(m, sc, w.c2, h, nullptr, sc.vp1, M, S, ACT_RELU, st, GemmOpts::row(e, EPI_LN_PRED));
+  NS_TRY(gemm(m, sc, w.c2, h, nullptr, sc.vp1, M, S, ACT_RELU, st));
+  NS_HIP(launch_ln_linear_embed(sc.vp1, m->P(w.ln2_g), m->P(w.ln2_b), m->P(w.lin_w), m->P(w.lin_b), pred, M, F, S, lens,
+                                control, target, bins, c.n_bins, emb, x_in, pos, x_out, D, st, cur_rm(sc)));
+  return 0;
+}
 static int predictor(const ns_model* m, const PredW& w, const float* x, const long long* lens, int B, int S, float control,
                      const float* target,
                      float* pred, const float* bins, const float* emb, const float* pos, float* x_out, Scratch& sc,
                      hipStream_t st) {
-  const ns_config& c = m->cfg;
-  const int M = rows_of(sc, B, S), F = c.vp_filter, D = w.c1.cin;
-  // conv1d_1 -> relu -> layer_norm_1 (no mask between the layers: model/modules.py:245-274)
-  NS_TRY(gemm_ln(m, sc, w.c1, x, nullptr, sc.vp1, sc.vp2, M, S, ACT_RELU, m->P(w.ln1_g), m->P(w.ln1_b), nullptr, st));
-  // conv1d_2 -> relu -> layer_norm_2 -> linear -> mask (-> bucketize + embedding add): the whole tail rides on conv1d_2's
-  // row epilogue — the full-row tile when the launch is large, the ticketed form on small grids
-  RowEpilogue e;
-  memset(&e, 0, sizeof(e));
-  e.ln_g = m->P(w.ln2_g); e.ln_b = m->P(w.ln2_b); e.lens = lens; e.wlin = m->P(w.lin_w); e.blin = m->P(w.lin_b); e.pred = pred;
-  e.control = control; e.target = target; e.bins = bins; e.n_edges = c.n_bins - 1; e.emb = emb; e.x_in = x; e.pos = pos; e.x_out = x_out;
-  e.D = D;
-  if (fuse_row_epilogue(M, F, F)) return gemm(m, sc, w.c2, sc.vp2, nullptr, nullptr, M, S, ACT_RELU, st, GemmOpts::row(e, EPI_LN_PRED));
-  if (conv_gemm_ticket_ok(M, F, F) && (e.ticket = sc.tk.take(conv_gemm_ticket_ints(M))) != nullptr)
-    return gemm(m, sc, w.c2, sc.vp2, nullptr, sc.vp1, M, S, ACT_RELU, st, GemmOpts::row(e, EPI_LN_PRED));
-  NS_TRY(gemm(m, sc, w.c2, sc.vp2, nullptr, sc.vp1, M, S, ACT_RELU, st));
-  NS_HIP(launch_ln_linear_embed(sc.vp1, m->P(w.ln2_g), m->P(w.ln2_b), m->P(w.lin_w), m->P(w.lin_b), pred, M, F, S, lens,
-                                control, target, bins, c.n_bins, emb, x, pos, x_out, D, st, cur_rm(sc)));
-  return 0;
+  NS_TRY(predictor_conv1(m, w, x, B, S, sc.vp2, sc, st));
+  return predictor_tail(m, w, sc.vp2, lens, B, S, control, target, pred, bins, emb, x, pos, x_out, sc, st);
 }
 
 // PostNet.forward (transformer/Layers.py:169-177); resid != nullptr adds `+ output` of fastspeech2_align.py:85
@@ -1140,6 +1149,37 @@ extern "C" int ns_op_variance_embedding(ns_model* m, int which, const float* x, 
   const size_t bins = which ? m->energy_bins : m->pitch_bins, emb = which ? m->energy_emb : m->pitch_emb;
   return predictor(m, m->pred[1 + which], x, (const long long*)lens, B, S, control, target, pred, m->P(bins), m->P(emb), nullptr, x_out,
                    sc, st);
+}
+// The predictor's two launches alone (for tests that hold one contraction plus its row epilogue to a reference): each chooses
+// full-row / ticketed / two-launch as the forward does, through the same scratch carving.  Arguments are refused before the model's state is looked at and before any device work.
+extern "C" int ns_op_predictor_conv1(ns_model* m, const char* prefix, const float* x, int B, int S, float* h, void* ws, size_t ws_bytes,
+                                     void* stream) {
+  if (!m) return fail("null model");
+  int i;
+  NS_TRY(find_pred(prefix, &i));
+  if (!x || !h || !ws) return fail("ns_op_predictor_conv1: null argument");
+  NS_OP_PROLOGUE(B, S);
+  return predictor_conv1(m, m->pred[i], x, B, S, h, sc, st);
+}
+extern "C" int ns_op_predictor_tail(ns_model* m, const char* prefix, const float* h, const int64_t* lens, int B, int S, float control,
+                                    const float* target, const float* x_in, int add_pos, float* pred, float* x_out, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  if (!m) return fail("null model");
+  int i;
+  NS_TRY(find_pred(prefix, &i));
+  if (!h || !lens || !pred || !ws) return fail("ns_op_predictor_tail: null argument");
+  if (i == 0 && (x_in || x_out || add_pos)) return fail("ns_op_predictor_tail: the duration predictor has no embedding");
+  if (x_in && !x_out) return fail("ns_op_predictor_tail: x_in without x_out");
+  if (!x_in && (x_out || add_pos)) return fail("ns_op_predictor_tail: x_out / add_pos without x_in");
+  NS_OP_PROLOGUE(B, S);
+  const PredW& w = m->pred[i];
+  const float *bins = nullptr, *emb = nullptr, *pos = nullptr;
+  if (x_in) {
+    bins = m->P(i == 2 ? m->energy_bins : m->pitch_bins);
+    emb = m->P(i == 2 ? m->energy_emb : m->pitch_emb);
+    if (add_pos) NS_TRY(position_rows(m, m->dec_pos, S, w.c1.cin, sc, &pos, st));
+  }
+  return predictor_tail(m, w, h, (const long long*)lens, B, S, control, target, pred, bins, emb, x_in, pos, x_out, sc, st);
 }
 extern "C" int ns_plan_gemm(int M, int N, int Cin, int KW, int32_t out[8]) {
   int o[8] = {0, 0, 0, 0, 0, 0, 0, 0};

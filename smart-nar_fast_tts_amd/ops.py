@@ -95,6 +95,39 @@ def variance_predictor(model, prefix, x, lens):
     return out
 
 
+def predictor_conv1(model, prefix, x):
+    """The first launch of a VariancePredictor alone: h [B,S,filter] = layer_norm_1(relu(conv1d_1(x))) (model/modules.py:245-260)."""
+    B, S, _ = x.shape
+    x = x.contiguous()
+    h = torch.empty(B, S, model._cfg.vp_filter, dtype=torch.float32, device=x.device)
+    ws = _ws(model, B, S)
+    _lib.check(model._lib.ns_op_predictor_conv1(model._h, prefix.encode(), _lib.ptr(x), B, S, _lib.ptr(h), _lib.ptr(ws), ws.numel(),
+                                                _st(x)), "predictor_conv1")
+    return h
+
+
+def predictor_tail(model, prefix, h, lens, control: float = 1.0, target=None, x_in=None, add_pos: bool = False, pred=None, x_out=None):
+    """The second launch of a VariancePredictor alone, from hidden rows ``h`` [B,S,filter] the caller supplies: conv1d_2 -> ReLU ->
+    layer_norm_2 -> Linear -> masked_fill (-> ``* control`` without a ``target``).  With ``x_in`` [B,S,d] also the pitch / energy
+    embedding add of ``prefix`` (from bucketize(target) when a target is given) and, with ``add_pos``, the decoder position rows.
+    Returns ``pred`` [B,S], or ``(pred, x_out)`` with ``x_in``.  ``pred`` / ``x_out`` may be passed in (pre-filled) to be written."""
+    B, S, _ = h.shape
+    h, lens = h.contiguous(), lens.long().contiguous()
+    if pred is None:
+        pred = torch.empty(B, S, dtype=torch.float32, device=h.device)
+    if target is not None:
+        target = target.contiguous().float()
+    if x_in is not None:
+        x_in = x_in.contiguous()
+        if x_out is None:
+            x_out = torch.empty_like(x_in)
+    ws = _ws(model, B, S)
+    _lib.check(model._lib.ns_op_predictor_tail(model._h, prefix.encode(), _lib.ptr(h), _lib.ptr(lens), B, S, float(control), _lib.ptr(target),
+                                               _lib.ptr(x_in), int(bool(add_pos)), _lib.ptr(pred), _lib.ptr(x_out), _lib.ptr(ws), ws.numel(),
+                                               _st(h)), "predictor_tail")
+    return pred if x_in is None else (pred, x_out)
+
+
 def duration_round(log_d, d_control: float = 1.0):
     """model/modules.py:132-135."""
     lib = _lib.load()

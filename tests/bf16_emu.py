@@ -119,22 +119,67 @@ class LnCheck:
         return f"worst |y - f64| / bound = {self.worst:.3g}"
 
 
-def gemm_ln_check(got, x, w, b, resid, g, beta, rel=GEMM_REL, round_fn=bf):
-    """got = LayerNorm(gemm(x) + resid) against float64, the GEMM's bound e = rel * unit propagated through the LayerNorm to
-    first order: with yhat = (z - mean) / sigma, d y_n = g_n / sigma * (d z_n - mean(d z) - yhat_n * mean(yhat d z)) and
-    |mean(yhat d z)| <= rms(yhat) rms(d z) = rms(e); plus FP32_REL * (|ref| + |ln_b|) for the fp32 row arithmetic."""
-    z = gemm_emu(x, w, b, round_fn=round_fn) + resid.double()
+def _ln_ref_bound(x, w, b, resid, g, beta, rel, round_fn, act):
+    """(float64 LayerNorm(act(gemm(x)) + resid), its first-order elementwise bound): see gemm_ln_check"""
+    z = gemm_emu(x, w, b, act=act, round_fn=round_fn)
+    if resid is not None:
+        z = z + resid.double()
     ref = layernorm_emu(z, g, beta)
     e = rel * gemm_unit(x, w, b, round_fn=round_fn)
     mean = z.mean(-1, keepdim=True)
     sigma = torch.sqrt(((z - mean) ** 2).mean(-1, keepdim=True) + LN_EPS)
     yhat = (z - mean) / sigma
     bound = g.double().abs() / sigma * (e + e.mean(-1, keepdim=True) + yhat.abs() * torch.sqrt((e ** 2).mean(-1, keepdim=True)))
-    bound = bound + FP32_REL * (ref.abs() + beta.double().abs())
+    return ref, bound + FP32_REL * (ref.abs() + beta.double().abs())
+
+
+def gemm_ln_check(got, x, w, b, resid, g, beta, rel=GEMM_REL, round_fn=bf, act=None):
+    """got = LayerNorm(act(gemm(x)) + resid) against float64, the GEMM's bound e = rel * unit propagated through the LayerNorm to
+    first order: with yhat = (z - mean) / sigma, d y_n = g_n / sigma * (d z_n - mean(d z) - yhat_n * mean(yhat d z)) and
+    |mean(yhat d z)| <= rms(yhat) rms(d z) = rms(e); plus FP32_REL * (|ref| + |ln_b|) for the fp32 row arithmetic.  act (ReLU, tanh)
+    is 1-Lipschitz, so the GEMM's bound holds on act(z); resid = None is no residual."""
+    ref, bound = _ln_ref_bound(x, w, b, resid, g, beta, rel, round_fn, act)
     got = got.reshape(ref.shape).double()
     err = (got - ref).abs()
     ok = bool((err <= bound).all()) and bool(torch.isfinite(got).all())
     return LnCheck(ok, float((err / bound.clamp_min(1e-300)).max()))
+
+
+# ---------------------------------------------------------------------------------------------------- predictor tail
+def pred_tail_ref(h, w2, b2, g2, beta2, wlin, blin, lens, control=1.0, target_given=False, rel=FP32_REL):
+    """(float64 pred [B, S], its first-order bound) of the second launch of a VariancePredictor on hidden rows h [B, S, F]:
+    (LayerNorm(relu(conv_rows(h, w2, b2))) . wlin + blin), zero at t >= lens[b], * control unless a target is given.
+    bound = sum_n |wlin_n| (LayerNorm bound)_n + FP32_REL (sum_n |y_n wlin_n| + |blin|), scaled like the value."""
+    y, yb = _ln_ref_bound(h, w2, b2, None, g2, beta2, rel, exact, "relu")
+    wl = wlin.double().reshape(-1)
+    pred = y @ wl + blin.double().reshape(())
+    bound = yb @ wl.abs() + FP32_REL * ((y * wl).abs().sum(-1) + blin.double().abs().reshape(()))
+    c = 1.0 if target_given else float(control)
+    valid = torch.arange(h.shape[1])[None, :] < torch.as_tensor(lens)[:, None]
+    zero = torch.zeros((), dtype=torch.float64)
+    return torch.where(valid, pred * c, zero), torch.where(valid, bound * abs(c), zero)
+
+
+def pred_tail_fp32(h, w2, b2, g2, beta2, wlin, blin, lens, control=1.0, target_given=False):
+    """torch's fp32 CPU evaluation of the same tail (what "as close to float64 as fp32 gets" means for it)"""
+    y = layernorm_emu(gemm_emu(h, w2, b2, act="relu", dtype=torch.float32, round_fn=exact), g2, beta2, dtype=torch.float32)
+    pred = y @ wlin.float().reshape(-1) + blin.float().reshape(())
+    valid = torch.arange(h.shape[1])[None, :] < torch.as_tensor(lens)[:, None]
+    pred = torch.where(valid, pred, torch.zeros((), dtype=torch.float32))
+    return pred if target_given else pred * torch.tensor(float(control), dtype=torch.float32)
+
+
+def pred_check(got, ref, bound, tight):
+    """every pred against float64 at tight x the first-order bound; a masked row (bound 0) must be exactly zero.  worst is in units
+    of the gate (<= 1 passes); worst * tight is the share of the first-order bound."""
+    got = got.reshape(ref.shape).double()
+    err = (got - ref).abs()
+    ok = bool((err <= tight * bound).all()) and bool(torch.isfinite(got).all())
+    live = bound > 0
+    worst = float((err[live] / (tight * bound[live])).max()) if bool(live.any()) else 0.0
+    if bool((err[~live] != 0).any()):
+        worst = float("inf")
+    return LnCheck(ok, worst)
 
 
 # ---------------------------------------------------------------------------------------------------- attention

@@ -269,11 +269,19 @@ def launches(M, shape, epi=0):
 _SCAN = {}
 
 
+# The variance predictors' two contractions (csrc/api.hip predictor_conv1 / predictor_tail; conv1d_1 of a 512-wide model reads 512
+# channels): ops.gemm cannot name them, they run under a row epilogue only — LayerNorm for conv1d_1, the predictor tail for conv1d_2,
+# both dispatched like a LayerNorm launch.  Their cases are tests/test_predictor_ops_host.py PRED_CASES.
+PRED_SHAPES = [(256, 256, 3), (512, 256, 3)]
+
+
 def scan():
-    """{form: {shape: smallest M}} over every accepted contraction and M = 1 ... SCAN_ROWS, plain and (row widths) LayerNorm"""
+    """{form: {shape: smallest M}} over every accepted contraction and M = 1 ... SCAN_ROWS, plain and (row widths) LayerNorm, and
+    the predictors' contractions under their row epilogue"""
     if not _SCAN:
-        for shape in all_shapes():
-            for epi_of in ((lambda M: 0),) + ((ln_epi,) if shape[1] in (256, 512) and shape[2] == 1 else ()):
+        for shape in all_shapes() + PRED_SHAPES:
+            plain = () if shape in PRED_SHAPES else ((lambda M: 0),)
+            for epi_of in plain + ((ln_epi,) if shape[1] in (256, 512) and (shape[2] == 1 or shape in PRED_SHAPES) else ()):
                 for M in range(1, SCAN_ROWS + 1):
                     for l in launches(M, shape, epi_of(M)):
                         _SCAN.setdefault(l[:7], {}).setdefault(shape, M)

@@ -826,6 +826,73 @@ int ns_lossg_forward(const ns_loss_args* a, void* ws, size_t ws_bytes, float* ou
  * and on an output that is not 16-byte aligned.  With every output NULL nothing is launched. */
 int ns_lossg_backward(const ns_loss_args* a, const void* record, const float* g7, const ns_lossg_grads* grads, void* stream);
 
+/* ==== VariancePredictor: a training forward and its backward (model/modules.py:233-286) ===========================================
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  The module is
+ *   conv1d_1 -> ReLU -> layer_norm_1 -> dropout_1 -> conv1d_2 -> ReLU -> layer_norm_2 -> dropout_2 -> Linear(F, 1) -> masked_fill
+ * on M = B * S rows of Cin channels, F filters, K taps ("same" padding (K - 1) / 2).  The weights are LIVE device tensors in checkpoint
+ * (torch) layout, read afresh by every call; dropout is given as two uint8 keep-masks [M, F] (1 = kept) and p_drop, the kept values
+ * scaled by 1 / (1 - p_drop).  Exact fp32 on the fp32 matrix cores; column sums in float64, rounded once.  No atomic, no host read;
+ * equal inputs give equal bits (the split of the weight gradient's contraction is a function of the shape alone: ns_pg_plan_wgrad). */
+#define NS_PG_ABI_VERSION 1
+int ns_pg_abi_version(void);
+typedef struct ns_pg_shape { int32_t B, S, Cin, F, K; } ns_pg_shape;
+/* Device pointers, 16-byte aligned, fp32, checkpoint layout. */
+typedef struct ns_pg_weights {
+  const float* w1;     /* [F, Cin, K] conv_layer.conv1d_1.conv.weight */
+  const float* b1;     /* [F] */
+  const float* ln1_g;  /* [F] conv_layer.layer_norm_1.weight */
+  const float* ln1_b;  /* [F] */
+  const float* w2;     /* [F, F, K] conv_layer.conv1d_2.conv.weight */
+  const float* b2;     /* [F] */
+  const float* ln2_g;  /* [F] */
+  const float* ln2_b;  /* [F] */
+  const float* wlin;   /* [1, F] linear_layer.weight */
+  const float* blin;   /* [1] linear_layer.bias */
+} ns_pg_weights;
+/* The outputs of ns_pg_backward: the same ten, shaped alike, and dx [B, S, Cin].  16-byte aligned.  NULL = not wanted: neither
+ * computed nor written, and a launch none of whose outputs is wanted is not made. */
+typedef struct ns_pg_grads {
+  float *w1, *b1, *ln1_g, *ln1_b, *w2, *b2, *ln2_g, *ln2_b, *wlin, *blin, *dx;
+} ns_pg_grads;
+/* Host only.  The split of the weight gradient dW[n][c][j] = sum_m dz[m, n] X[m + j - pad, c] (N x KW*Cin outputs, M contracted):
+ * out = {tile rows (n), tile columns (j*Cin + c), rows of m per range, ranges, tiles, workspace floats (< 2^31), accumulation chunk
+ * (rows of m; 0 = one sequential sum), 0}.  Range r contracts rows [r * rows, min(M, (r + 1) * rows)) and
+ * writes its partial tile to the workspace; a second pass sums the ranges in ascending order in float64.  Returns 0, or nonzero with
+ * ns_last_error() for a shape the kernels refuse. */
+int ns_pg_plan_wgrad(int M, int N, int Cin, int KW, int32_t out[8]);
+/* Bytes of the workspace of every ns_pg_* call of this shape (0 and ns_last_error() for a refused shape), and of `saved`
+ * (v1 = relu(conv1d_1), h1 = dropout_1(layer_norm_1(v1)), v2 = relu(conv1d_2): 3 * M * F floats). */
+size_t ns_pg_ws_bytes(const ns_pg_shape* shape);
+size_t ns_pg_saved_bytes(const ns_pg_shape* shape);
+/* Kernel launches the calling thread's last ns_pg_* call enqueued. */
+int ns_pg_last_launches(void);
+/* Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a pointer that is not
+ * 16-byte aligned, K even or <= 0, F not 256 or 512, Cin not a multiple of 4 (forward, backward and dgrad: of 16), B * S * max(F, Cin)
+ * >= 2^31, p_drop outside [0, 1), keep-masks without p_drop > 0 or p_drop > 0 without them, a workspace smaller than ns_pg_ws_bytes.
+ * pred [B, S] = mask ? +0.0 : h2 . wlin + blin.  mask: uint8 [B * S], 1 = padded, nullable.  saved: ns_pg_saved_bytes, or NULL
+ * (nothing kept: the no_grad forward).  Five launches. */
+int ns_pg_forward(const ns_pg_shape* shape, const ns_pg_weights* weights, const float* x, const uint8_t* mask, const uint8_t* keep1,
+                  const uint8_t* keep2, float p_drop, float* pred, void* saved, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of sum_m g[m] pred[m] with respect to every non-NULL member of grads, from `saved` as ns_pg_forward wrote it for the
+ * same arguments.  dp = mask ? +0.0 : g is a selection: a NaN in g behind the mask reaches nothing.  Up to ten launches. */
+int ns_pg_backward(const ns_pg_shape* shape, const ns_pg_weights* weights, const float* x, const uint8_t* mask, const uint8_t* keep1,
+                   const uint8_t* keep2, float p_drop, const void* saved, const float* g, const ns_pg_grads* grads, void* ws,
+                   size_t ws_bytes, void* stream);
+/* Each kernel alone.  dW [N, Cin, KW] (torch layout) and db [N] (nullable) from dz [B*S, N] and X [B*S, Cin]; a tap outside the
+ * utterance's [0, S) rows reads as zero. */
+int ns_pg_op_wgrad(const float* dz, const float* X, int B, int S, int N, int Cin, int KW, float* dW, float* db, void* ws, size_t ws_bytes,
+                   void* stream);
+/* dX [B*S, Cin] = sum_j sum_n dz[m - j + pad, n] W[n][c][j] from W [N, Cin, KW] in torch layout: the pack kernel, then the forward's
+ * Conv1D-as-GEMM on the transposed, tap-flipped weights. */
+int ns_pg_op_dgrad(const float* dz, const float* W, int B, int S, int N, int Cin, int KW, float* dX, void* ws, size_t ws_bytes, void* stream);
+/* The row-local backward of  y = dropout(LayerNorm(v)), v = relu(conv + b)  on M rows of F columns.  tail == 0: dy [M, F] is the
+ * upstream gradient of y.  tail != 0: the upstream is g [M] through Linear(F, 1) and the mask (dy is ignored), wlin / ln_b are read,
+ * d_wlin [F] and d_blin [1] are written.  Writes dz [M, F] = dv gated by v > 0, d_ln_g, d_ln_b, d_b [F] each (all required).  keep
+ * [M, F] iff p_drop > 0. */
+int ns_pg_op_row_backward(int tail, const float* dy, const float* g, const uint8_t* mask, const float* v, const float* ln_g,
+                          const float* ln_b, const float* wlin, const uint8_t* keep, float p_drop, int M, int F, float* dz, float* d_ln_g,
+                          float* d_ln_b, float* d_b, float* d_wlin, float* d_blin, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

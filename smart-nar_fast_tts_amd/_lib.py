@@ -70,6 +70,24 @@ class NsOptHyper(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("global_step", C.c_int64), ("fuse_clip", C.c_int32), ("zero_grads", C.c_int32)]
 
 
+class NsPgShape(C.Structure):
+    """``ns_pg_shape`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "S", "Cin", "F", "K")]
+
+
+PG_NAMES = ("w1", "b1", "ln1_g", "ln1_b", "w2", "b2", "ln2_g", "ln2_b", "wlin", "blin")
+
+
+class NsPgWeights(C.Structure):
+    """``ns_pg_weights`` (include/nar_fs2.h): the ten parameters in checkpoint layout."""
+    _fields_ = [(n, C.c_void_p) for n in PG_NAMES]
+
+
+class NsPgGrads(C.Structure):
+    """``ns_pg_grads`` (include/nar_fs2.h): the ten parameter gradients and ``dx``, each nullable."""
+    _fields_ = [(n, C.c_void_p) for n in PG_NAMES + ("dx",)]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -229,6 +247,17 @@ SIGNATURES = {
     "ns_lossg_record_bytes": (_Z, []),
     "ns_lossg_forward": (_I, [C.POINTER(NsLossArgs), _P, _Z, _P, _P, _P]),
     "ns_lossg_backward": (_I, [C.POINTER(NsLossArgs), _P, _P, C.POINTER(NsLossgGrads), _P]),
+    # VariancePredictor training forward and backward (predictor.VariancePredictor; handle-less)
+    "ns_pg_abi_version": (_I, []),
+    "ns_pg_plan_wgrad": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int32)]),
+    "ns_pg_ws_bytes": (_Z, [C.POINTER(NsPgShape)]),
+    "ns_pg_saved_bytes": (_Z, [C.POINTER(NsPgShape)]),
+    "ns_pg_last_launches": (_I, []),
+    "ns_pg_forward": (_I, [C.POINTER(NsPgShape), C.POINTER(NsPgWeights), _P, _P, _P, _P, _F, _P, _P, _P, _Z, _P]),
+    "ns_pg_backward": (_I, [C.POINTER(NsPgShape), C.POINTER(NsPgWeights), _P, _P, _P, _P, _F, _P, _P, C.POINTER(NsPgGrads), _P, _Z, _P]),
+    "ns_pg_op_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ns_pg_op_dgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "ns_pg_op_row_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

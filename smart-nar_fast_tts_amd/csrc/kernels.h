@@ -334,6 +334,40 @@ hipError_t launch_opt_scale(const OptTensor* table, int n_tensors, int n_chunks,
 hipError_t launch_opt_adam(const OptTensor* table, int n_tensors, int n_chunks, const OptHyper& h, float* exp_avg, float* exp_avg_sq,
                            const OptRecord* record, hipStream_t st);
 hipError_t launch_opt_zero(const OptTensor* table, int n_tensors, int n_chunks, hipStream_t st);
+// ---- VariancePredictor training forward / backward (predgrad.hip; model/modules.py:233-286) -------------------------------------
+// Weight gradient of a "same"-padded Conv1d over row-major activations: dW[n][c][j] = sum_m dz[m, n] X[m + j - pad, c], a
+// N x (KW * Cin) GEMM contracted over the M rows, split over row ranges (PgWgradPlan) whose partial tiles a second pass sums.
+constexpr int PG_TILE_N = 128, PG_TILE_C = 128, PG_STEP_ROWS = 16;  // output tile of a workgroup; rows of m per LDS stage
+constexpr int PG_WG_TARGET = 256;                                   // workgroups the split aims at: one per CU
+constexpr int PG_ROW_BLOCK = 64;                                    // rows per workgroup of the row backward = rows per column partial
+constexpr int PG_SLOTS = 5;                                         // column sums per row block: d_ln_g, d_ln_b, d_b, d_wlin, d_blin
+struct PgWgradPlan { int tile_n, tile_c, rows, ranges, tiles, chunk; long long ws_floats; };
+// a function of the shape (and of the process-wide accumulation chunk) alone; false: refused (N % 128, Cin % 4, sizes)
+bool pg_plan_wgrad(int M, int N, int Cin, int KW, PgWgradPlan* out);
+inline int pg_row_blocks(int M) { return (M + PG_ROW_BLOCK - 1) / PG_ROW_BLOCK; }
+// partial [ranges][N][KW * Cin] floats (uninitialised); two launches: the GEMM, then the fixed-order sum into dW [N][Cin][KW]
+hipError_t launch_pg_wgrad(const float* dz, const float* X, int M, int S, int N, int Cin, int KW, const PgWgradPlan& pl, float* partial,
+                           float* dW, hipStream_t st);
+// one launch, up to two convolutions (a null w skips one): w [N][Cin][KW] -> wp [N][KW*Cin] (the forward's form, nullable) and
+// wt [Cin][KW*N] with wt[c][j*N + n] = w[n][c][KW-1-j] (the data gradient's form, nullable)
+struct PgPack { const float* w; float* wp; float* wt; int N, Cin, KW; };
+hipError_t launch_pg_pack(const PgPack& a, const PgPack& b, hipStream_t st);
+// h [M, F] = (LayerNorm(v) * ln_g + ln_b) * keep * scale (h nullable); wlin != nullptr additionally pred[m] = mask[m] ? +0 : h[m] . wlin + blin
+hipError_t launch_pg_row_forward(const float* v, const float* ln_g, const float* ln_b, const uint8_t* keep, float scale, float* h,
+                                 const float* wlin, const float* blin, const uint8_t* mask, float* pred, int M, int F, hipStream_t st);
+// see ns_pg_op_row_backward (nar_fs2.h); part: [pg_row_blocks(M)][PG_SLOTS][F] doubles, uninitialised
+struct PgRowBackward {
+  int tail, M, F; float scale;
+  const float *dy, *g, *v, *ln_g, *ln_b, *wlin; const uint8_t *mask, *keep;
+  float* dz; double* part;
+};
+hipError_t launch_pg_row_backward(const PgRowBackward& a, hipStream_t st);
+// part[blk][0][:] = column sums of rows [64 blk, 64 blk + 64) of dz [M, F]
+hipError_t launch_pg_colsum(const float* dz, int M, int F, double* part, hipStream_t st);
+// out[i][:] = sum over blocks, ascending, of part[i / PG_SLOTS][blk][i % PG_SLOTS][:] for the up to 2 * PG_SLOTS non-null outputs
+// (slot 4 is a scalar: column 0 only); part holds `stages` arrays of [nblk][PG_SLOTS][F] doubles
+struct PgColFinal { float* out[2 * PG_SLOTS]; };
+hipError_t launch_pg_col_final(const double* part, int nblk, int F, const PgColFinal& o, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

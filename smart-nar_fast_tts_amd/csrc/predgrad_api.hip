@@ -1,0 +1,282 @@
+// C-ABI of the VariancePredictor training forward and backward (include/nar_fs2.h ns_pg_*; model/modules.py:233-286).  No handle:
+// the weights are the caller's live tensors in checkpoint layout, the workspace and the saved activations belong to the caller.
+// Host-side only; every argument is validated before the first HIP call.
+#include "../../include/nar_fs2.h"
+#include "host_core.h"
+
+using namespace ns;
+
+static_assert(sizeof(ns_pg_shape) == 20, "ns_pg_shape layout");
+static_assert(sizeof(ns_pg_weights) == 10 * sizeof(void*) && sizeof(ns_pg_grads) == 11 * sizeof(void*), "ns_pg_weights / ns_pg_grads layout");
+
+namespace {
+thread_local int t_launches = 0;
+
+struct Ws {  // the workspace of one shape, carved in this order
+  float *w1p, *w1t, *w2p, *w2t;  // packed weights: forward form and data-gradient form of both convolutions
+  float* partial;                // the weight gradient's per-range tiles (the larger of the two convolutions')
+  double* colpart;               // [2][row blocks][PG_SLOTS][F]
+  float *a, *b, *c;              // [M, F] each: dz2 / dh1 / dz1 of the backward, v1 / h1 / v2 of a forward that saves nothing
+};
+
+int check_dims(int B, int S, int F, int Cin, int K, int cin_mult, const std::string& w) {
+  if (B <= 0 || S <= 0) return api_fail(w + "B and S must be positive, got " + std::to_string(B) + " x " + std::to_string(S));
+  if (K <= 0 || K % 2 == 0) return api_fail(w + "K must be odd, got " + std::to_string(K));
+  if (F != 256 && F != 512) return api_fail(w + "F must be 256 or 512, got " + std::to_string(F));
+  if (Cin <= 0 || Cin % cin_mult != 0) return api_fail(w + "Cin must be a multiple of " + std::to_string(cin_mult) + ", got " + std::to_string(Cin));
+  const long long M = (long long)B * S;
+  if (M * (F > Cin ? F : Cin) >= (1ll << 31)) return api_fail(w + "problem too large: B * S * max(F, Cin) must stay below 2^31");
+  return 0;
+}
+
+int carve(const ns_pg_shape& s, void* base, Ws* ws, size_t* bytes, const std::string& w) {
+  const int M = s.B * s.S;
+  PgWgradPlan p1, p2;
+  if (!pg_plan_wgrad(M, s.F, s.Cin, s.K, &p1) || !pg_plan_wgrad(M, s.F, s.F, s.K, &p2)) return api_fail(w + "problem too large for the weight gradient's split");
+  Bump bump(base);
+  const size_t n1 = (size_t)s.F * s.K * s.Cin, n2 = (size_t)s.F * s.K * s.F, mf = (size_t)M * s.F;
+  ws->w1p = bump.f(n1); ws->w1t = bump.f(n1); ws->w2p = bump.f(n2); ws->w2t = bump.f(n2);
+  ws->partial = bump.f((size_t)(p1.ws_floats > p2.ws_floats ? p1.ws_floats : p2.ws_floats));
+  ws->colpart = (double*)bump.raw((size_t)2 * pg_row_blocks(M) * PG_SLOTS * s.F * sizeof(double));
+  ws->a = bump.f(mf); ws->b = bump.f(mf); ws->c = bump.f(mf);
+  *bytes = bump.off;
+  return 0;
+}
+
+bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+int check_drop(const uint8_t* keep1, const uint8_t* keep2, float p, const std::string& w) {
+  if (!(p >= 0.f && p < 1.f)) return api_fail(w + "p_drop must lie in [0, 1)");
+  if (p > 0.f && (!keep1 || !keep2)) return api_fail(w + "p_drop > 0 needs both keep-masks");
+  if (p == 0.f && (keep1 || keep2)) return api_fail(w + "keep-masks given although p_drop == 0");
+  if (misaligned(keep1) || misaligned(keep2)) return api_fail(w + "keep-masks must be 16-byte aligned");
+  return 0;
+}
+
+int check_weights(const ns_pg_weights* k, const std::string& w) {
+  const void* p[10] = {k->w1, k->b1, k->ln1_g, k->ln1_b, k->w2, k->b2, k->ln2_g, k->ln2_b, k->wlin, k->blin};
+  const char* names[10] = {"w1", "b1", "ln1_g", "ln1_b", "w2", "b2", "ln2_g", "ln2_b", "wlin", "blin"};
+  for (int i = 0; i < 10; ++i) {
+    if (!p[i]) return api_fail(w + "null weights->" + names[i]);
+    if (i < 9 ? misaligned(p[i]) : ((uintptr_t)p[i] & 3) != 0) return api_fail(w + "weights->" + names[i] + " must be 16-byte aligned");
+  }
+  return 0;
+}
+
+// Y [M, N] = act(conv(X [M, Cin], W packed [N][KW * Cin]) + bias) through the forward's dispatch; counts its launches
+int conv(const float* X, const float* W, const float* bias, float* Y, int M, int S, int N, int Cin, int KW, int pad, int act, hipStream_t st) {
+  ConvGemm p;
+  memset(&p, 0, sizeof(p));
+  p.X = X; p.ldx = Cin; p.W = W; p.bias = bias; p.Y = Y; p.ldy = N;
+  p.M = M; p.N = N; p.Cin = Cin; p.KW = KW; p.pad = pad; p.S = S; p.act = act; p.epi = EPI_NONE;
+  int rec[2][8];
+  const int n = conv_gemm_describe(M, N, Cin, KW, 0, rec);
+  if (n <= 0) return api_fail("ns_pg: the Conv1D-as-GEMM dispatch refuses this shape");
+  NS_HIP(launch_conv_gemm(p, st));
+  t_launches += n;
+  return 0;
+}
+}  // namespace
+
+extern "C" int ns_pg_abi_version(void) { return NS_PG_ABI_VERSION; }
+extern "C" int ns_pg_last_launches(void) { return t_launches; }
+
+extern "C" int ns_pg_plan_wgrad(int M, int N, int Cin, int KW, int32_t out[8]) {
+  if (!out) return api_fail("ns_pg_plan_wgrad: null argument");
+  PgWgradPlan p;
+  if (!pg_plan_wgrad(M, N, Cin, KW, &p))
+    return api_fail("ns_pg_plan_wgrad: refused (M > 0, N a multiple of 128, Cin a multiple of 4, KW odd, sizes below 2^31)");
+  out[0] = p.tile_n; out[1] = p.tile_c; out[2] = p.rows; out[3] = p.ranges; out[4] = p.tiles; out[5] = (int32_t)p.ws_floats; out[6] = p.chunk; out[7] = 0;
+  return 0;
+}
+
+extern "C" size_t ns_pg_ws_bytes(const ns_pg_shape* s) {
+  const std::string w = "ns_pg_ws_bytes: ";
+  if (!s) { api_fail(w + "null argument"); return 0; }
+  if (check_dims(s->B, s->S, s->F, s->Cin, s->K, 4, w)) return 0;
+  Ws ws; size_t bytes = 0;
+  if (carve(*s, nullptr, &ws, &bytes, w)) return 0;
+  return bytes;
+}
+
+extern "C" size_t ns_pg_saved_bytes(const ns_pg_shape* s) {
+  const std::string w = "ns_pg_saved_bytes: ";
+  if (!s) { api_fail(w + "null argument"); return 0; }
+  if (check_dims(s->B, s->S, s->F, s->Cin, s->K, 4, w)) return 0;
+  return (size_t)3 * s->B * s->S * s->F * sizeof(float);
+}
+
+extern "C" int ns_pg_forward(const ns_pg_shape* s, const ns_pg_weights* k, const float* x, const uint8_t* mask, const uint8_t* keep1,
+                             const uint8_t* keep2, float p_drop, float* pred, void* saved, void* ws_mem, size_t ws_bytes, void* stream) {
+  const std::string w = "ns_pg_forward: ";
+  t_launches = 0;
+  if (!s || !k || !x || !pred || !ws_mem) return api_fail(w + "null argument");
+  NS_TRY(check_dims(s->B, s->S, s->F, s->Cin, s->K, 16, w));
+  NS_TRY(check_weights(k, w));
+  NS_TRY(check_drop(keep1, keep2, p_drop, w));
+  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem) || ((uintptr_t)pred & 3)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
+  Ws ws; size_t need = 0;
+  NS_TRY(carve(*s, ws_mem, &ws, &need, w));
+  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_pg_ws_bytes)");
+  const int M = s->B * s->S, F = s->F, K = s->K, pad = (K - 1) / 2;
+  const size_t mf = (size_t)M * F;
+  float* v1 = saved ? (float*)saved : ws.a;
+  float* h1 = saved ? v1 + mf : ws.b;
+  float* v2 = saved ? v1 + 2 * mf : ws.c;
+  const float scale = 1.f / (1.f - p_drop);
+  hipStream_t st = (hipStream_t)stream;
+  NS_HIP(launch_pg_pack(PgPack{k->w1, ws.w1p, nullptr, F, s->Cin, K}, PgPack{k->w2, ws.w2p, nullptr, F, F, K}, st));
+  ++t_launches;
+  NS_TRY(conv(x, ws.w1p, k->b1, v1, M, s->S, F, s->Cin, K, pad, ACT_RELU, st));
+  NS_HIP(launch_pg_row_forward(v1, k->ln1_g, k->ln1_b, keep1, scale, h1, nullptr, nullptr, nullptr, nullptr, M, F, st));
+  ++t_launches;
+  NS_TRY(conv(h1, ws.w2p, k->b2, v2, M, s->S, F, F, K, pad, ACT_RELU, st));
+  NS_HIP(launch_pg_row_forward(v2, k->ln2_g, k->ln2_b, keep2, scale, nullptr, k->wlin, k->blin, mask, pred, M, F, st));
+  ++t_launches;
+  return 0;
+}
+
+extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, const float* x, const uint8_t* mask, const uint8_t* keep1,
+                              const uint8_t* keep2, float p_drop, const void* saved, const float* g, const ns_pg_grads* d, void* ws_mem,
+                              size_t ws_bytes, void* stream) {
+  const std::string w = "ns_pg_backward: ";
+  t_launches = 0;
+  if (!s || !k || !x || !saved || !g || !d || !ws_mem) return api_fail(w + "null argument");
+  NS_TRY(check_dims(s->B, s->S, s->F, s->Cin, s->K, 16, w));
+  NS_TRY(check_weights(k, w));
+  NS_TRY(check_drop(keep1, keep2, p_drop, w));
+  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem) || ((uintptr_t)g & 3)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
+  float* outs[11] = {d->w1, d->b1, d->ln1_g, d->ln1_b, d->w2, d->b2, d->ln2_g, d->ln2_b, d->wlin, d->blin, d->dx};
+  for (int i = 0; i < 11; ++i)
+    if (i == 9 ? ((uintptr_t)outs[i] & 3) != 0 : misaligned(outs[i])) return api_fail(w + "every gradient must be 16-byte aligned");
+  Ws ws; size_t need = 0;
+  NS_TRY(carve(*s, ws_mem, &ws, &need, w));
+  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_pg_ws_bytes)");
+  const int M = s->B * s->S, F = s->F, Cin = s->Cin, K = s->K, padT = K - 1 - (K - 1) / 2;
+  const size_t mf = (size_t)M * F;
+  const float* v1 = (const float*)saved;
+  const float* h1 = v1 + mf;
+  const float* v2 = v1 + 2 * mf;
+  const float scale = 1.f / (1.f - p_drop);
+  hipStream_t st = (hipStream_t)stream;
+  const bool stage1 = d->w1 || d->b1 || d->ln1_g || d->ln1_b || d->dx;  // anything upstream of conv1d_2's input
+  const bool stage2 = stage1 || d->w2 || d->b2 || d->ln2_g || d->ln2_b || d->wlin || d->blin;
+  if (!stage2) return 0;
+  PgWgradPlan p1, p2;
+  pg_plan_wgrad(M, F, Cin, K, &p1);  // (both accepted by carve above)
+  pg_plan_wgrad(M, F, F, K, &p2);
+  const int nblk = pg_row_blocks(M);
+
+  if (stage1 || d->dx) {
+    NS_HIP(launch_pg_pack(PgPack{d->dx ? k->w1 : nullptr, nullptr, ws.w1t, F, Cin, K}, PgPack{stage1 ? k->w2 : nullptr, nullptr, ws.w2t, F, F, K}, st));
+    ++t_launches;
+  }
+  PgRowBackward r;
+  memset(&r, 0, sizeof(r));
+  r.tail = 1; r.M = M; r.F = F; r.scale = scale; r.g = g; r.mask = mask; r.v = v2; r.ln_g = k->ln2_g; r.ln_b = k->ln2_b; r.wlin = k->wlin;
+  r.keep = keep2; r.dz = ws.a; r.part = ws.colpart;
+  NS_HIP(launch_pg_row_backward(r, st));
+  ++t_launches;
+  if (d->w2) {
+    NS_HIP(launch_pg_wgrad(ws.a, h1, M, s->S, F, F, K, p2, ws.partial, d->w2, st));
+    t_launches += 2;
+  }
+  if (stage1) {
+    NS_TRY(conv(ws.a, ws.w2t, nullptr, ws.b, M, s->S, F, F, K, padT, ACT_NONE, st));
+    memset(&r, 0, sizeof(r));
+    r.tail = 0; r.M = M; r.F = F; r.scale = scale; r.dy = ws.b; r.v = v1; r.ln_g = k->ln1_g; r.keep = keep1; r.dz = ws.c;
+    r.part = ws.colpart + (size_t)nblk * PG_SLOTS * F;
+    NS_HIP(launch_pg_row_backward(r, st));
+    ++t_launches;
+    if (d->w1) {
+      NS_HIP(launch_pg_wgrad(ws.c, x, M, s->S, F, Cin, K, p1, ws.partial, d->w1, st));
+      t_launches += 2;
+    }
+    if (d->dx) NS_TRY(conv(ws.c, ws.w1t, nullptr, d->dx, M, s->S, Cin, F, K, padT, ACT_NONE, st));
+  }
+  PgColFinal fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.out[0] = d->ln2_g; fin.out[1] = d->ln2_b; fin.out[2] = d->b2; fin.out[3] = d->wlin; fin.out[4] = d->blin;
+  if (stage1) { fin.out[PG_SLOTS + 0] = d->ln1_g; fin.out[PG_SLOTS + 1] = d->ln1_b; fin.out[PG_SLOTS + 2] = d->b1; }
+  bool any = false;
+  for (int i = 0; i < 2 * PG_SLOTS; ++i) any = any || fin.out[i];
+  if (any) {
+    NS_HIP(launch_pg_col_final(ws.colpart, nblk, F, fin, st));
+    ++t_launches;
+  }
+  return 0;
+}
+
+extern "C" int ns_pg_op_wgrad(const float* dz, const float* X, int B, int S, int N, int Cin, int KW, float* dW, float* db, void* ws_mem,
+                              size_t ws_bytes, void* stream) {
+  const std::string w = "ns_pg_op_wgrad: ";
+  t_launches = 0;
+  if (!dz || !X || !dW || !ws_mem) return api_fail(w + "null argument");
+  NS_TRY(check_dims(B, S, N, Cin, KW, 4, w));
+  if (misaligned(dz) || misaligned(X) || misaligned(dW) || misaligned(db) || misaligned(ws_mem)) return api_fail(w + "every pointer must be 16-byte aligned");
+  const int M = B * S;
+  PgWgradPlan pl;
+  if (!pg_plan_wgrad(M, N, Cin, KW, &pl)) return api_fail(w + "problem too large for the weight gradient's split");
+  Bump bump(ws_mem);
+  float* partial = bump.f((size_t)pl.ws_floats);
+  double* colpart = (double*)bump.raw((size_t)pg_row_blocks(M) * PG_SLOTS * N * sizeof(double));
+  if (ws_bytes < bump.off) return api_fail(w + "workspace too small: " + std::to_string(bump.off) + " bytes needed");
+  hipStream_t st = (hipStream_t)stream;
+  NS_HIP(launch_pg_wgrad(dz, X, M, S, N, Cin, KW, pl, partial, dW, st));
+  t_launches += 2;
+  if (db) {
+    NS_HIP(launch_pg_colsum(dz, M, N, colpart, st));
+    PgColFinal fin;
+    memset(&fin, 0, sizeof(fin));
+    fin.out[0] = db;
+    NS_HIP(launch_pg_col_final(colpart, pg_row_blocks(M), N, fin, st));
+    t_launches += 2;
+  }
+  return 0;
+}
+
+extern "C" int ns_pg_op_dgrad(const float* dz, const float* W, int B, int S, int N, int Cin, int KW, float* dX, void* ws_mem, size_t ws_bytes,
+                              void* stream) {
+  const std::string w = "ns_pg_op_dgrad: ";
+  t_launches = 0;
+  if (!dz || !W || !dX || !ws_mem) return api_fail(w + "null argument");
+  NS_TRY(check_dims(B, S, N, Cin, KW, 16, w));
+  if (misaligned(dz) || misaligned(W) || misaligned(dX) || misaligned(ws_mem)) return api_fail(w + "every pointer must be 16-byte aligned");
+  Bump bump(ws_mem);
+  float* wt = bump.f((size_t)N * Cin * KW);
+  if (ws_bytes < bump.off) return api_fail(w + "workspace too small: " + std::to_string(bump.off) + " bytes needed");
+  hipStream_t st = (hipStream_t)stream;
+  NS_HIP(launch_pg_pack(PgPack{W, nullptr, wt, N, Cin, KW}, PgPack{nullptr, nullptr, nullptr, 0, 0, 0}, st));
+  ++t_launches;
+  return conv(dz, wt, nullptr, dX, B * S, S, Cin, N, KW, KW - 1 - (KW - 1) / 2, ACT_NONE, st);
+}
+
+extern "C" int ns_pg_op_row_backward(int tail, const float* dy, const float* g, const uint8_t* mask, const float* v, const float* ln_g,
+                                     const float* ln_b, const float* wlin, const uint8_t* keep, float p_drop, int M, int F, float* dz,
+                                     float* d_ln_g, float* d_ln_b, float* d_b, float* d_wlin, float* d_blin, void* ws_mem, size_t ws_bytes,
+                                     void* stream) {
+  const std::string w = "ns_pg_op_row_backward: ";
+  t_launches = 0;
+  if (!v || !ln_g || !dz || !d_ln_g || !d_ln_b || !d_b || !ws_mem) return api_fail(w + "null argument");
+  if (tail ? (!g || !ln_b || !wlin || !d_wlin || !d_blin) : !dy) return api_fail(w + "null argument");
+  NS_TRY(check_dims(M, 1, F, 4, 1, 4, w));
+  NS_TRY(check_drop(keep, keep, p_drop, w));
+  const void* al[] = {dy, v, ln_g, ln_b, wlin, dz, d_ln_g, d_ln_b, d_b, d_wlin, ws_mem};
+  for (const void* p : al)
+    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
+  const size_t need = (size_t)pg_row_blocks(M) * PG_SLOTS * F * sizeof(double);
+  if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
+  PgRowBackward r;
+  memset(&r, 0, sizeof(r));
+  r.tail = tail != 0; r.M = M; r.F = F; r.scale = 1.f / (1.f - p_drop); r.dy = dy; r.g = g; r.mask = tail ? mask : nullptr; r.v = v;
+  r.ln_g = ln_g; r.ln_b = ln_b; r.wlin = wlin; r.keep = keep; r.dz = dz; r.part = (double*)ws_mem;
+  hipStream_t st = (hipStream_t)stream;
+  NS_HIP(launch_pg_row_backward(r, st));
+  PgColFinal fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.out[0] = d_ln_g; fin.out[1] = d_ln_b; fin.out[2] = d_b;
+  if (tail) { fin.out[3] = d_wlin; fin.out[4] = d_blin; }
+  NS_HIP(launch_pg_col_final(r.part, pg_row_blocks(M), F, fin, st));
+  t_launches += 2;
+  return 0;
+}

@@ -1,0 +1,341 @@
+"""The VariancePredictor training forward and backward on the GPU (csrc/predgrad.hip through ns_pg_* and predictor.VariancePredictor).
+
+Each kernel alone — the weight gradient (with db, K = 3 and 5, the workspace filled with 0xFF beforehand), the data gradient, the row
+backward in both instantiations with and without keep-masks — then the whole module: the saved activations and pred against float64
+of their own inputs at the existing bounds (tests/bf16_emu.py, PRED_TIGHT), every gradient at the project gate of
+tests/predictor_grad_cpu.py judged from the DEVICE's saved activations, needs_input_grad, run-to-run bits, and one native training
+step into optim.ScheduledOptim.  The yardstick itself is proven in tests/test_predictor_grad_host.py.
+
+Not reachable: ops-level launch_conv_gemm takes a loaded model's named weights only, so the data gradient is not compared bitwise with a
+hand-packed W' through ops; it is held to the contraction contract against float64 instead.
+
+NS_FP32_OPS_REPORT=<path> appends every measured share as a JSON line (profiles/predictor_grad_r16.md was written from one).
+
+Measured on the MI355X (profiles/predictor_grad_r16.md): every gradient at or below 0.42 of its gate, pred at most 0.053 and the saved
+activations 0.013 of their bounds, wgrad alone 0.068 and dgrad alone 0.014 of the contraction contract, the row backward alone 0.20, the
+native step 0.21 of optim_cpu.gate_of."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import tests.test_predictor_ops_host as P
+from tests import bf16_emu as E
+from tests import lossgrad_cpu as lg
+from tests import optim_cpu as oc
+from tests import predictor_grad_cpu as pc
+from tests.test_gpu_fp32_ops import _report
+from tests.util import load_golden
+
+pytestmark = pytest.mark.gpu
+REL = E.FP32_REL
+F = P.F
+CASES = [(5, 1, [1] * 5), (5, 3, [3, 2, 1, 3, 3]), (4, 33, [33, 0, 20, 33]), (3, 343, [343] * 3), (7, 911, [911, 640, 3, 877, 420, 911, 129])]
+CONFIGS = {"tiny": 256, "tiny512": 512}
+_id = lambda c: f"{c[0]}x{c[1]}"  # noqa: E731
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+@pytest.fixture(scope="module")
+def so():
+    import smart_nar_fast_tts_amd._lib as L
+
+    return L, L.load()
+
+
+def _plan(so, M, N, Cin, K):
+    out = (C.c_int32 * 8)()
+    assert so[1].ns_pg_plan_wgrad(M, N, Cin, K, out) == 0
+    return list(out)
+
+
+def _ws(nbytes=96 << 20, fill=0xFF):
+    return torch.full((nbytes,), fill, dtype=torch.uint8, device="cuda")
+
+
+def _check(L, rc, what):
+    L.check(rc, what)
+
+
+# ---------------------------------------------------------------------------------------------------- each kernel alone
+def test_cases_split_the_rows(so):
+    for B, S, _ in CASES[3:]:
+        for Cin in CONFIGS.values():
+            for K in (3, 5):
+                _, _, rows, ranges, *_ = _plan(so, B * S, F, Cin, K)
+                assert ranges >= 2 and (B * S) % rows != 0
+
+
+@pytest.mark.parametrize("K", [3, 5])
+@pytest.mark.parametrize("case", CASES, ids=_id)
+def test_wgrad_alone_elementwise(so, case, K):
+    L, lib = so
+    B, S, _ = case
+    Cin = 512 if (B, S, K) == (3, 343, 3) else 256
+    M = B * S
+    rs = np.random.RandomState(B * S + K)
+    dz, x = rs.standard_normal((B, S, F)).astype(np.float32), rs.standard_normal((B, S, Cin)).astype(np.float32)
+    ws = _ws()
+    dW = torch.full((F, Cin, K), float("nan"), device="cuda")
+    db = torch.full((F,), float("nan"), device="cuda")
+    dz_d, x_d = dev(dz), dev(x)  # (named: a temporary's block would be handed to the next one)
+    _check(L, lib.ns_pg_op_wgrad(L.ptr(dz_d), L.ptr(x_d), B, S, F, Cin, K, L.ptr(dW), L.ptr(db), L.ptr(ws), ws.numel(), L.stream_ptr()), "ns_pg_op_wgrad")
+    assert lib.ns_pg_last_launches() == 4
+    dz64, x64 = torch.from_numpy(dz).double(), torch.from_numpy(x).double()
+    ref, unit = pc.wgrad(dz64, x64, K, (K - 1) // 2), pc.wgrad(dz64.abs(), x64.abs(), K, (K - 1) // 2)
+    got = dW.cpu().double()
+    assert bool(torch.isfinite(got).all())
+    share = float(((got - ref).abs() / (REL * unit).clamp_min(1e-300)).max())
+    assert bool(((got - ref).abs() <= REL * unit).all()), share
+    ref_b, unit_b = dz64.reshape(M, F).sum(0), dz64.abs().reshape(M, F).sum(0)
+    got_b = db.cpu().double()
+    share_b = float(((got_b - ref_b).abs() / (REL * unit_b)).max())
+    assert bool(torch.isfinite(got_b).all()) and share_b <= 1.0
+    # the wrong padding (the neighbouring utterance's row) is outside the bound wherever an utterance boundary exists
+    if B > 1 and S > 1:
+        cross = pc.wgrad(dz64, x64, K, (K - 1) // 2, cross=True)
+        assert not bool(((cross - ref).abs() <= REL * unit).all())
+    _report(test="pg_wgrad", case=_id(case), K=K, Cin=Cin, ranges=_plan(so, M, F, Cin, K)[3], share=share, share_db=share_b)
+
+
+@pytest.mark.parametrize("K", [3, 5])
+@pytest.mark.parametrize("case", CASES, ids=_id)
+def test_dgrad_alone_elementwise(so, case, K):
+    L, lib = so
+    B, S, _ = case
+    Cin = 512 if (B, S, K) == (3, 343, 3) else 256
+    rs = np.random.RandomState(B * S + K + 1)
+    dz = rs.standard_normal((B, S, F)).astype(np.float32)
+    w = (rs.standard_normal((F, Cin, K)) * (F * K) ** -0.5).astype(np.float32)
+    ws = _ws(8 << 20)
+    dX = torch.full((B, S, Cin), float("nan"), device="cuda")
+    dz_d, w_d = dev(dz), dev(w)
+    _check(L, lib.ns_pg_op_dgrad(L.ptr(dz_d), L.ptr(w_d), B, S, F, Cin, K, L.ptr(dX), L.ptr(ws), ws.numel(), L.stream_ptr()), "ns_pg_op_dgrad")
+    dz64, w64 = torch.from_numpy(dz).double(), torch.from_numpy(w).double()
+    ref, unit = pc.dgrad(dz64, w64, (K - 1) // 2), pc.dgrad(dz64.abs(), w64.abs(), (K - 1) // 2)
+    got = dX.cpu().double()
+    share = float(((got - ref).abs() / (REL * unit).clamp_min(1e-300)).max())
+    assert bool(torch.isfinite(got).all()) and bool(((got - ref).abs() <= REL * unit).all()), share
+    if K > 1 and S > 1:
+        noflip = pc.dgrad(dz64, w64, (K - 1) // 2, mutate="dgrad_without_tap_flip")
+        assert not bool(((noflip - ref).abs() <= REL * unit).all())
+    _report(test="pg_dgrad", case=_id(case), K=K, Cin=Cin, share=share)
+
+
+def _row_ref(tail, up, g, mask, v, w, keep, p, dtype):
+    """the row backward alone in dtype: dict of dz, d_ln_g, d_ln_b, d_b (and d_wlin, d_blin)"""
+    t = lambda a: torch.as_tensor(a).to(dtype)  # noqa: E731
+    k = None if keep is None else t(keep) * torch.tensor(1.0 / (1.0 - p), dtype=dtype)
+    v = t(v)
+    if tail:
+        dp = torch.where(torch.as_tensor(mask).bool(), torch.zeros((), dtype=dtype), t(g))
+        up_ = dp[:, None] * t(w["wlin"])
+    else:
+        up_ = t(up)
+    dz, d_g, d_b, xh = pc.row_backward(up_, v, t(w["g"]), k)
+    out = dict(dz=dz, d_ln_g=d_g, d_ln_b=d_b, d_b=dz.sum(0))
+    if tail:
+        h = xh * t(w["g"]) + t(w["b"])
+        h = h if k is None else h * k
+        out.update(d_wlin=(dp[:, None] * h).sum(0), d_blin=dp.sum().reshape(1))
+    return {n: a.numpy() for n, a in out.items()}
+
+
+@pytest.mark.parametrize("Fw", [256, 512])
+@pytest.mark.parametrize("p", [0.0, 0.5])
+@pytest.mark.parametrize("tail", [0, 1])
+def test_row_backward_alone(so, tail, p, Fw):
+    """197 rows: past one workgroup's 64 (four column partials, the last one of 5 rows)"""
+    L, lib = so
+    M = 197
+    rs = np.random.RandomState(17 + tail + Fw)
+    v = np.maximum(rs.standard_normal((M, Fw)) + 0.3, 0).astype(np.float32)  # what a ReLU leaves: about a third exact zeros
+    up, g = rs.standard_normal((M, Fw)).astype(np.float32), rs.standard_normal(M).astype(np.float32)
+    mask = rs.rand(M) < 0.3
+    g[np.flatnonzero(mask)[:3]] = np.nan  # behind the mask
+    w = dict(g=(1 + 0.2 * rs.standard_normal(Fw)).astype(np.float32), b=(0.1 * rs.standard_normal(Fw)).astype(np.float32),
+             wlin=(rs.standard_normal(Fw) * Fw ** -0.5).astype(np.float32))
+    keep = (rs.rand(M, Fw) >= p) if p > 0 else None
+    outs = {n: torch.full(s, float("nan"), device="cuda") for n, s in (("dz", (M, Fw)), ("d_ln_g", (Fw,)), ("d_ln_b", (Fw,)), ("d_b", (Fw,)), ("d_wlin", (Fw,)), ("d_blin", (1,)))}
+    ws = _ws(4 << 20)
+    keep_d = None if keep is None else dev(keep.astype(np.uint8))
+    d = {n: dev(a) for n, a in dict(up=up, g=g, mask=mask.astype(np.uint8), v=v, ln_g=w["g"], ln_b=w["b"], wlin=w["wlin"]).items()}
+    _check(L, lib.ns_pg_op_row_backward(tail, L.ptr(d["up"]), L.ptr(d["g"]), L.ptr(d["mask"]), L.ptr(d["v"]), L.ptr(d["ln_g"]), L.ptr(d["ln_b"]),
+                                        L.ptr(d["wlin"]), L.ptr(keep_d), p, M, Fw, *[L.ptr(outs[n]) for n in ("dz", "d_ln_g", "d_ln_b", "d_b", "d_wlin", "d_blin")],
+                                        L.ptr(ws), ws.numel(), L.stream_ptr()), "ns_pg_op_row_backward")
+    r64, r32 = _row_ref(tail, up, g, mask, v, w, keep, p, torch.float64), _row_ref(tail, up, g, mask, v, w, keep, p, torch.float32)
+    worst = {}
+    for n in r64:
+        got = outs[n].cpu().numpy().astype(np.float64)
+        gate = 2.0 * float(np.abs(r32[n].astype(np.float64) - r64[n]).max()) + lg.ulp32(np.abs(r64[n]).max())
+        assert np.isfinite(got).all(), n
+        worst[n] = float(np.abs(got - r64[n]).max() / gate)
+    if not tail:
+        assert torch.isnan(outs["d_wlin"]).all() and torch.isnan(outs["d_blin"]).all()  # not written
+    else:
+        assert not outs["dz"][dev(mask)].any()  # +0 behind the mask, NaN in g or not
+    assert (outs["dz"][dev(v) <= 0] == 0).all()
+    _report(test="pg_row_backward", tail=tail, p=p, F=Fw, shares=worst)
+    assert max(worst.values()) <= 1.0, worst
+
+
+# ---------------------------------------------------------------------------------------------------- the whole module
+_MODULES = {}
+
+
+def module(config, which="pitch"):
+    from smart_nar_fast_tts_amd import predictor
+    import smart_nar_fast_tts_amd.workload as wl
+
+    if config not in _MODULES:
+        w = P.pred_weights(config, which)
+        m = predictor.VariancePredictor(wl.model_config(config))
+        sd = dict(zip(predictor.PARAM_NAMES, (w[k] for k in ("w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2"))))
+        sd["linear_layer.weight"], sd["linear_layer.bias"] = w["wlin"].reshape(1, -1), w["blin"].reshape(1)
+        m.load_state_dict(sd)
+        _MODULES[config] = (m.cuda(), {k: w[k] for k in pc.NAMES[:10]})
+    return _MODULES[config]
+
+
+def _inputs(config, case, nan_behind_mask):
+    B, S, lens = case
+    x = P.x_of(B, S, CONFIGS[config], seed=B * S + 5)
+    mask = pc.mask_of(lens, S)
+    g = np.random.RandomState(B * S + 9).standard_normal((B, S)).astype(np.float32)
+    if nan_behind_mask and mask.any():
+        g[mask] = np.where(np.arange(int(mask.sum())) % 2 == 0, np.nan, g[mask])
+    return x, mask, g
+
+
+def _run(m, x, mask, g, keeps=None, need=None):
+    """one forward + backward through the module's own marshalling: (pred, saved (v1, h1, v2), grads by pc.NAMES, launches)"""
+    m.train(keeps is not None)
+    call = m._marshal(dev(x.numpy()), dev(mask), None if keeps is None else tuple(dev(k) for k in keeps))
+    pred, saved = m._forward(call, save=True)
+    need = [True] * 11 if need is None else need
+    outs = m._backward(call, saved, dev(g), need)
+    B, S = mask.shape
+    sv = saved.cpu().reshape(3, B, S, -1)
+    grads = dict(zip(("dx",) + pc.NAMES[:10], (None if o is None else o.cpu().numpy().reshape(-1) for o in outs)))
+    return pred.cpu(), sv, grads, dict(m.last_launches)
+
+
+def _flat(ref):
+    return {n: np.asarray(a).reshape(-1) for n, a in ref.items() if n in pc.NAMES}
+
+
+@pytest.mark.parametrize("config", list(CONFIGS))
+@pytest.mark.parametrize("case", CASES, ids=_id)
+def test_module_forward_and_backward(config, case):
+    m, w = module(config)
+    B, S, lens = case
+    # ---- eval (no dropout), g = randn: the saved activations and pred at their bounds, then every gradient at the gate
+    x, mask, g = _inputs(config, case, False)
+    pred, (v1, h1, v2), grads, launches = _run(m, x, mask, g)
+    pw = P.pred_weights(config, "pitch")
+    c1 = E.gemm_check(v1, x, pw["w1"], pw["b1"], act="relu", rel=REL, round_fn=E.exact)
+    c2 = P.stage1_check(h1, x, pw)
+    c3 = E.gemm_check(v2, h1, pw["w2"], pw["b2"], act="relu", rel=REL, round_fn=E.exact)
+    ref, bound = P.tail_ref(h1, pw, lens)
+    c4 = E.pred_check(pred, ref, bound, P.PRED_TIGHT)
+    assert c1.ok and c2.ok and c3.ok and c4.ok, (str(c1), str(c2), str(c3), str(c4))
+    assert not pred[torch.from_numpy(mask)].view(torch.int32).any()  # +0.0 at masked positions
+    r64 = _flat(pc.closed_form(x, w, mask, g, (v1, h1, v2), dtype=torch.float64))
+    r32 = _flat(pc.closed_form(x, w, mask, g, (v1, h1, v2), dtype=torch.float32))
+    gates = pc.gate(r32, r64)
+    sh = pc.shares(grads, r64, gates)
+    _report(test="pg_module", config=config, case=_id(case), mode="eval", launches=launches, v1=c1.worst, h1=c2.worst, v2=c3.worst, pred=c4.worst, shares=sh)
+    assert max(sh.values()) <= 1.0, sh
+    # ---- train with keep-masks at p = dropout, NaN in g behind the mask
+    rs = np.random.RandomState(B * S + 3)
+    keeps = tuple(rs.rand(B, S, F) >= m.dropout for _ in range(2))
+    x, mask, g = _inputs(config, case, True)
+    g0 = np.where(mask, 0.0, g).astype(np.float32)
+    pred, (v1, h1, v2), grads, launches = _run(m, x, mask, g, keeps)
+    r64 = _flat(pc.closed_form(x, w, mask, g0, (v1, h1, v2), keeps, m.dropout, torch.float64))
+    r32 = _flat(pc.closed_form(x, w, mask, g0, (v1, h1, v2), keeps, m.dropout, torch.float32))
+    sh = pc.shares(grads, r64, pc.gate(r32, r64))
+    _report(test="pg_module", config=config, case=_id(case), mode="train_nan_behind_mask", launches=launches, shares=sh)
+    assert max(sh.values()) <= 1.0, sh
+    # the dropped h1 is the kept fp32 LayerNorm rows times 1 / (1 - p): zero exactly where the mask drops
+    assert not h1[torch.from_numpy(~keeps[0])].any()
+
+
+def test_needs_input_grad_and_run_to_run_bits():
+    m, w = module("tiny")
+    m.eval()
+    case = CASES[2]
+    x, mask, g = _inputs("tiny", case, True)
+    params = m.ordered_parameters()
+
+    def once(x_grad=True, frozen=()):
+        for i, p in enumerate(params):
+            p.requires_grad_(i not in frozen)
+            p.grad = None
+        xd = dev(x.numpy()).requires_grad_(x_grad)
+        pred = m(xd, dev(mask))
+        pred.backward(dev(g))
+        bits = [None if p.grad is None else p.grad.cpu().numpy().tobytes() for p in params]
+        return pred.detach().cpu().numpy().tobytes(), bits, None if xd.grad is None else xd.grad.cpu().numpy().tobytes(), dict(m.last_launches)
+
+    try:
+        a, b = once(), once()
+        assert a[:3] == b[:3], "two runs give identical bits"
+        assert a[2] is not None and all(v is not None for v in a[1])
+        nx = once(x_grad=False)
+        assert nx[2] is None and nx[1] == a[1] and nx[0] == a[0]
+        assert nx[3]["backward"] == a[3]["backward"] - 1, (nx[3], a[3])  # no dX GEMM
+        fz = once(frozen=(0,))
+        assert fz[1][0] is None and fz[1][1:] == a[1][1:] and fz[2] == a[2]
+        assert fz[3]["backward"] == a[3]["backward"] - 2, (fz[3], a[3])  # no wgrad, no reduce
+        with torch.no_grad():
+            quiet = m(dev(x.numpy()), dev(mask))
+        assert quiet.cpu().numpy().tobytes() == a[0] and not quiet.requires_grad
+        _report(test="pg_launches", forward=a[3]["forward"], backward=a[3]["backward"], backward_no_dx=nx[3]["backward"], backward_frozen_w1=fz[3]["backward"])
+    finally:
+        for p in params:
+            p.requires_grad_(True)
+            p.grad = None
+
+
+def test_one_native_training_step():
+    """loss gradient (the tiny lossgrad fixture's d_pitch) -> this module's backward -> optim.ScheduledOptim.step_and_update_lr():
+    the ten updated tensors against the float64 chain at optim_cpu.gate_of of torch's fp32 CPU chain"""
+    import smart_nar_fast_tts_amd.workload as wl
+    from smart_nar_fast_tts_amd import optim, predictor
+
+    meta, z = load_golden("lossgrad_tiny")
+    _, zt = load_golden(meta["source"])
+    g32, g64, mask = z["pitch"], z["pitch_f64"], zt["mel_masks"].astype(bool)
+    B, S = g32.shape
+    w = {k: P.pred_weights("tiny", "pitch")[k] for k in pc.NAMES[:10]}
+    m = predictor.VariancePredictor(wl.model_config("tiny"))
+    src, _ = module("tiny")
+    m.load_state_dict(src.state_dict())
+    m = m.cuda().eval()
+    x = P.x_of(B, S, 256, seed=77)
+    start = 3998
+    cfg = {"optimizer": dict(betas=list(oc.BETAS), eps=oc.EPS, weight_decay=0.0, **oc.SHIPPED)}
+    so = optim.ScheduledOptim(m, cfg, {"transformer": {"encoder_hidden": oc.ENCODER_HIDDEN}}, start)
+    pred = m(dev(x.numpy()), dev(mask))
+    pred.backward(dev(g32))
+    so.step_and_update_lr()
+    lr = so._optimizer.param_groups[0]["lr"]
+    assert abs(lr - oc.lr_at(start + 1, **oc.SHIPPED)) <= 1e-12 * lr
+    got = [p.detach().cpu().numpy().reshape(-1) for p in m.ordered_parameters()]
+    chain = {}
+    for name, g, dtype in (("f64", g64, torch.float64), ("f32", g32, torch.float32)):
+        grads, _ = pc.autograd_ref(x, w, mask, g, dtype=dtype)
+        case = dict(params=[np.asarray(w[k], dtype=np.float32).reshape(-1) for k in pc.NAMES[:10]], grads=[[grads[k].reshape(-1) for k in pc.NAMES[:10]]],
+                    lrs=[lr], betas=oc.BETAS, eps=oc.EPS, weight_decay=0.0, max_norm=None)
+        chain[name] = oc.run(case)[0]["p"] if name == "f64" else oc.torch_run(case)[0]["p"]
+    sh = {}
+    for k, a, t32, w64 in zip(pc.NAMES[:10], got, chain["f32"], chain["f64"]):
+        err = np.abs(a.astype(np.float64) - w64).max()
+        sh[k] = float(err / oc.gate_of(t32, w64)) if np.isfinite(err) else float("inf")
+    _report(test="pg_native_step", shares=sh)
+    assert max(sh.values()) <= 1.0, sh

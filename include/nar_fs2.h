@@ -325,6 +325,60 @@ int ns_plan_gemm_bf16_ln(int M, int N, int Cin, int KW);
  * does (the partials its workspace reserves plus the op's ticket block); 0 = pass no scratch. */
 size_t ns_op_attention_scratch_bytes(int B, int S, int H, int dk);
 
+/* ---- Test hooks: one stage alone on PACKED rows (the default layout of ns_forward_mel_packed / ns_forward_durations_packed:
+ * utterance b owns the Mp-row matrix's rows [off[b], off[b] + win[b]), win[b] = min(max(len[b], 0) + guard, S)).  Each entry goes
+ * through the function the forwards call with a packed context; additions only, NS_ABI_VERSION is unchanged.  Every entry refuses
+ * null or inconsistent arguments before any device work.
+ *
+ * ns_op_pack_plan: Mp = sum of the windows and att_wgs = sum of ceil(win / 128) * H, computed on the host from lens_host by the
+ * forwards' own helpers; with lens_dev and plan_dev (both or neither) also the device plan, plan_ints >= 4 B + 4 + 3 Mp ints laid
+ * out as  off [B+1] | win [B], 1 unused | att_off [B+1] | att_order [B], 1 unused | row_b [Mp] | row_t [Mp] | row_w [Mp]
+ * (att_order: utterances by descending window, ties by index; att_off: exclusive scan of ceil(win / 128) * H in that order).
+ * guard: 20 for frame rows, 2 for phoneme rows.  Every other entry takes the same (plan_dev, B, S, Mp, att_wgs). */
+int ns_op_pack_plan(const int64_t* lens_dev, const int64_t* lens_host, int B, int S, int H, int guard, int32_t* plan_dev, size_t plan_ints,
+                    int32_t* Mp, int32_t* att_wgs, void* stream);
+/* ns_op_gemm on packed rows: x_p [Mp, Cin] -> out_p [Mp, N], zero padding at each window's own edges, the model's precision mode */
+int ns_op_gemm_packed(ns_model* m, const char* name, const float* x_p, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, float* out_p,
+                      void* stream);
+/* ns_op_attention_core_mode on packed rows: qkv_p [Mp, 3 H dk] -> out_p [Mp, H dk]; keys of utterance b are its rows
+ * t < min(lens[b], win[b]).  flags: bit 0 = the bf16 mode's kernels, bit 1 = withhold the ticket block carved from the end of
+ * `scratch` (the strip form then merges its key ranges by a launch of its own). */
+int ns_op_attention_core_packed(const float* qkv_p, const int64_t* lens, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, int H, int dk,
+                                float* out_p, void* scratch /* nullable */, size_t scratch_bytes, void* stream, int flags);
+/* host only: what ns_op_attention_core_packed makes of a scratch of scratch_bytes under `flags` (the op carves by this very function):
+ * the floats left to the split-key partials, and whether a ticket block was taken from the end */
+int ns_op_attention_packed_carve(int B, int S, int H, size_t scratch_bytes, int flags, size_t* partial_floats, int32_t* has_tickets);
+/* host only: what the packed attention launch of this shape does, answered by the function the launch dispatches on.
+ * out = {form: 0 strip kernel / 1 flat work list, key ranges per strip / per work-list workgroup, merge launch 0 / 1,
+ * 32-key tiles per range of a window of S}.  scratch_floats: floats of scratch left to the partials (0 = none). */
+int ns_plan_attention_packed(int B, int S, int H, int dk, int att_wgs, int Mp, size_t scratch_floats, int has_tickets, int32_t out[4]);
+/* host only: the key ranges whose partials ns_op_block_packed and the packed forwards reserve on these rows (before the workspace's
+ * size limits them): scratch for that many makes ns_op_attention_core_packed split as the block's own attention does */
+int ns_plan_attention_split_packed(int att_wgs, int S, int H, int dk, int Mp);
+/* which: 0 = ns_op_positionwise_ffn, 1 = ns_op_multi_head_attention, 2 = ns_op_fft_block on the packed rows of layer `prefix`
+ * (the FFTBlock's own prefix for all three).  mask_rows != 0 zeroes the rows at t >= lens[b] (always for which = 2).  ws:
+ * ns_op_ws_bytes(m, B, S) bytes. */
+int ns_op_block_packed(ns_model* m, int which, const char* prefix, const float* x_p, const int64_t* lens /* nullable for an unmasked ffn */,
+                       const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, int mask_rows, float* out_p, void* ws, size_t ws_bytes,
+                       void* stream);
+/* The packed data movement, each launch alone.  ns_op_length_regulate_packed and ns_op_embed_pos_packed write row maps themselves
+ * (the former builds the whole plan with guard 20; the latter needs off / win of a plan built before).  status nullable.
+ * ns_op_unpack_outputs: mel_bias [n_mel], post_const [11, n_mel]; p_p / p_pred, e_p / e_pred and mel_mask are nullable. */
+int ns_op_length_regulate_packed(const float* x, const int32_t* cum, const int64_t* mel_lens, int B, int L, int D, int T, int Mp, int H,
+                                 float* out_p, int32_t* status, int32_t* plan_dev, size_t plan_ints, void* stream);
+int ns_op_embed_pos_packed(const int64_t* texts, const float* emb, const float* pos, const int32_t* plan_dev, int B, int L, int Mp, int att_wgs, int D,
+                           int n_vocab, float* out_p, void* stream);
+int ns_op_add_pos_packed(const float* x_p, const float* pos, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, int D, float* out_p,
+                         void* stream);
+int ns_op_pack_vector(const float* src, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, float* dst_p, void* stream);
+int ns_op_unpack_rows(const float* src_p, const int64_t* lens /* nullable */, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, int D,
+                      float* dst, void* stream);
+int ns_op_unpack_phase1(const float* rows_p, const float* vec_p, const int64_t* lens, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs,
+                        int D, float* rows, float* vec, void* stream);
+int ns_op_unpack_outputs(const int32_t* plan_dev, int B, int T, int Mp, int att_wgs, int n_mel, const int64_t* mel_lens, const float* mel_p,
+                         const float* post_p, const float* p_p, const float* e_p, const float* mel_bias, const float* post_const, float* mel,
+                         float* post, float* p_pred, float* e_pred, uint8_t* mel_mask, void* stream);
+
 /* Measurement hook for bench.py's roofline legs: while enabled, the launches of the three heaviest kernels inside
  * ns_forward_mel carry hipEvents ON THEIR OWN DISPATCH PACKETS (hipExtLaunchKernel start / stop events: the kernel's begin and
  * end timestamps, no marker packet on the stream; a timed launch still costs the stream ~5 us, so bench.py times slot 0 inside

@@ -156,6 +156,21 @@ SIGNATURES = {
     "ns_plan_gemm_bf16": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ns_plan_gemm_bf16_ln": (_I, [_I, _I, _I, _I]),
     "ns_op_attention_scratch_bytes": (_Z, [_I, _I, _I, _I]),
+    # packed-row test hooks: (plan, B, S, Mp, att_wgs) after the tensors
+    "ns_op_pack_plan": (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "ns_op_gemm_packed": (_I, [_P, _S, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "ns_op_attention_core_packed": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P, _I]),
+    "ns_op_attention_packed_carve": (_I, [_I, _I, _I, _Z, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "ns_plan_attention_packed": (_I, [_I, _I, _I, _I, _I, _I, _Z, _I, C.POINTER(C.c_int32)]),
+    "ns_plan_attention_split_packed": (_I, [_I, _I, _I, _I, _I]),
+    "ns_op_block_packed": (_I, [_P, _I, _S, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "ns_op_length_regulate_packed": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ns_op_embed_pos_packed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "ns_op_add_pos_packed": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "ns_op_pack_vector": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "ns_op_unpack_rows": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "ns_op_unpack_phase1": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ns_op_unpack_outputs": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ns_profile_enable": (_I, [_P, _I]),
     "ns_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ns_profile_read_slot": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -693,14 +693,25 @@ static int decoder_stack(ns_model* m, float* x, const long long* lens, int B, in
 // lens_host (nullable): the host copy of src_lens.  With it, and when the utterances' phoneme counts leave >= 10 % of the [B, L]
 // grid as padding, everything up to the duration predictor runs on PACKED phoneme rows (kernels.h PHONEME_GUARD: exact, see
 // there) and the padded [B, L] tensors the caller and phase 2 expect are rebuilt before the duration tail.
-static size_t phase1_packed_rows(const int64_t* lens_host, int B, int L) {
+// Rows and attention work-list length of a packed phase, from the host copy of the lengths the device plan reads (rowops.hip
+// k_pack_plan): window b = min(max(len[b], 0) + guard, S); rows = their sum, workgroups = sum of ceil(window / 128) * H.
+static size_t window_rows(const int64_t* lens_host, int B, int S, int guard) {
   size_t mp = 0;
   for (int b = 0; b < B; ++b) {
-    long long l = (lens_host[b] < 0 ? 0 : lens_host[b]) + PHONEME_GUARD;
-    mp += (size_t)(l < (long long)L ? l : (long long)L);
+    long long l = (lens_host[b] < 0 ? 0 : lens_host[b]) + guard;
+    mp += (size_t)(l < (long long)S ? l : (long long)S);
   }
   return mp;
 }
+static int window_att_wgs(const int64_t* lens_host, int B, int S, int guard, int H) {
+  int wgs = 0;
+  for (int b = 0; b < B; ++b) {
+    long long l = (lens_host[b] < 0 ? 0 : lens_host[b]) + guard;
+    wgs += (int)(((l < S ? l : S) + 127) / 128) * H;
+  }
+  return wgs;
+}
+static size_t phase1_packed_rows(const int64_t* lens_host, int B, int L) { return window_rows(lens_host, B, L, PHONEME_GUARD); }
 static size_t phase1_packed_extra_bytes(const ns_config& c, int B, int L) {  // plan + packed encoder output + packed log-durations
   Bump bp(nullptr);
   const size_t M = (size_t)B * L;
@@ -766,11 +777,7 @@ static int forward_durations(ns_model* m, const int64_t* texts, const int64_t* s
   float *enc_w = enc_out, *logd_w = log_d;
   if (packed) {
     const int M = (int)Mp, d = c.d_enc;
-    int base = 0;  // the attention work list's length, from the same lengths the device plan reads
-    for (int b = 0; b < B; ++b) {
-      long long l = (lens_host[b] < 0 ? 0 : lens_host[b]) + PHONEME_GUARD;
-      base += (int)(((l < L ? l : L) + 127) / 128) * c.n_enc_head;
-    }
+    const int base = window_att_wgs(lens_host, B, L, PHONEME_GUARD, c.n_enc_head);  // the attention work list's length
     size_t n = (size_t)attention_split_packed(base, L, d / c.n_enc_head, Mp, d);
     const size_t per = Mp * d + 2 * Mp * c.n_enc_head;
     const size_t extra = phase1_packed_extra_bytes(c, B, L);
@@ -876,15 +883,7 @@ extern "C" int ns_forward_durations_packed(ns_model* m, const int64_t* texts, co
 //     what the dense computation gives; frames beyond are constants of the weights (postnet_constants below).
 // Same arithmetic per row, so valid frames differ from the dense path's only where a launch picks another tile shape for
 // the smaller M (fp32 summation order, ~1e-6).  Needs the lengths on the host (row count), hence the separate entry point.
-static size_t packed_rows(const int64_t* lens_host, int B, int T) {
-  size_t mp = 0;
-  for (int b = 0; b < B; ++b) {
-    long long l = lens_host[b] < 0 ? 0 : lens_host[b];
-    l += PACK_GUARD;
-    mp += (size_t)(l < (long long)T ? l : (long long)T);
-  }
-  return mp;
-}
+static size_t packed_rows(const int64_t* lens_host, int B, int T) { return window_rows(lens_host, B, T, PACK_GUARD); }
 static size_t packed_extra_bytes(const ns_config& c, int B, int T) {  // on top of carve(): plan, packed outputs, PostNet constants
   Bump bp(nullptr);
   const size_t M = (size_t)B * T;
@@ -934,12 +933,8 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
   Bump bp(ws_dec);
   Scratch sc = carve(c, bp, Mrows, T, packed);
   if (packed) {  // split-key partials for a work list of few workgroups (attention.hip packed launch): whatever the workspace still holds
-    size_t base = 0;
-    for (int b = 0; b < B; ++b) {
-      long long l = (lens_host[b] < 0 ? 0 : lens_host[b]) + PACK_GUARD;
-      base += (size_t)(((l < T ? l : T) + 127) / 128) * c.n_dec_head;
-    }
-    size_t n = (size_t)attention_split_packed((int)base, T, d / c.n_dec_head, Mrows, d);
+    const int base = window_att_wgs(lens_host, B, T, PACK_GUARD, c.n_dec_head);
+    size_t n = (size_t)attention_split_packed(base, T, d / c.n_dec_head, Mrows, d);
     if (n > 1) {
       const size_t per = Mrows * d + 2 * Mrows * c.n_dec_head;  // floats per key range
       const size_t avail = ws_bytes > bp.off + packed_extra_bytes(c, B, T) ? (ws_bytes - bp.off - packed_extra_bytes(c, B, T)) / sizeof(float) : 0;
@@ -966,11 +961,7 @@ static int forward_mel(ns_model* m, int B, int L, int T, const int64_t* mel_lens
     } else {
       NS_HIP(launch_length_regulate_packed(enc_out, cum, B, L, c.d_enc, T, M, c.n_dec_head, sc.xa, lens, status, sc.tk.base, TICKET_INTS, plan, &pk.rm, st));
     }
-    for (int b = 0; b < B; ++b) {  // the attention work list's length, from the same lengths the device plan reads
-      long long l = (lens_host[b] < 0 ? 0 : lens_host[b]) + PACK_GUARD;
-      if (l > T) l = T;
-      pk.rm.att_wgs += (int)((l + 127) / 128) * c.n_dec_head;
-    }
+    pk.rm.att_wgs = window_att_wgs(lens_host, B, T, PACK_GUARD, c.n_dec_head);  // the attention work list's length
     // frame-level targets arrive on the padded [B, T] grid
     if (p_targets && c.pitch_frame_level) { NS_HIP(launch_pack_vector(pk.rm, T, p_targets, pt_p, M, st)); p_targets = pt_p; }
     if (e_targets && c.energy_frame_level) { NS_HIP(launch_pack_vector(pk.rm, T, e_targets, et_p, M, st)); e_targets = et_p; }
@@ -1346,4 +1337,200 @@ extern "C" int ns_plan_gemm_bf16(int M, int N, int32_t* bm, int32_t* bn) {
 }
 extern "C" int ns_op_ffn_conv1(ns_model* m, const char* prefix, const float* x, int B, int S, float* hidden, void* stream) {
   return named_gemm(m, std::string(prefix ? prefix : "") + ".w_1", false, x, B, S, hidden, stream);
+}
+
+// ------------------------------------------------------------------------------------------- packed-row test hooks
+// One stage alone on PACKED rows (kernels.h RowMap), through the functions the forwards call: gemm() with sc.pk set,
+// launch_attention with a RowMap, the launch_* functions of rowops.hip.  The caller builds the plan once (ns_op_pack_plan) and
+// hands every later entry the same (plan, B, S, Mp, att_wgs).  Arguments are refused before any device work.
+extern "C" int ns_op_pack_plan(const int64_t* lens_dev, const int64_t* lens_host, int B, int S, int H, int guard, int32_t* plan_dev,
+                               size_t plan_ints, int32_t* Mp_out, int32_t* att_wgs_out, void* stream) {
+  if (!lens_host || !Mp_out || !att_wgs_out) return fail("ns_op_pack_plan: lens_host, Mp and att_wgs are required");
+  if (B <= 0 || S <= 0 || H <= 0 || guard <= 0) return fail("ns_op_pack_plan: B, S, H and guard must be positive");
+  if ((size_t)B * S >= ((size_t)1 << 30)) return fail("ns_op_pack_plan: more than 2^30 grid rows");
+  const size_t Mp = window_rows(lens_host, B, S, guard);
+  *Mp_out = (int32_t)Mp;
+  *att_wgs_out = window_att_wgs(lens_host, B, S, guard, H);
+  if (!plan_dev && !lens_dev) return 0;  // the sizes alone (host only)
+  if (!plan_dev || !lens_dev) return fail("ns_op_pack_plan: lens_dev and plan_dev go together");
+  if (plan_ints < pack_plan_ints(B, Mp)) return fail("ns_op_pack_plan: plan buffer smaller than pack_plan_ints(B, Mp)");
+  RowMap rm;
+  memset(&rm, 0, sizeof(rm));
+  NS_HIP(launch_pack_plan((const long long*)lens_dev, B, S, H, (int)Mp, (int*)plan_dev, &rm, (hipStream_t)stream, guard));
+  return 0;
+}
+
+static int packed_ctx(const char* who, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, PackedCtx* pk) {
+  if (!plan_dev) return fail(std::string(who) + ": null plan");
+  if (B <= 0 || S <= 0 || Mp <= 0 || att_wgs <= 0 || (size_t)Mp > (size_t)B * S) return fail(std::string(who) + ": bad packed shape");
+  memset(pk, 0, sizeof(*pk));
+  plan_pointers(const_cast<int*>((const int*)plan_dev), B, Mp, &pk->rm);
+  pk->Mp = Mp;
+  pk->rm.rows = Mp;
+  pk->rm.att_wgs = att_wgs;
+  return 0;
+}
+
+extern "C" int ns_op_gemm_packed(ns_model* m, const char* name, const float* x_p, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs,
+                                 float* out_p, void* stream) {
+  NS_TRY(check_ready(m));
+  if (!name || !x_p || !out_p) return fail("ns_op_gemm_packed: null argument");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_gemm_packed", plan_dev, B, S, Mp, att_wgs, &pk));
+  const ConvW* w; int act;
+  NS_TRY(find_conv(m, name, &w, &act));
+  Scratch sc;
+  memset(&sc, 0, sizeof(sc));
+  sc.pk = &pk;
+  return gemm(m, sc, *w, x_p, nullptr, out_p, Mp, S, act, (hipStream_t)stream);
+}
+
+// What ns_op_attention_core_packed makes of a scratch of scratch_bytes (host only; the op itself carves by this function): the floats
+// left to the split-key partials and whether a ticket block was taken from the end.
+extern "C" int ns_op_attention_packed_carve(int B, int S, int H, size_t scratch_bytes, int flags, size_t* partial_floats, int32_t* has_tickets) {
+  if (B <= 0 || S <= 0 || H <= 0 || !partial_floats || !has_tickets) return fail("ns_op_attention_packed_carve: bad argument");
+  size_t floats = scratch_bytes / sizeof(float);
+  const size_t tk = ((size_t)attention_ticket_ints(B, S, H) + 63) & ~(size_t)63;
+  *has_tickets = 0;
+  if (!(flags & 2) && floats > tk) { floats -= tk; *has_tickets = 1; }
+  *partial_floats = floats;
+  return 0;
+}
+// flags: bit 0 = the bf16 mode's kernels, bit 1 = withhold the ticket block (the strips then merge by a launch of their own)
+extern "C" int ns_op_attention_core_packed(const float* qkv_p, const int64_t* lens, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs,
+                                           int H, int dk, float* out_p, void* scratch, size_t scratch_bytes, void* stream, int flags) {
+  if (!qkv_p || !lens || !out_p) return fail("ns_op_attention_core_packed: null argument");
+  if (H <= 0 || (dk != 128 && dk != 64 && dk != 32)) return fail("ns_op_attention_core_packed: d_k must be 32, 64 or 128");
+  if (flags & ~3) return fail("ns_op_attention_core_packed: unknown flag");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_attention_core_packed", plan_dev, B, S, Mp, att_wgs, &pk));
+  // the strip kernel's tickets are carved from the END of the caller's scratch and zeroed here, as ns_op_attention_core_mode does
+  float* sp = (float*)scratch;
+  size_t floats = 0;
+  int32_t has_tk = 0;
+  int* tickets = nullptr;
+  if (sp) NS_TRY(ns_op_attention_packed_carve(B, S, H, scratch_bytes, flags, &floats, &has_tk));
+  if (has_tk) {
+    tickets = (int*)(sp + floats);
+    NS_HIP(hipMemsetAsync(tickets, 0, (scratch_bytes / sizeof(float) - floats) * sizeof(int), (hipStream_t)stream));
+  }
+  NS_HIP(launch_attention(qkv_p, (const long long*)lens, B, S, H, dk, out_p, sp, floats, tickets, (hipStream_t)stream, &pk.rm, nullptr, (flags & 1) != 0));
+  return 0;
+}
+
+// the packed launch_attention's own decision (attention.hip attention_plan_packed); host only.
+// out = {form: 0 strips / 1 work list, key ranges, merge launch 0 / 1, 32-key tiles per range of a window of S}
+extern "C" int ns_plan_attention_packed(int B, int S, int H, int dk, int att_wgs, int Mp, size_t scratch_floats, int has_tickets, int32_t out[4]) {
+  if (!out) return fail("ns_plan_attention_packed: null out");
+  if (B <= 0 || S <= 0 || H <= 0 || att_wgs <= 0 || Mp <= 0 || (dk != 128 && dk != 64 && dk != 32)) return fail("ns_plan_attention_packed: bad shape");
+  const AttentionPackedPlan pl = attention_plan_packed(B, S, H, dk, att_wgs, (size_t)Mp, scratch_floats, has_tickets != 0);
+  out[0] = pl.form; out[1] = pl.nsplit; out[2] = pl.merge; out[3] = pl.tiles;
+  return 0;
+}
+
+// key ranges whose partials ns_op_block_packed (and the packed forwards) reserve for a stack of H heads of d_k on these rows: hand
+// ns_op_attention_core_packed that many and it splits its keys as the block's own attention does
+extern "C" int ns_plan_attention_split_packed(int att_wgs, int S, int H, int dk, int Mp) {
+  if (att_wgs <= 0 || S <= 0 || H <= 0 || dk <= 0 || Mp <= 0) return 1;
+  return attention_split_packed(att_wgs, S, dk, (size_t)Mp, H * dk);
+}
+// which: 0 = PositionwiseFeedForward, 1 = MultiHeadAttention, 2 = FFTBlock (always masked), on packed rows of the layer `prefix`
+// (the FFTBlock's prefix; mask_rows: zero the rows at t >= lens[b] as the FFTBlock does).  ws: ns_op_ws_bytes(m, B, S) bytes; the
+// attention's split-key partials are sized from what that workspace still holds, as the packed forwards size theirs.
+extern "C" int ns_op_block_packed(ns_model* m, int which, const char* prefix, const float* x_p, const int64_t* lens, const int32_t* plan_dev,
+                                  int B, int S, int Mp, int att_wgs, int mask_rows, float* out_p, void* ws, size_t ws_bytes, void* stream) {
+  NS_TRY(check_ready(m));
+  if (which < 0 || which > 2) return fail("ns_op_block_packed: which must be 0 (ffn), 1 (mha) or 2 (fft block)");
+  if (!x_p || !out_p || !ws) return fail("ns_op_block_packed: null argument");
+  if (!lens && (which != 0 || mask_rows)) return fail("ns_op_block_packed: lens is required");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_block_packed", plan_dev, B, S, Mp, att_wgs, &pk));
+  const LayerW* L; int d, H;
+  NS_TRY(find_layer(m, prefix, &L, &d, &H, ""));
+  if (ws_bytes < ns_op_ws_bytes(m, B, S)) return fail("workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  Bump bp(ws);
+  Scratch sc = carve(m->cfg, bp, (size_t)Mp, S, true);
+  if (sc.tk.base) NS_HIP(hipMemsetAsync(sc.tk.base, 0, TICKET_INTS * sizeof(int), st));
+  size_t n = (size_t)attention_split_packed(att_wgs, S, d / H, (size_t)Mp, d);
+  const size_t per = (size_t)Mp * d + 2 * (size_t)Mp * H;
+  const size_t avail = ws_bytes > bp.off + 256 ? (ws_bytes - bp.off - 256) / sizeof(float) : 0;
+  while (n > 1 && n * per > avail) --n;
+  if (n > 1) { sc.att_part_floats = n * per; sc.att_part = bp.f(sc.att_part_floats); }
+  sc.pk = &pk;
+  const long long* ln = (const long long*)lens;
+  if (which == 0) return ffn(m, *L, d, x_p, ln, B, S, out_p, mask_rows != 0, sc, st);
+  if (which == 1) return mha(m, *L, d, H, x_p, ln, B, S, out_p, mask_rows != 0, sc, st);
+  return fft_block(m, *L, d, H, x_p, ln, B, S, out_p, sc, st);
+}
+
+// launch_length_regulate_packed alone: the plan (into plan_dev, pack_plan_ints(B, Mp) ints), the row maps and the gather
+extern "C" int ns_op_length_regulate_packed(const float* x, const int32_t* cum, const int64_t* mel_lens, int B, int L, int D, int T, int Mp, int H,
+                                            float* out_p, int32_t* status, int32_t* plan_dev, size_t plan_ints, void* stream) {
+  if (!x || !cum || !mel_lens || !out_p || !plan_dev) return fail("ns_op_length_regulate_packed: null argument");
+  if (B <= 0 || L <= 0 || T <= 0 || H <= 0 || Mp <= 0 || D <= 0 || D % 4 != 0 || (size_t)Mp > (size_t)B * T) return fail("ns_op_length_regulate_packed: bad shape");
+  if (plan_ints < pack_plan_ints(B, (size_t)Mp)) return fail("ns_op_length_regulate_packed: plan buffer smaller than pack_plan_ints(B, Mp)");
+  RowMap rm;
+  memset(&rm, 0, sizeof(rm));
+  NS_HIP(launch_length_regulate_packed(x, cum, B, L, D, T, Mp, H, out_p, (const long long*)mel_lens, status, nullptr, 0, (int*)plan_dev, &rm,
+                                       (hipStream_t)stream));
+  return 0;
+}
+// launch_embed_pos_packed alone (it also writes the row maps): pos [>= L, D], emb [n_vocab, D]
+extern "C" int ns_op_embed_pos_packed(const int64_t* texts, const float* emb, const float* pos, const int32_t* plan_dev, int B, int L, int Mp, int att_wgs,
+                                      int D, int n_vocab, float* out_p, void* stream) {
+  if (!texts || !emb || !pos || !out_p) return fail("ns_op_embed_pos_packed: null argument");
+  if (D <= 0 || D % 4 != 0 || n_vocab <= 0) return fail("ns_op_embed_pos_packed: bad shape");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_embed_pos_packed", plan_dev, B, L, Mp, att_wgs, &pk));
+  NS_HIP(launch_embed_pos_packed((const long long*)texts, emb, pos, out_p, pk.rm, B, Mp, L, D, n_vocab, nullptr, 0, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ns_op_add_pos_packed(const float* x_p, const float* pos, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, int D, float* out_p,
+                                    void* stream) {
+  if (!x_p || !pos || !out_p) return fail("ns_op_add_pos_packed: null argument");
+  if (D <= 0 || D % 4 != 0) return fail("ns_op_add_pos_packed: D must be a positive multiple of 4");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_add_pos_packed", plan_dev, B, S, Mp, att_wgs, &pk));
+  NS_HIP(launch_add_pos(x_p, pos, out_p, Mp, S, D, (hipStream_t)stream, &pk.rm));
+  return 0;
+}
+extern "C" int ns_op_pack_vector(const float* src, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, float* dst_p, void* stream) {
+  if (!src || !dst_p) return fail("ns_op_pack_vector: null argument");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_pack_vector", plan_dev, B, S, Mp, att_wgs, &pk));
+  NS_HIP(launch_pack_vector(pk.rm, S, src, dst_p, Mp, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ns_op_unpack_rows(const float* src_p, const int64_t* lens, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, int D, float* dst,
+                                 void* stream) {
+  if (!src_p || !dst) return fail("ns_op_unpack_rows: null argument");
+  if (D <= 0) return fail("ns_op_unpack_rows: D must be positive");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_unpack_rows", plan_dev, B, S, Mp, att_wgs, &pk));
+  NS_HIP(launch_unpack_rows(pk.rm, (const long long*)lens, B, S, D, src_p, dst, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ns_op_unpack_phase1(const float* rows_p, const float* vec_p, const int64_t* lens, const int32_t* plan_dev, int B, int S, int Mp,
+                                   int att_wgs, int D, float* rows, float* vec, void* stream) {
+  if (!rows_p || !vec_p || !lens || !rows || !vec) return fail("ns_op_unpack_phase1: null argument");
+  if (D <= 0 || D % 4 != 0) return fail("ns_op_unpack_phase1: D must be a positive multiple of 4");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_unpack_phase1", plan_dev, B, S, Mp, att_wgs, &pk));
+  NS_HIP(launch_unpack_phase1(pk.rm, (const long long*)lens, B, S, D, rows_p, rows, vec_p, vec, (hipStream_t)stream));
+  return 0;
+}
+// launch_unpack_outputs alone: mel_bias [n_mel] and post_const [11, n_mel] are the caller's; p_p / p_pred and e_p / e_pred are
+// nullable in pairs, mel_mask is nullable
+extern "C" int ns_op_unpack_outputs(const int32_t* plan_dev, int B, int T, int Mp, int att_wgs, int n_mel, const int64_t* mel_lens, const float* mel_p,
+                                    const float* post_p, const float* p_p, const float* e_p, const float* mel_bias, const float* post_const,
+                                    float* mel, float* post, float* p_pred, float* e_pred, uint8_t* mel_mask, void* stream) {
+  if (!mel_lens || !mel_p || !post_p || !mel_bias || !post_const || !mel || !post) return fail("ns_op_unpack_outputs: null argument");
+  if ((p_pred && !p_p) || (e_pred && !e_p)) return fail("ns_op_unpack_outputs: p_pred / e_pred without their packed source");
+  if (n_mel <= 0) return fail("ns_op_unpack_outputs: n_mel must be positive");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_unpack_outputs", plan_dev, B, T, Mp, att_wgs, &pk));
+  NS_HIP(launch_unpack_outputs(pk.rm, B, T, n_mel, (const long long*)mel_lens, mel_p, post_p, p_p, e_p, mel_bias, post_const, mel, post, p_pred,
+                               e_pred, mel_mask, (hipStream_t)stream));
+  return 0;
 }

@@ -810,6 +810,50 @@ static void launch_k_strip(bool bf, dim3 grid, hipStream_t st, Args... args) {
   else hipLaunchKernelGGL((k_attention_strip<DK, false>), grid, dim3(256), 0, st, args...);
 }
 
+// The strip launch of (B, S, H, dk) over M rows with scratch_floats floats of scratch (0 = none): key-range workgroups per strip and
+// 32-key tiles per wave; false = the strips are not taken (a wave would sweep more than 4 tiles).
+static bool strip_plan(int B, int S, int H, int dk, size_t M, size_t scratch_floats, int* nsplit_out, int* tpr_out) {
+  const int d = H * dk, tiles = (S + 31) / 32;
+  auto part_floats = [&](int n) { return (size_t)n * (M * d + 2 * M * H); };
+  const long strips = (long)tiles * H * B;
+  int nsplit = (int)((256 + strips - 1) / strips);
+  if (nsplit > (tiles + 3) / 4) nsplit = (tiles + 3) / 4;   // at least one key tile per wave
+  if (nsplit > ATT_STRIP_SPLIT_MAX) nsplit = ATT_STRIP_SPLIT_MAX;
+  if (nsplit > 1 && !scratch_floats) nsplit = 1;
+  if (part_floats(nsplit) * 4 >= (1ull << 31)) nsplit = 1;  // 31-bit descriptor offsets over the partials
+  while (nsplit > 1 && part_floats(nsplit) > scratch_floats) --nsplit;
+  int tpr = (tiles + 4 * nsplit - 1) / (4 * nsplit);
+  nsplit = ((tiles + tpr - 1) / tpr + 3) / 4;                // no workgroup of empty ranges
+  tpr = (tiles + 4 * nsplit - 1) / (4 * nsplit);
+  *nsplit_out = nsplit; *tpr_out = tpr;
+  return tpr <= 4;
+}
+
+// The packed launch's decision (kernels.h AttentionPackedPlan): launch_attention below dispatches on the answer.
+AttentionPackedPlan attention_plan_packed(int B, int S, int H, int dk, int att_wgs, size_t Mp, size_t scratch_floats, bool has_tickets) {
+  AttentionPackedPlan pl = {1, 1, 0, (S + 31) / 32};
+  const int d = H * dk;
+  // a handful of short windows (phase 1 of a ragged batch, L <= ~500): the strip kernel on the packed rows, no merge launch
+  if ((long)((S + 127) / 128) * H * B < ATT_SPLIT_MAX_BLOCKS && (long long)Mp * 3 * d * 4 < (1ll << 31)) {
+    int nsplit, tpr;
+    if (strip_plan(B, S, H, dk, Mp, scratch_floats, &nsplit, &tpr)) {
+      pl.form = 0; pl.nsplit = nsplit; pl.merge = (nsplit > 1 && !has_tickets) ? 1 : 0; pl.tiles = tpr;
+      return pl;
+    }
+  }
+  // Few workgroups (a handful of ragged utterances): the launch would last as long as the longest utterance's sweep while
+  // most CUs idle.  Every workgroup's key axis is cut into nsplit ranges (of ITS utterance's key tiles), the partials are
+  // merged by k_attention_merge — the split-key path of the grid, on the work list.
+  int nsplit = 1;
+  if (scratch_floats) {
+    nsplit = attention_split_packed(att_wgs, S, dk, Mp, d);
+    while (nsplit > 1 && (size_t)nsplit * (Mp * d + 2 * Mp * H) > scratch_floats) --nsplit;
+    if (nsplit < 1) nsplit = 1;
+  }
+  pl.nsplit = nsplit; pl.merge = nsplit > 1 ? 1 : 0; pl.tiles = (pl.tiles + nsplit - 1) / nsplit;
+  return pl;
+}
+
 // Few workgroups (single-utterance latency, the encoder): a 128-query workgroup's time is its serial sweep over the key tiles.
 // First choice, k_attention_strip: a workgroup per 32-query strip whose four waves split the key axis, and up to nsplit such
 // workgroups per strip merged by the last arriver — taken when that leaves every wave at most 4 key tiles (beyond that the shared
@@ -821,18 +865,8 @@ static bool launch_strips(const float* qkv, const long long* lens, int B, int S,
   const int d = H * dk, tiles = (S + 31) / 32;
   const float c = 1.4426950408889634f / sqrtf((float)dk);
   const size_t M = rm ? (size_t)rm->rows : (size_t)B * S;
-  auto part_floats = [&](int n) { return (size_t)n * (M * d + 2 * M * H); };
-  const long strips = (long)tiles * H * B;
-  int nsplit = (int)((256 + strips - 1) / strips);
-  if (nsplit > (tiles + 3) / 4) nsplit = (tiles + 3) / 4;   // at least one key tile per wave
-  if (nsplit > ATT_STRIP_SPLIT_MAX) nsplit = ATT_STRIP_SPLIT_MAX;
-  if (nsplit > 1 && !scratch) nsplit = 1;
-  if (part_floats(nsplit) * 4 >= (1ull << 31)) nsplit = 1;  // 31-bit descriptor offsets over the partials
-  while (nsplit > 1 && part_floats(nsplit) > scratch_floats) --nsplit;
-  int tpr = (tiles + 4 * nsplit - 1) / (4 * nsplit);
-  nsplit = ((tiles + tpr - 1) / tpr + 3) / 4;                // no workgroup of empty ranges
-  tpr = (tiles + 4 * nsplit - 1) / (4 * nsplit);
-  if (tpr > 4) return false;
+  int nsplit, tpr;
+  if (!strip_plan(B, S, H, dk, M, scratch ? scratch_floats : 0, &nsplit, &tpr)) return false;
   float* opart = nsplit > 1 ? scratch : nullptr;
   float* mlpart = nsplit > 1 ? scratch + (size_t)nsplit * M * d : nullptr;
   const int* off = rm ? rm->off : nullptr;
@@ -859,21 +893,14 @@ hipError_t launch_attention(const float* qkv, const long long* lens, int B, int 
     const int d = H * dk;
     if ((long long)S * 3 * d * 4 >= (1ll << 31) || (dk != 128 && dk != 64 && dk != 32) || !rm->off || !rm->win) return hipErrorInvalidValue;
     if (!rm->att_off || !rm->att_order || rm->att_wgs <= 0 || rm->rows <= 0) return hipErrorInvalidValue;
-    // a handful of short windows (phase 1 of a ragged batch, L <= ~500): the strip kernel on the packed rows, no merge launch
-    if ((long)((S + 127) / 128) * H * B < ATT_SPLIT_MAX_BLOCKS && (long long)rm->rows * 3 * d * 4 < (1ll << 31) &&
-        launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, rm, ev0, ev1, bf))
-      return hipGetLastError();
-    const float c = 1.4426950408889634f / sqrtf((float)dk);
-    // Few workgroups (a handful of ragged utterances): the launch would last as long as the longest utterance's sweep while
-    // most CUs idle.  Every workgroup's key axis is cut into nsplit ranges (of ITS utterance's key tiles), the partials are
-    // merged by k_attention_merge — the split-key path of the grid, on the work list.
     const size_t Mp = (size_t)rm->rows;
-    int nsplit = 1;
-    if (scratch) {
-      nsplit = attention_split_packed(rm->att_wgs, S, dk, Mp, d);
-      while (nsplit > 1 && (size_t)nsplit * (Mp * d + 2 * Mp * H) > scratch_floats) --nsplit;
-      if (nsplit < 1) nsplit = 1;
+    const AttentionPackedPlan pl = attention_plan_packed(B, S, H, dk, rm->att_wgs, Mp, scratch ? scratch_floats : 0, tickets != nullptr);
+    if (pl.form == 0) {
+      if (!launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, rm, ev0, ev1, bf)) return hipErrorInvalidValue;
+      return hipGetLastError();
     }
+    const float c = 1.4426950408889634f / sqrtf((float)dk);
+    const int nsplit = pl.nsplit;
     float* opart = nsplit > 1 ? scratch : nullptr;
     float* mlpart = nsplit > 1 ? scratch + (size_t)nsplit * Mp * d : nullptr;
     dim3 grid(rm->att_wgs * nsplit);

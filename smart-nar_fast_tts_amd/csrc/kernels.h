@@ -119,6 +119,12 @@ hipError_t launch_attention(const float* qkv, const long long* lens, int B, int 
 int attention_split(int B, int S, int H, int dk);
 // the same for a packed launch: att_wgs workgroups on the work list, S = the longest window, Mp packed rows
 int attention_split_packed(int att_wgs, int S, int dk, size_t Mp, int d);
+// What a packed launch_attention of this shape does, decided by the function the launch itself asks: form 0 = k_attention_strip on
+// the packed rows, 1 = k_attention on the flat work list; nsplit key ranges per strip workgroup group / per work-list workgroup;
+// merge = a k_attention_merge launch follows; tiles = 32-key tiles per range of an utterance whose window is S (a strip's range is
+// one wave's share).  scratch_floats = 0: no scratch.
+struct AttentionPackedPlan { int form, nsplit, merge, tiles; };
+AttentionPackedPlan attention_plan_packed(int B, int S, int H, int dk, int att_wgs, size_t Mp, size_t scratch_floats, bool has_tickets);
 
 // ---- row kernels (rowops.hip) -----------------------------------------------------------------
 // y = LayerNorm_C(x) * g + b ; rows with t >= lens[b] are written as zero when lens != nullptr
@@ -161,6 +167,8 @@ hipError_t launch_duration_target_tail(const long long* d_targets, const long lo
 // plan: int storage for off [B+1], win [B], row_b / row_t / row_w [Mp] — pack_plan_ints(B, Mp) ints; *rm receives the pointers.
 constexpr int PACK_GUARD = 20;  // frames kept past an utterance's end: the PostNet's reach (5 layers x 2) twice over, see api.hip
 inline size_t pack_plan_ints(int B, size_t Mp) { return (size_t)4 * B + 4 + 3 * Mp; }
+// the plan's layout: off [B+1] | win [B] + 1 unused | att_off [B+1] | att_order [B] + 1 unused | row_b [Mp] | row_t [Mp] | row_w [Mp]
+void plan_pointers(int* plan, int B, int Mp, RowMap* rm);
 // H: attention heads of the stack that will run on these rows (the plan's attention work list is per head)
 hipError_t launch_length_regulate_packed(const float* x, const int32_t* cum, int B, int L, int D, int T, int Mp, int H, float* out,
                                          const long long* mel_lens, int32_t* status, int* zero, int nzero, int* plan, RowMap* rm,

@@ -164,7 +164,6 @@ hipError_t launch_store_lens(const long long* host, int n, long long* dst, hipSt
   return hipGetLastError();
 }
 
-static void plan_pointers(int* plan, int B, int Mp, RowMap* rm);
 // The same on packed phoneme rows (kernels.h RowMap, api.hip forward_durations): row m is phoneme row_t[m] of utterance row_b[m].
 // Also zeroes the phase's ticket counters (the plan kernels ahead of it do not).
 __global__ __launch_bounds__(256) void k_embed_pos_packed(const long long* __restrict__ texts, const float* __restrict__ emb,
@@ -515,7 +514,7 @@ __global__ void k_pack_rows(const int* __restrict__ off, const int* __restrict__
   row_b[m] = lo; row_t[m] = m - off[lo]; row_w[m] = win[lo];
 }
 
-static void plan_pointers(int* plan, int B, int Mp, RowMap* rm) {
+void plan_pointers(int* plan, int B, int Mp, RowMap* rm) {
   int* off = plan;
   int* win = off + B + 1;
   int* att_off = win + B + 1;

@@ -351,3 +351,211 @@ def aligner_durations(attn_last, src_lens, mel_lens):
     _lib.check(lib.ns_aln_op_durations(_lib.ptr(attn_last), _lib.ptr(src_lens), _lib.ptr(mel_lens), B, H, T, L, _lib.ptr(out),
                                        _st(attn_last)), "aligner_durations")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- packed rows (test hooks)
+class PackedPlan:
+    """What ``pack_plan`` built: the device plan (int32, ``None`` for a host-only plan) and the numbers every packed op takes.
+    Utterance b owns rows [off[b], off[b] + win[b]) of the ``Mp`` packed rows, win[b] = min(max(lens[b], 0) + guard, S)."""
+
+    def __init__(self, plan, lens, S, H, guard, Mp, att_wgs):
+        self.plan, self.lens, self.B, self.S, self.H, self.guard, self.Mp, self.att_wgs = plan, list(lens), len(lens), S, H, guard, Mp, att_wgs
+
+    @property
+    def args(self):
+        return (_lib.ptr(self.plan), self.B, self.S, self.Mp, self.att_wgs)
+
+    def section(self, name):
+        """one array of the device plan (``off``, ``win``, ``att_off``, ``att_order``, ``row_b``, ``row_t``, ``row_w``)"""
+        B, Mp = self.B, self.Mp
+        start = {"off": 0, "win": B + 1, "att_off": 2 * B + 2, "att_order": 3 * B + 3, "row_b": 4 * B + 4, "row_t": 4 * B + 4 + Mp, "row_w": 4 * B + 4 + 2 * Mp}[name]
+        return self.plan[start:start + {"off": B + 1, "win": B, "att_off": B + 1, "att_order": B}.get(name, Mp)]
+
+
+def pack_plan_ints(B: int, Mp: int) -> int:
+    return 4 * B + 4 + 3 * Mp
+
+
+def pack_plan(lens, S: int, H: int, guard: int, device=None, fill: int = 0) -> PackedPlan:
+    """The packing plan of ``lens`` (a list of ints) on an axis of S rows for a stack of H heads (``ns_op_pack_plan``).  With
+    ``device=None`` only the host numbers (Mp, att_wgs) — no GPU needed; else also the device plan, its buffer pre-filled with
+    ``fill`` so that a caller can tell what the kernels wrote."""
+    import ctypes
+
+    lib = _lib.load()
+    host = torch.tensor(list(lens), dtype=torch.long)
+    mp, wgs = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(lib.ns_op_pack_plan(_lib.ptr(None), _lib.ptr(host), len(lens), int(S), int(H), int(guard), _lib.ptr(None), 0, ctypes.byref(mp),
+                                   ctypes.byref(wgs), _lib.ptr(None)), "pack_plan")
+    if device is None:
+        return PackedPlan(None, lens, S, H, guard, mp.value, wgs.value)
+    dev = host.to(device)
+    plan = torch.full((pack_plan_ints(len(lens), mp.value),), fill, dtype=torch.int32, device=device)
+    _lib.check(lib.ns_op_pack_plan(_lib.ptr(dev), _lib.ptr(host), len(lens), int(S), int(H), int(guard), _lib.ptr(plan), plan.numel(),
+                                   ctypes.byref(mp), ctypes.byref(wgs), _st(plan)), "pack_plan")
+    return PackedPlan(plan, lens, S, H, guard, mp.value, wgs.value)
+
+
+def plan_attention_packed(B, S, H, dk, att_wgs, Mp, scratch_floats: int = 0, has_tickets: bool = False):
+    """(form 0 strips / 1 work list, key ranges, merge launch 0 / 1, 32-key tiles per range) of the packed attention launch, from
+    the function the launch dispatches on (host only)."""
+    import ctypes
+
+    o = (ctypes.c_int32 * 4)()
+    _lib.check(_lib.load().ns_plan_attention_packed(int(B), int(S), int(H), int(dk), int(att_wgs), int(Mp), int(scratch_floats),
+                                                    int(bool(has_tickets)), o), "plan_attention_packed")
+    return tuple(o)
+
+
+def attention_packed_scratch(p: PackedPlan, dk: int, split=True, tickets: bool = True):
+    """(floats of scratch ``attention_core_packed`` allocates, floats of it left to the partials, ticket block carved) for the same
+    arguments: room for 16 key ranges — ``split="block"``: for as many as ``block_packed`` reserves for its own attention — plus the
+    ticket block the op takes from the end."""
+    if not split:
+        return 0, 0, False
+    n = _lib.load().ns_plan_attention_split_packed(p.att_wgs, p.S, p.H, int(dk), p.Mp) if split == "block" else 16
+    if n <= 1:
+        return 0, 0, False
+    import ctypes
+
+    lib = _lib.load()
+    flags = 0 if tickets else 2
+
+    def carve(total):  # what the op makes of `total` floats, asked of the op's own function
+        part, has = ctypes.c_size_t(0), ctypes.c_int32(0)
+        _lib.check(lib.ns_op_attention_packed_carve(p.B, p.S, p.H, total * 4, flags, ctypes.byref(part), ctypes.byref(has)), "attention_packed_carve")
+        return part.value, bool(has.value)
+
+    want = n * (p.Mp * p.H * dk + 2 * p.Mp * p.H)
+    big = want + (1 << 28)
+    floats = want + (big - carve(big)[0])  # + the ticket block the op takes from the end
+    return (floats,) + carve(floats)
+
+
+def attention_core_packed(qkv_p, lens, p: PackedPlan, split=True, tickets: bool = True, bf16: bool = False):
+    """``attention_core`` on packed rows: qkv_p [Mp, 3 d] -> [Mp, d].  ``split`` hands the launch scratch for its key ranges,
+    ``tickets=False`` withholds the ticket block (the strip form then merges by a launch of its own)."""
+    lib = _lib.load()
+    Mp, d3 = qkv_p.shape
+    assert Mp == p.Mp
+    d = d3 // 3
+    qkv_p, lens = qkv_p.contiguous(), lens.long().contiguous()
+    out = torch.empty(Mp, d, dtype=torch.float32, device=qkv_p.device)
+    floats = attention_packed_scratch(p, d // p.H, split, tickets)[0]
+    scratch = torch.empty(floats, dtype=torch.float32, device=qkv_p.device) if floats else None
+    _lib.check(lib.ns_op_attention_core_packed(_lib.ptr(qkv_p), _lib.ptr(lens), *p.args, p.H, d // p.H, _lib.ptr(out), _lib.ptr(scratch),
+                                               floats * 4, _st(qkv_p), (1 if bf16 else 0) | (0 if tickets else 2)), "attention_core_packed")
+    return out
+
+
+def gemm_packed(model, name: str, x_p, p: PackedPlan):
+    """``gemm`` on packed rows: x_p [Mp, Cin] -> [Mp, N], zero padding at each window's own edges."""
+    x_p = x_p.contiguous()
+    assert x_p.shape == (p.Mp, gemm_shape(model, name)[0])
+    out = torch.empty(p.Mp, gemm_shape(model, name)[1], dtype=torch.float32, device=x_p.device)
+    _lib.check(model._lib.ns_op_gemm_packed(model._h, name.encode(), _lib.ptr(x_p), *p.args, _lib.ptr(out), _st(x_p)), "gemm_packed")
+    return out
+
+
+def block_packed(model, which: str, prefix: str, x_p, lens, p: PackedPlan, mask_rows: bool = False):
+    """``positionwise_ffn`` ("ffn"), ``multi_head_attention`` ("mha") or ``fft_block`` ("fft") of the layer ``prefix`` (the
+    FFTBlock's prefix) on packed rows x_p [Mp, d]."""
+    x_p = x_p.contiguous()
+    assert x_p.shape[0] == p.Mp
+    out = torch.empty_like(x_p)
+    ws = _ws(model, p.B, p.S)
+    lens_t = lens.long().contiguous() if lens is not None else None
+    _lib.check(model._lib.ns_op_block_packed(model._h, {"ffn": 0, "mha": 1, "fft": 2}[which], prefix.encode(), _lib.ptr(x_p), _lib.ptr(lens_t),
+                                             *p.args, int(bool(mask_rows)), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _st(x_p)), "block_packed")
+    return out
+
+
+def length_regulate_packed(x, cum, mel_lens, T: int, H: int, fill: int = 0):
+    """``launch_length_regulate_packed`` alone: x [B, L, D], cum int32 [B, L], mel_lens int64 [B] (device) -> (out_p [Mp, D],
+    status int32 [B], the PackedPlan it built with guard 20)."""
+    lib = _lib.load()
+    B, L, D = x.shape
+    x, cum, mel_lens = x.contiguous(), cum.int().contiguous(), mel_lens.long().contiguous()
+    p = pack_plan(mel_lens.cpu().tolist(), T, H, 20)
+    p.plan = torch.full((pack_plan_ints(B, p.Mp),), fill, dtype=torch.int32, device=x.device)
+    out = torch.empty(p.Mp, D, dtype=torch.float32, device=x.device)
+    status = torch.full((B,), -1, dtype=torch.int32, device=x.device)
+    _lib.check(lib.ns_op_length_regulate_packed(_lib.ptr(x), _lib.ptr(cum), _lib.ptr(mel_lens), B, L, D, int(T), p.Mp, int(H), _lib.ptr(out),
+                                                _lib.ptr(status), _lib.ptr(p.plan), p.plan.numel(), _st(x)), "length_regulate_packed")
+    return out, status, p
+
+
+def embed_pos_packed(texts, emb, pos, p: PackedPlan):
+    """texts int64 [B, L], emb [n_vocab, D], pos [>= L, D] -> [Mp, D]; also (re)writes the plan's row maps"""
+    lib = _lib.load()
+    B, L = texts.shape
+    assert (B, L) == (p.B, p.S) and pos.shape[0] >= L
+    texts, emb, pos = texts.long().contiguous(), emb.contiguous(), pos.contiguous()
+    out = torch.empty(p.Mp, emb.shape[1], dtype=torch.float32, device=emb.device)
+    _lib.check(lib.ns_op_embed_pos_packed(_lib.ptr(texts), _lib.ptr(emb), _lib.ptr(pos), _lib.ptr(p.plan), B, L, p.Mp, p.att_wgs, emb.shape[1],
+                                          emb.shape[0], _lib.ptr(out), _st(emb)), "embed_pos_packed")
+    return out
+
+
+def add_pos_packed(x_p, pos, p: PackedPlan):
+    lib = _lib.load()
+    assert x_p.shape[0] == p.Mp and pos.shape[0] >= p.S and pos.shape[1] == x_p.shape[1]
+    x_p, pos = x_p.contiguous(), pos.contiguous()
+    out = torch.empty_like(x_p)
+    _lib.check(lib.ns_op_add_pos_packed(_lib.ptr(x_p), _lib.ptr(pos), *p.args, x_p.shape[1], _lib.ptr(out), _st(x_p)), "add_pos_packed")
+    return out
+
+
+def pack_vector(src, p: PackedPlan):
+    """src [B, S] -> [Mp]"""
+    lib = _lib.load()
+    assert src.shape == (p.B, p.S)
+    src = src.contiguous().float()
+    out = torch.empty(p.Mp, dtype=torch.float32, device=src.device)
+    _lib.check(lib.ns_op_pack_vector(_lib.ptr(src), *p.args, _lib.ptr(out), _st(src)), "pack_vector")
+    return out
+
+
+def unpack_rows(src_p, lens, p: PackedPlan):
+    """src_p [Mp, D] -> [B, S, D]: rows at t < min(lens[b], win[b]) (lens None: t < win[b]), zeros elsewhere"""
+    lib = _lib.load()
+    assert src_p.shape[0] == p.Mp
+    src_p = src_p.contiguous()
+    lens_t = lens.long().contiguous() if lens is not None else None
+    D = src_p.shape[1]
+    out = torch.full((p.B, p.S, D), float("nan"), dtype=torch.float32, device=src_p.device)
+    _lib.check(lib.ns_op_unpack_rows(_lib.ptr(src_p), _lib.ptr(lens_t), *p.args, D, _lib.ptr(out), _st(src_p)), "unpack_rows")
+    return out
+
+
+def unpack_phase1(rows_p, vec_p, lens, p: PackedPlan):
+    """rows_p [Mp, D], vec_p [Mp] -> (rows [B, S, D]: zeros past a window; vec [B, S]: zeros at t >= min(lens[b], win[b]))"""
+    lib = _lib.load()
+    assert rows_p.shape[0] == p.Mp == vec_p.shape[0]
+    rows_p, vec_p, lens = rows_p.contiguous(), vec_p.contiguous(), lens.long().contiguous()
+    D = rows_p.shape[1]
+    rows = torch.full((p.B, p.S, D), float("nan"), dtype=torch.float32, device=rows_p.device)
+    vec = torch.full((p.B, p.S), float("nan"), dtype=torch.float32, device=rows_p.device)
+    _lib.check(lib.ns_op_unpack_phase1(_lib.ptr(rows_p), _lib.ptr(vec_p), _lib.ptr(lens), *p.args, D, _lib.ptr(rows), _lib.ptr(vec), _st(rows_p)),
+               "unpack_phase1")
+    return rows, vec
+
+
+def unpack_outputs(p: PackedPlan, mel_lens, mel_p, post_p, p_p, e_p, mel_bias, post_const, mask: bool = True):
+    """``launch_unpack_outputs`` alone; p_p / e_p may be None (no p_pred / e_pred).  Returns (mel, post, p_pred, e_pred, mel_mask)
+    on the padded [B, T] grid, outputs pre-filled with NaN / 255 so that an unwritten element shows."""
+    lib = _lib.load()
+    n_mel = mel_p.shape[1]
+    assert mel_p.shape == post_p.shape == (p.Mp, n_mel) and mel_bias.shape == (n_mel,) and post_const.shape == (11, n_mel)
+    dev = mel_p.device
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    mel_lens, mel_p, post_p, p_p, e_p, mel_bias, post_const = mel_lens.long().contiguous(), c(mel_p), c(post_p), c(p_p), c(e_p), c(mel_bias), c(post_const)
+    nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)  # noqa: E731
+    mel, post = nan(p.B, p.S, n_mel), nan(p.B, p.S, n_mel)
+    pp = nan(p.B, p.S) if p_p is not None else None
+    ep = nan(p.B, p.S) if e_p is not None else None
+    mm = torch.full((p.B, p.S), 255, dtype=torch.uint8, device=dev) if mask else None
+    _lib.check(lib.ns_op_unpack_outputs(*p.args, n_mel, _lib.ptr(mel_lens), _lib.ptr(mel_p), _lib.ptr(post_p), _lib.ptr(p_p), _lib.ptr(e_p),
+                                        _lib.ptr(mel_bias), _lib.ptr(post_const), _lib.ptr(mel), _lib.ptr(post), _lib.ptr(pp), _lib.ptr(ep),
+                                        _lib.ptr(mm), _st(mel_p)), "unpack_outputs")
+    return mel, post, pp, ep, mm

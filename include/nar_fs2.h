@@ -947,6 +947,72 @@ int ns_pg_op_row_backward(int tail, const float* dy, const float* g, const uint8
                           const float* ln_b, const float* wlin, const uint8_t* keep, float p_drop, int M, int F, float* dz, float* d_ln_g,
                           float* d_ln_b, float* d_b, float* d_wlin, float* d_blin, void* ws, size_t ws_bytes, void* stream);
 
+/* ==== MultiHeadAttention (self-attention): a training forward and its backward (transformer/SubLayers.py:8-59) =====================
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  With q = k = v = x [B, S, d], M = B * S rows, H heads,
+ * dk = d / H, c = 1 / sqrt(dk):
+ *   qkv = x [Wq; Wk; Wv]^T + [bq; bk; bv]      [M, 3d], head h at h * dk inside each third
+ *   P   = softmax_j(c Q K^T), keys j >= lens[b] masked     per (b, h); never written to memory
+ *   ctx = merge_heads(P V);  z = dropout(ctx Wfc^T + bfc) + x;  y = LayerNorm(z)
+ * Padded QUERY rows are computed like any other and y is not masked (FFTBlock does that outside).  The weights are LIVE device tensors
+ * in checkpoint layout; dropout is a uint8 keep-mask [M, d] (1 = kept) and p_drop.  Exact fp32 on the fp32 matrix cores; column sums,
+ * row statistics and D = dctx . ctx in float64, rounded once.  No atomic, no host read; equal inputs give equal bits.
+ * lens: int64 [B] on the device, NULL = every key valid.  An utterance with lens[b] == 0 has NaN in ctx (as the reference has). */
+#define NS_AG_ABI_VERSION 1
+int ns_ag_abi_version(void);
+typedef struct ns_ag_shape { int32_t B, S, d, H; } ns_ag_shape;
+/* Device pointers, 16-byte aligned, fp32, checkpoint layout. */
+typedef struct ns_ag_weights {
+  const float* wq;    /* [d, d] w_qs.weight */
+  const float* bq;    /* [d] */
+  const float* wk;    /* [d, d] w_ks.weight */
+  const float* bk;    /* [d] */
+  const float* wv;    /* [d, d] w_vs.weight */
+  const float* bv;    /* [d] */
+  const float* wfc;   /* [d, d] fc.weight */
+  const float* bfc;   /* [d] */
+  const float* ln_g;  /* [d] layer_norm.weight */
+  const float* ln_b;  /* [d] */
+} ns_ag_weights;
+/* The outputs of ns_ag_backward: the same ten, shaped alike, and dx [B, S, d].  16-byte aligned.  NULL = not wanted: neither
+ * computed nor written, and a launch none of whose outputs is wanted is not made. */
+typedef struct ns_ag_grads {
+  float *wq, *bq, *wk, *bk, *wv, *bv, *wfc, *bfc, *ln_g, *ln_b, *dx;
+} ns_ag_grads;
+/* Bytes of the workspace of ns_ag_forward / ns_ag_backward of this shape (0 and ns_last_error() for a refused shape), and of `saved`:
+ * qkv [M, 3d] | ctx [M, d] | z [M, d] | lse [B, H, S] floats, in this order, dense. */
+size_t ns_ag_ws_bytes(const ns_ag_shape* shape);
+size_t ns_ag_saved_bytes(const ns_ag_shape* shape);
+/* Kernel launches the calling thread's last ns_ag_* call enqueued. */
+int ns_ag_last_launches(void);
+/* Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a pointer that is not 16-byte
+ * aligned (lens: 8), d not 256 or 512, d % H != 0, dk not in {32, 64, 128}, B * S * 3d >= 2^31, p_drop outside [0, 1), a keep-mask
+ * without p_drop > 0 or p_drop > 0 without one, a workspace smaller than ns_ag_ws_bytes.
+ * y [B, S, d].  saved: ns_ag_saved_bytes, or NULL (nothing kept, no lse launch: the no_grad forward).
+ * Launches: 1 (pack) + G(M, 3d, d) + 1 (attention) + 1 (lse, only with `saved`) + G(M, d, d) + 1 (row), where G(M, N, K) is the
+ * Conv1D-as-GEMM dispatch's own launch count for that shape (ns_plan_gemm_launches, 1 or 2). */
+int ns_ag_forward(const ns_ag_shape* shape, const ns_ag_weights* weights, const float* x, const int64_t* lens, const uint8_t* keep,
+                  float p_drop, float* y, void* saved, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of sum g[m, :] . y[m, :] (g [B, S, d], read on every row) with respect to every non-NULL member of grads, from `saved`
+ * as ns_ag_forward wrote it for the same arguments.
+ * Launches with every output wanted: 1 (pack) + 1 (row backward) + 2 (dWfc: GEMM, reduce) + G(M, d, d) (dctx) + 2 (attention
+ * backward: the query-owning and the key-owning kernel) + 3 * 2 (dWq, dWk, dWv) + 1 (column sums of dqkv) + G(M, d, 3d) (dx, the
+ * residual branch dz added in its epilogue) + 1 (final column sums) = 14 + G(M, d, d) + G(M, d, 3d).  An unwanted weight gradient
+ * drops its 2 launches, dx its GEMM, the three projection biases their column sums; with nothing wanted upstream of ctx (only wfc,
+ * bfc, ln_g, ln_b) the pack, dctx and the attention backward are dropped too. */
+int ns_ag_backward(const ns_ag_shape* shape, const ns_ag_weights* weights, const float* x, const int64_t* lens, const uint8_t* keep,
+                   float p_drop, const void* saved, const float* g, const ns_ag_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* Each new kernel alone.  lse [B, H, S] from qkv [B*S, 3d]: one launch. */
+int ns_ag_op_lse(const float* qkv, const int64_t* lens, int B, int S, int d, int H, float* lse, void* stream);
+/* dqkv [B*S, 3d] = (dQ | dK | dV) from qkv, ctx [B*S, d], lse and dctx [B*S, d]; dK and dV rows at keys >= lens[b] are +0.0 and
+ * nothing those rows of qkv hold is read into a sum.  ws: B * H * S floats (D).  Two launches. */
+int ns_ag_op_attention_backward(const float* qkv, const float* ctx, const float* lse, const float* dctx, const int64_t* lens, int B, int S,
+                                int d, int H, float* dqkv, void* ws, size_t ws_bytes, void* stream);
+/* The row-local backward of y = LayerNorm(z), z = dropout(u) + x on M rows of d columns from dy [M, d] and the saved z: dz (the
+ * residual branch of dx), du = dz keep / (1 - p), d_ln_g, d_ln_b and d_bfc = column sums of du (all required).  keep [M, d] iff
+ * p_drop > 0.  ws: ceil(M / 64) * 5 * d doubles.  Two launches. */
+int ns_ag_op_row_backward(const float* dy, const float* z, const float* ln_g, const uint8_t* keep, float p_drop, int M, int d, float* dz,
+                          float* du, float* d_ln_g, float* d_ln_b, float* d_bfc, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,24 @@ class NsPgGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PG_NAMES + ("dx",)]
 
 
+class NsAgShape(C.Structure):
+    """``ns_ag_shape`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "S", "d", "H")]
+
+
+AG_NAMES = ("wq", "bq", "wk", "bk", "wv", "bv", "wfc", "bfc", "ln_g", "ln_b")
+
+
+class NsAgWeights(C.Structure):
+    """``ns_ag_weights`` (include/nar_fs2.h): the ten parameters in checkpoint layout."""
+    _fields_ = [(n, C.c_void_p) for n in AG_NAMES]
+
+
+class NsAgGrads(C.Structure):
+    """``ns_ag_grads`` (include/nar_fs2.h): the ten parameter gradients and ``dx``, each nullable."""
+    _fields_ = [(n, C.c_void_p) for n in AG_NAMES + ("dx",)]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -273,6 +291,16 @@ SIGNATURES = {
     "ns_pg_op_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "ns_pg_op_dgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "ns_pg_op_row_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    # MultiHeadAttention (self-attention) training forward and backward (sublayers.MultiHeadAttention; handle-less)
+    "ns_ag_abi_version": (_I, []),
+    "ns_ag_ws_bytes": (_Z, [C.POINTER(NsAgShape)]),
+    "ns_ag_saved_bytes": (_Z, [C.POINTER(NsAgShape)]),
+    "ns_ag_last_launches": (_I, []),
+    "ns_ag_forward": (_I, [C.POINTER(NsAgShape), C.POINTER(NsAgWeights), _P, _P, _P, _F, _P, _P, _P, _Z, _P]),
+    "ns_ag_backward": (_I, [C.POINTER(NsAgShape), C.POINTER(NsAgWeights), _P, _P, _P, _F, _P, _P, C.POINTER(NsAgGrads), _P, _Z, _P]),
+    "ns_ag_op_lse": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "ns_ag_op_attention_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "ns_ag_op_row_backward": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -1,0 +1,272 @@
+// C-ABI of the MultiHeadAttention training forward and backward (include/nar_fs2.h ns_ag_*; transformer/SubLayers.py:8-59, self-attention).
+// No handle: the weights are the caller's live tensors in checkpoint layout, the workspace and the saved activations belong to the
+// caller.  Host-side only; every argument is validated before the first HIP call.  The four Linears run on what predgrad.hip and
+// gemm_conv.hip already have (launch_conv_gemm at KW = 1, launch_pg_wgrad, launch_pg_col_final); the launch counts are stated in the
+// header.
+#include "../../include/nar_fs2.h"
+#include "host_core.h"
+
+using namespace ns;
+
+static_assert(sizeof(ns_ag_shape) == 16, "ns_ag_shape layout");
+static_assert(sizeof(ns_ag_weights) == 10 * sizeof(void*) && sizeof(ns_ag_grads) == 11 * sizeof(void*), "ns_ag_weights / ns_ag_grads layout");
+
+namespace {
+thread_local int t_launches = 0;
+
+struct Ws {  // the workspace of one shape, carved in this order
+  float *wp, *bp, *wt, *wfct;  // [3d][d] and [3d] (forward), [d][3d] and [d][d] (data gradients)
+  float* partial;              // the weight gradient's per-range tiles
+  double* colpart;             // [2][row blocks][PG_SLOTS][d]
+  float *a, *b, *c;            // [M, d] each: u (forward); dz, du, dctx (backward)
+  float* wide;                 // [M, 3d]: dqkv (backward), qkv of a forward that saves nothing
+  float* stat;                 // [B, H, S]: D (backward)
+};
+
+bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+int check_dims(int B, int S, int d, int H, const std::string& w) {
+  if (B <= 0 || S <= 0) return api_fail(w + "B and S must be positive, got " + std::to_string(B) + " x " + std::to_string(S));
+  if (d != 256 && d != 512) return api_fail(w + "d must be 256 or 512, got " + std::to_string(d));
+  if (H <= 0 || d % H != 0) return api_fail(w + "d must be a multiple of H, got d = " + std::to_string(d) + ", H = " + std::to_string(H));
+  const int dk = d / H;
+  if (dk != 32 && dk != 64 && dk != 128) return api_fail(w + "d / H must be 32, 64 or 128, got " + std::to_string(dk));
+  if ((long long)B * S * 3 * d >= (1ll << 31)) return api_fail(w + "problem too large: B * S * 3d must stay below 2^31");
+  return 0;
+}
+
+int carve(const ns_ag_shape& s, void* base, Ws* ws, size_t* bytes, const std::string& w) {
+  const int M = s.B * s.S, d = s.d;
+  PgWgradPlan pl;
+  if (!pg_plan_wgrad(M, d, d, 1, &pl)) return api_fail(w + "problem too large for the weight gradient's split");
+  Bump bump(base);
+  const size_t dd = (size_t)d * d, md = (size_t)M * d;
+  ws->wp = bump.f(3 * dd); ws->bp = bump.f(3 * (size_t)d); ws->wt = bump.f(3 * dd); ws->wfct = bump.f(dd);
+  ws->partial = bump.f((size_t)pl.ws_floats);
+  ws->colpart = (double*)bump.raw((size_t)2 * pg_row_blocks(M) * PG_SLOTS * d * sizeof(double));
+  ws->a = bump.f(md); ws->b = bump.f(md); ws->c = bump.f(md);
+  ws->wide = bump.f(3 * md);
+  ws->stat = bump.f((size_t)s.B * s.H * s.S);
+  *bytes = bump.off;
+  return 0;
+}
+
+int check_drop(const uint8_t* keep, float p, const std::string& w) {
+  if (!(p >= 0.f && p < 1.f)) return api_fail(w + "p_drop must lie in [0, 1)");
+  if (p > 0.f && !keep) return api_fail(w + "p_drop > 0 needs a keep-mask");
+  if (p == 0.f && keep) return api_fail(w + "keep-mask given although p_drop == 0");
+  if (misaligned(keep)) return api_fail(w + "the keep-mask must be 16-byte aligned");
+  return 0;
+}
+
+int check_weights(const ns_ag_weights* k, const std::string& w) {
+  const void* p[10] = {k->wq, k->bq, k->wk, k->bk, k->wv, k->bv, k->wfc, k->bfc, k->ln_g, k->ln_b};
+  const char* names[10] = {"wq", "bq", "wk", "bk", "wv", "bv", "wfc", "bfc", "ln_g", "ln_b"};
+  for (int i = 0; i < 10; ++i) {
+    if (!p[i]) return api_fail(w + "null weights->" + names[i]);
+    if (misaligned(p[i])) return api_fail(w + "weights->" + names[i] + " must be 16-byte aligned");
+  }
+  return 0;
+}
+
+// Y [M, N] = X [M, K] W[N][K]^T + bias + resid through the forward's dispatch; counts its launches
+int gemm(const float* X, const float* W, const float* bias, const float* resid, float* Y, int M, int S, int N, int K, hipStream_t st) {
+  ConvGemm p;
+  memset(&p, 0, sizeof(p));
+  p.X = X; p.ldx = K; p.W = W; p.bias = bias; p.resid = resid; p.ldr = N; p.Y = Y; p.ldy = N;
+  p.M = M; p.N = N; p.Cin = K; p.KW = 1; p.pad = 0; p.S = S; p.act = ACT_NONE; p.epi = EPI_NONE;
+  int rec[2][8];
+  const int n = conv_gemm_describe(M, N, K, 1, 0, rec);
+  if (n <= 0) return api_fail("ns_ag: the Conv1D-as-GEMM dispatch refuses this shape");
+  NS_HIP(launch_conv_gemm(p, st));
+  t_launches += n;
+  return 0;
+}
+
+int common(const char* who, const ns_ag_shape* s, const ns_ag_weights* k, const float* x, const int64_t* lens, const uint8_t* keep, float p_drop,
+           const void* saved, void* ws_mem, size_t ws_bytes, Ws* ws) {
+  const std::string w = std::string(who) + ": ";
+  NS_TRY(check_dims(s->B, s->S, s->d, s->H, w));
+  NS_TRY(check_weights(k, w));
+  NS_TRY(check_drop(keep, p_drop, w));
+  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
+  if ((uintptr_t)lens & 7) return api_fail(w + "lens must be 8-byte aligned");
+  size_t need = 0;
+  NS_TRY(carve(*s, ws_mem, ws, &need, w));
+  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_ag_ws_bytes)");
+  return 0;
+}
+}  // namespace
+
+extern "C" int ns_ag_abi_version(void) { return NS_AG_ABI_VERSION; }
+extern "C" int ns_ag_last_launches(void) { return t_launches; }
+
+extern "C" size_t ns_ag_ws_bytes(const ns_ag_shape* s) {
+  const std::string w = "ns_ag_ws_bytes: ";
+  if (!s) { api_fail(w + "null argument"); return 0; }
+  if (check_dims(s->B, s->S, s->d, s->H, w)) return 0;
+  Ws ws; size_t bytes = 0;
+  if (carve(*s, nullptr, &ws, &bytes, w)) return 0;
+  return bytes;
+}
+
+extern "C" size_t ns_ag_saved_bytes(const ns_ag_shape* s) {
+  const std::string w = "ns_ag_saved_bytes: ";
+  if (!s) { api_fail(w + "null argument"); return 0; }
+  if (check_dims(s->B, s->S, s->d, s->H, w)) return 0;
+  return ((size_t)5 * s->B * s->S * s->d + (size_t)s->B * s->H * s->S) * sizeof(float);
+}
+
+extern "C" int ns_ag_forward(const ns_ag_shape* s, const ns_ag_weights* k, const float* x, const int64_t* lens, const uint8_t* keep, float p_drop,
+                             float* y, void* saved, void* ws_mem, size_t ws_bytes, void* stream) {
+  t_launches = 0;
+  if (!s || !k || !x || !y || !ws_mem) return api_fail("ns_ag_forward: null argument");
+  if (misaligned(y)) return api_fail("ns_ag_forward: y must be 16-byte aligned");
+  Ws ws;
+  NS_TRY(common("ns_ag_forward", s, k, x, lens, keep, p_drop, saved, ws_mem, ws_bytes, &ws));
+  const int M = s->B * s->S, d = s->d, H = s->H, dk = d / H;
+  const size_t md = (size_t)M * d;
+  float* qkv = saved ? (float*)saved : ws.wide;
+  float* ctx = saved ? qkv + 3 * md : ws.c;
+  float* z = saved ? qkv + 4 * md : nullptr;
+  float* lse = saved ? qkv + 5 * md : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  NS_HIP(launch_ag_pack(AgPack{k->wq, k->wk, k->wv, k->bq, k->bk, k->bv, k->wfc, ws.wp, ws.bp, nullptr, nullptr, d}, st));
+  ++t_launches;
+  NS_TRY(gemm(x, ws.wp, ws.bp, nullptr, qkv, M, s->S, 3 * d, d, st));
+  NS_HIP(launch_attention(qkv, (const long long*)lens, s->B, s->S, H, dk, ctx, nullptr, 0, nullptr, st));
+  ++t_launches;
+  if (lse) {
+    NS_HIP(launch_ag_lse(qkv, (const long long*)lens, s->B, s->S, H, dk, lse, st));
+    ++t_launches;
+  }
+  NS_TRY(gemm(ctx, k->wfc, k->bfc, nullptr, ws.a, M, s->S, d, d, st));
+  NS_HIP(launch_ag_row_forward(ws.a, x, keep, 1.f / (1.f - p_drop), k->ln_g, k->ln_b, z, y, M, d, st));
+  ++t_launches;
+  return 0;
+}
+
+extern "C" int ns_ag_backward(const ns_ag_shape* s, const ns_ag_weights* k, const float* x, const int64_t* lens, const uint8_t* keep, float p_drop,
+                              const void* saved, const float* g, const ns_ag_grads* dg, void* ws_mem, size_t ws_bytes, void* stream) {
+  const std::string w = "ns_ag_backward: ";
+  t_launches = 0;
+  if (!s || !k || !x || !saved || !g || !dg || !ws_mem) return api_fail(w + "null argument");
+  if (misaligned(g)) return api_fail(w + "g must be 16-byte aligned");
+  float* outs[11] = {dg->wq, dg->bq, dg->wk, dg->bk, dg->wv, dg->bv, dg->wfc, dg->bfc, dg->ln_g, dg->ln_b, dg->dx};
+  for (int i = 0; i < 11; ++i)
+    if (misaligned(outs[i])) return api_fail(w + "every gradient must be 16-byte aligned");
+  Ws ws;
+  NS_TRY(common("ns_ag_backward", s, k, x, lens, keep, p_drop, saved, ws_mem, ws_bytes, &ws));
+  bool any = false;
+  for (int i = 0; i < 11; ++i) any = any || outs[i];
+  if (!any) return 0;
+  const int M = s->B * s->S, d = s->d, H = s->H, dk = d / H, nblk = pg_row_blocks(M);
+  const size_t md = (size_t)M * d;
+  const float* qkv = (const float*)saved;
+  const float* ctx = qkv + 3 * md;
+  const float* z = qkv + 4 * md;
+  const float* lse = qkv + 5 * md;
+  hipStream_t st = (hipStream_t)stream;
+  const bool bias3 = dg->bq || dg->bk || dg->bv;
+  const bool upstream = dg->dx || dg->wq || dg->wk || dg->wv || bias3;  // anything behind ctx
+  PgWgradPlan pl;
+  pg_plan_wgrad(M, d, d, 1, &pl);  // (accepted by carve above)
+  float *dz = ws.a, *du = ws.b, *dctx = ws.c, *dqkv = ws.wide;
+  double* part_row = ws.colpart + (size_t)nblk * PG_SLOTS * d;  // stage 1; stage 0 holds the three thirds of dqkv
+
+  if (upstream) {
+    NS_HIP(launch_ag_pack(AgPack{k->wq, k->wk, k->wv, k->bq, k->bk, k->bv, k->wfc, nullptr, nullptr, dg->dx ? ws.wt : nullptr, ws.wfct, d}, st));
+    ++t_launches;
+  }
+  AgRowBackward r;
+  memset(&r, 0, sizeof(r));
+  r.M = M; r.F = d; r.scale = 1.f / (1.f - p_drop); r.dy = g; r.z = z; r.ln_g = k->ln_g; r.keep = keep; r.dz = dz; r.du = du; r.part = part_row;
+  NS_HIP(launch_ag_row_backward(r, st));
+  ++t_launches;
+  if (dg->wfc) {
+    NS_HIP(launch_pg_wgrad(du, ctx, M, s->S, d, d, 1, pl, ws.partial, dg->wfc, st));
+    t_launches += 2;
+  }
+  if (upstream) {
+    NS_TRY(gemm(du, ws.wfct, nullptr, nullptr, dctx, M, s->S, d, d, st));
+    NS_HIP(launch_ag_attention_backward(qkv, ctx, lse, dctx, (const long long*)lens, s->B, s->S, H, dk, ws.stat, dqkv, st));
+    t_launches += 2;
+    float* dw[3] = {dg->wq, dg->wk, dg->wv};
+    for (int i = 0; i < 3; ++i)
+      if (dw[i]) {
+        NS_HIP(launch_pg_wgrad(dqkv + (size_t)i * d, x, M, s->S, d, d, 1, pl, ws.partial, dw[i], st, 3 * d));
+        t_launches += 2;
+      }
+    if (bias3) {
+      NS_HIP(launch_ag_colsum3(dqkv, M, d, ws.colpart, st));
+      ++t_launches;
+    }
+    if (dg->dx) NS_TRY(gemm(dqkv, ws.wt, nullptr, dz, dg->dx, M, s->S, d, 3 * d, st));
+  }
+  PgColFinal fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.out[0] = dg->bq; fin.out[1] = dg->bk; fin.out[2] = dg->bv;
+  fin.out[PG_SLOTS + 0] = dg->ln_g; fin.out[PG_SLOTS + 1] = dg->ln_b; fin.out[PG_SLOTS + 2] = dg->bfc;
+  any = false;
+  for (int i = 0; i < 2 * PG_SLOTS; ++i) any = any || fin.out[i];
+  if (any) {
+    NS_HIP(launch_pg_col_final(ws.colpart, nblk, d, fin, st));
+    ++t_launches;
+  }
+  return 0;
+}
+
+extern "C" int ns_ag_op_lse(const float* qkv, const int64_t* lens, int B, int S, int d, int H, float* lse, void* stream) {
+  const std::string w = "ns_ag_op_lse: ";
+  t_launches = 0;
+  if (!qkv || !lse) return api_fail(w + "null argument");
+  NS_TRY(check_dims(B, S, d, H, w));
+  if (misaligned(qkv) || ((uintptr_t)lse & 3) || ((uintptr_t)lens & 7)) return api_fail(w + "qkv must be 16-byte aligned (lens: 8, lse: 4)");
+  NS_HIP(launch_ag_lse(qkv, (const long long*)lens, B, S, H, d / H, lse, (hipStream_t)stream));
+  ++t_launches;
+  return 0;
+}
+
+extern "C" int ns_ag_op_attention_backward(const float* qkv, const float* ctx, const float* lse, const float* dctx, const int64_t* lens, int B, int S,
+                                           int d, int H, float* dqkv, void* ws_mem, size_t ws_bytes, void* stream) {
+  const std::string w = "ns_ag_op_attention_backward: ";
+  t_launches = 0;
+  if (!qkv || !ctx || !lse || !dctx || !dqkv || !ws_mem) return api_fail(w + "null argument");
+  NS_TRY(check_dims(B, S, d, H, w));
+  const void* al[] = {qkv, ctx, dctx, dqkv, ws_mem};
+  for (const void* p : al)
+    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
+  if (((uintptr_t)lse & 3) || ((uintptr_t)lens & 7)) return api_fail(w + "lse must be 4-byte, lens 8-byte aligned");
+  const size_t need = (size_t)B * H * S * sizeof(float);
+  if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
+  NS_HIP(launch_ag_attention_backward(qkv, ctx, lse, dctx, (const long long*)lens, B, S, H, d / H, (float*)ws_mem, dqkv, (hipStream_t)stream));
+  t_launches += 2;
+  return 0;
+}
+
+extern "C" int ns_ag_op_row_backward(const float* dy, const float* z, const float* ln_g, const uint8_t* keep, float p_drop, int M, int d, float* dz,
+                                     float* du, float* d_ln_g, float* d_ln_b, float* d_bfc, void* ws_mem, size_t ws_bytes, void* stream) {
+  const std::string w = "ns_ag_op_row_backward: ";
+  t_launches = 0;
+  if (!dy || !z || !ln_g || !dz || !du || !d_ln_g || !d_ln_b || !d_bfc || !ws_mem) return api_fail(w + "null argument");
+  if (M <= 0) return api_fail(w + "M must be positive");
+  if (d != 256 && d != 512) return api_fail(w + "d must be 256 or 512, got " + std::to_string(d));
+  if ((long long)M * d >= (1ll << 31)) return api_fail(w + "problem too large");
+  NS_TRY(check_drop(keep, p_drop, w));
+  const void* al[] = {dy, z, ln_g, dz, du, d_ln_g, d_ln_b, d_bfc, ws_mem};
+  for (const void* p : al)
+    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
+  const size_t need = (size_t)pg_row_blocks(M) * PG_SLOTS * d * sizeof(double);
+  if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
+  AgRowBackward r;
+  memset(&r, 0, sizeof(r));
+  r.M = M; r.F = d; r.scale = 1.f / (1.f - p_drop); r.dy = dy; r.z = z; r.ln_g = ln_g; r.keep = keep; r.dz = dz; r.du = du; r.part = (double*)ws_mem;
+  hipStream_t st = (hipStream_t)stream;
+  NS_HIP(launch_ag_row_backward(r, st));
+  PgColFinal fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.out[0] = d_ln_g; fin.out[1] = d_ln_b; fin.out[2] = d_bfc;
+  NS_HIP(launch_pg_col_final(r.part, pg_row_blocks(M), d, fin, st));
+  t_launches += 2;
+  return 0;
+}

@@ -354,8 +354,9 @@ struct PgWgradPlan { int tile_n, tile_c, rows, ranges, tiles, chunk; long long w
 bool pg_plan_wgrad(int M, int N, int Cin, int KW, PgWgradPlan* out);
 inline int pg_row_blocks(int M) { return (M + PG_ROW_BLOCK - 1) / PG_ROW_BLOCK; }
 // partial [ranges][N][KW * Cin] floats (uninitialised); two launches: the GEMM, then the fixed-order sum into dW [N][Cin][KW]
+// ldz: floats between rows of dz (0 = N; a column block of a wider matrix, attngrad_api.hip)
 hipError_t launch_pg_wgrad(const float* dz, const float* X, int M, int S, int N, int Cin, int KW, const PgWgradPlan& pl, float* partial,
-                           float* dW, hipStream_t st);
+                           float* dW, hipStream_t st, int ldz = 0);
 // one launch, up to two convolutions (a null w skips one): w [N][Cin][KW] -> wp [N][KW*Cin] (the forward's form, nullable) and
 // wt [Cin][KW*N] with wt[c][j*N + n] = w[n][c][KW-1-j] (the data gradient's form, nullable)
 struct PgPack { const float* w; float* wp; float* wt; int N, Cin, KW; };
@@ -376,6 +377,31 @@ hipError_t launch_pg_colsum(const float* dz, int M, int F, double* part, hipStre
 // (slot 4 is a scalar: column 0 only); part holds `stages` arrays of [nblk][PG_SLOTS][F] doubles
 struct PgColFinal { float* out[2 * PG_SLOTS]; };
 hipError_t launch_pg_col_final(const double* part, int nblk, int F, const PgColFinal& o, hipStream_t st);
+// ---- MultiHeadAttention training forward / backward, self-attention (attngrad.hip; transformer/SubLayers.py:8-59) ------------------
+// qkv [B*S, 3d] in launch_attention's layout; lse, D [B, H, S]; lens [B] nullable (= S); dk in {32, 64, 128}.
+// lse[b, h, i] = log sum_{j < lens[b]} exp(q_i . k_j / sqrt(dk)); one launch
+hipError_t launch_ag_lse(const float* qkv, const long long* lens, int B, int S, int H, int dk, float* lse, hipStream_t st);
+// dqkv [B*S, 3d] = (dQ | dK | dV) from dctx [B*S, d]; two launches: the query-owning kernel (writes D[b, h, i] = dctx_i . ctx_i and
+// dQ), then the key-owning kernel (reads D, writes dK and dV; +0.0 at keys >= lens[b])
+hipError_t launch_ag_attention_backward(const float* qkv, const float* ctx, const float* lse, const float* dctx, const long long* lens, int B,
+                                        int S, int H, int dk, float* D, float* dqkv, hipStream_t st);
+// z (nullable) = u * keep * scale + x, y = LayerNorm(z) * ln_g + ln_b; rows of F = 256 / 512; keep uint8 [M, F] nullable
+hipError_t launch_ag_row_forward(const float* u, const float* x, const uint8_t* keep, float scale, const float* ln_g, const float* ln_b, float* z,
+                                 float* y, int M, int F, hipStream_t st);
+// LayerNorm backward from the saved z: dz, du = dz * keep * scale; part [pg_row_blocks(M)][PG_SLOTS][F] doubles, slots 0 .. 2 written
+// (d_ln_g, d_ln_b, column sums of du), summed by launch_pg_col_final
+struct AgRowBackward {
+  int M, F; float scale;
+  const float *dy, *z, *ln_g; const uint8_t* keep;
+  float *dz, *du; double* part;
+};
+hipError_t launch_ag_row_backward(const AgRowBackward& a, hipStream_t st);
+// part[blk][third][:] = column sums of rows [64 blk, 64 blk + 64) of dqkv[:, third * d .. third * d + d): launch_pg_col_final at F = d
+hipError_t launch_ag_colsum3(const float* dqkv, int M, int d, double* part, hipStream_t st);
+// one launch: wp [3d][d] = Wq | Wk | Wv and bp [3d] (the forward's form), wt [d][3d] = wp^T and wfct [d][d] = Wfc^T (the data
+// gradients' form); each output nullable
+struct AgPack { const float *wq, *wk, *wv, *bq, *bk, *bv, *wfc; float *wp, *bp, *wt, *wfct; int d; };
+hipError_t launch_ag_pack(const AgPack& p, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

@@ -25,7 +25,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int PG_LD = 160;
 
 __global__ __launch_bounds__(256) void k_pg_wgrad(const float* __restrict__ dz, const float* __restrict__ X, int M, int S, int N, int Cin,
-                                                  int KW, int rows, int tiles_c, int fl, float* __restrict__ partial) {
+                                                  int KW, int rows, int tiles_c, int fl, float* __restrict__ partial, int ldz) {
   __shared__ __attribute__((aligned(16))) float As[2][PG_STEP_ROWS * PG_LD];
   __shared__ __attribute__((aligned(16))) float Bs[2][PG_STEP_ROWS * PG_LD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void k_pg_wgrad(const float* __restrict__ dz, 
       const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
       ra[i] = zero; rb[i] = zero;
       if (m < mend) {
-        if (n_ok) ra[i] = *reinterpret_cast<const f32x4*>(dz + (size_t)m * N + n0 + cg);
+        if (n_ok) ra[i] = *reinterpret_cast<const f32x4*>(dz + (size_t)m * ldz + n0 + cg);
         const int t = m % S + j - pad;
         if (kk_ok && t >= 0 && t < S) rb[i] = *reinterpret_cast<const f32x4*>(X + (size_t)(m + j - pad) * Cin + c);
       }
@@ -159,10 +159,10 @@ bool pg_plan_wgrad(int M, int N, int Cin, int KW, PgWgradPlan* out) {
 }
 
 hipError_t launch_pg_wgrad(const float* dz, const float* X, int M, int S, int N, int Cin, int KW, const PgWgradPlan& pl, float* partial,
-                           float* dW, hipStream_t st) {
+                           float* dW, hipStream_t st, int ldz) {
   const int tiles_c = pl.tiles / (N / PG_TILE_N);
   hipLaunchKernelGGL(k_pg_wgrad, dim3(pl.tiles, pl.ranges), dim3(256), 0, st, dz, X, M, S, N, Cin, KW, pl.rows, tiles_c, pl.chunk / PG_STEP_ROWS,
-                     partial);
+                     partial, ldz > 0 ? ldz : N);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const long long n = (long long)N * Cin;

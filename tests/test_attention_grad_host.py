@@ -1,0 +1,261 @@
+"""The yardstick of tests/test_gpu_attention_grad.py proven on the CPU, and every refusal of the ns_ag_* family (no GPU).
+
+On the fixture (tests/golden/attention_grad_tiny.npz, the reference's own MultiHeadAttention in train() at dropout 0 with q = k = v) the
+float64 restatement agrees with the reference's float64 autograd to <= 1e-10 relative; in fp32 the assertion allows one fp32 ulp of
+the tensor's largest magnitude, because torch's CPU matmul may split its sums differently with another thread count.  (d_bk is zero
+in exact arithmetic — the softmax does not see a key bias — so its fixture values are rounding noise around 5e-7 in fp32 and 1e-15 in
+float64; its 1e-10 and its ulp are taken relative to the other gradients' scale, not to its own maximum.)"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from tests import attention_grad_cpu as ac
+from tests import lossgrad_cpu as lg
+from tests.util import load_golden
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as ge
+
+    ge.build()
+    import smart_nar_fast_tts_amd._lib as L
+
+    return L, L.load()
+
+
+def _fixture(c):
+    meta, z = load_golden("attention_grad_tiny")
+    w = {k: z[f"{c}_w_{k}"] for k in ac.NAMES[:10]}
+    return meta, z, w, z[f"{c}_x"], z[f"{c}_g"], meta["lens"], meta["configs"][c]
+
+
+# ---------------------------------------------------------------------------------------------------- the yardstick
+@pytest.mark.parametrize("c", ["a", "b"])
+def test_restatement_reproduces_the_reference(c):
+    meta, z, w, x, g, lens, H = _fixture(c)
+    r64, f64 = ac.autograd_ref(x, w, lens, H, g, dtype=torch.float64)
+    r32, f32 = ac.autograd_ref(x, w, lens, H, g, dtype=torch.float32)
+    assert np.abs(f64["y"].numpy() - z[f"{c}_y_f64"]).max() <= 1e-10 * np.abs(z[f"{c}_y_f64"]).max()
+    assert np.abs(f32["y"].numpy().astype(np.float64) - z[f"{c}_y"]).max() <= lg.ulp32(np.abs(z[f"{c}_y"]).max())
+    scale = max(np.abs(z[f"{c}_d_{n}_f64"]).max() for n in ac.NAMES)
+    for n in ac.NAMES:
+        want64, want32 = z[f"{c}_d_{n}_f64"], z[f"{c}_d_{n}"]
+        assert r64[n].shape == want64.shape
+        # (d_bk is zero up to rounding: relative to the gradients' common scale)
+        assert np.abs(r64[n] - want64).max() <= 1e-10 * (scale if n == "bk" else np.abs(want64).max()), n
+        err = np.abs(r32[n].astype(np.float64) - want32.astype(np.float64)).max()
+        print(f"{c} {n}: fp32 restatement vs reference {err:.3g} ({'bitwise' if err == 0 else 'ulp of max: %.3g' % lg.ulp32(np.abs(want32).max())})")
+        assert err <= lg.ulp32(np.abs(z[f"{c}_d_bq"]).max() if n == "bk" else np.abs(want32).max()), n
+
+
+@pytest.mark.parametrize("p", [0.0, 0.5])
+@pytest.mark.parametrize("c", ["a", "b"])
+def test_closed_form_equals_float64_autograd(c, p):
+    meta, z, w, x, g, lens, H = _fixture(c)
+    keep = (np.random.RandomState(7).rand(*x.shape) >= p) if p > 0 else None
+    ref, fwd = ac.autograd_ref(x, w, lens, H, g, keep, p, torch.float64)
+    got = ac.closed_form(x, w, lens, H, g, (fwd["qkv"], fwd["ctx"], fwd["z"], fwd["lse"]), keep, p, torch.float64)
+    scale = max(np.abs(ref[n]).max() for n in ac.NAMES)
+    for n in ac.NAMES:
+        assert np.abs(got[n] - ref[n]).max() <= 1e-10 * (scale if n == "bk" else np.abs(ref[n]).max()), n
+    # masked keys: dK and dV rows past lens[b] are exactly zero, padded QUERY rows still carry a dQ
+    d = x.shape[-1]
+    pad = np.arange(x.shape[1])[None, :] >= np.asarray(lens)[:, None]
+    assert not got["_dqkv"][..., d:][pad].any() and np.abs(got["_dqkv"][..., :d][pad]).max() > 0
+
+
+def _gated(x, w, lens, H, g, keep, p):
+    """(saved tensors of the fp32 forward, float64 closed form from them, fp32 closed form, the gates)"""
+    fwd = ac.statement(x, w, lens, H, keep, p, torch.float32)
+    saved = tuple(fwd[k].detach() for k in ("qkv", "ctx", "z", "lse"))
+    r64 = ac.closed_form(x, w, lens, H, g, saved, keep, p, torch.float64)
+    r32 = ac.closed_form(x, w, lens, H, g, saved, keep, p, torch.float32)
+    return saved, r64, r32, ac.gate(r32, r64)
+
+
+@pytest.mark.parametrize("mutant", ac.MUTANTS)
+def test_gate_rejects_mutant(mutant):
+    """each mutant, evaluated in float64 (its only error is the mutation), is outside the gate of at least one tensor; the fp32 closed
+    form itself is inside every gate (share <= 0.5 by construction)"""
+    B, S, d, H = 4, 9, 32, 2
+    lens = [9, 1, 5, 9]
+    w = ac.seeded_weights(d, seed=3)
+    rs = np.random.RandomState(11)
+    x = rs.standard_normal((B, S, d)).astype(np.float32)
+    g = rs.standard_normal((B, S, d)).astype(np.float32)
+    if mutant == "lse_without_max":  # scores around +90: exp overflows fp32 without the row maximum
+        shift = np.float32(np.sqrt(90.0 / np.sqrt(d // H)))
+        w = dict(w, bq=w["bq"] + shift, bk=w["bk"] + shift)
+    p = 0.5 if mutant == "keep_scale_dropped" else 0.0
+    keep = (rs.rand(B, S, d) >= p) if p > 0 else None
+    saved, r64, r32, gates = _gated(x, w, lens, H, g, keep, p)
+    if mutant == "lse_without_max":
+        assert 60 < float(saved[3].max()) and not bool(torch.isfinite(ac.lse_of(saved[0], lens, H, torch.float32, with_max=False)).all())
+    good = ac.shares(r32, r64, gates)
+    assert max(good.values()) <= 0.5 + 1e-12
+    bad = ac.shares(ac.closed_form(x, w, lens, H, g, saved, keep, p, torch.float64, mutate=mutant), r64, gates)
+    worst = max(bad, key=bad.get)
+    print(f"{mutant}: worst share {bad[worst]:.3g} ({worst})")
+    assert bad[worst] > 1.0
+    expected = {"D_dropped": "wq", "c_applied_once": "wk", "dK_without_transpose": "wk", "masked_keys_exp0": "wv", "residual_dropped": "dx",
+                "keep_scale_dropped": "wfc", "db_over_valid_rows_only": "bq", "heads_swapped": "wq", "lse_without_max": "wv"}
+    assert bad[expected[mutant]] > 1.0, bad
+
+
+def test_a_nan_share_is_infinite_and_a_zero_gradient_exact():
+    z = {n: np.zeros(3) for n in ac.NAMES}
+    gates = ac.gate(z, z)
+    assert all(v < 1e-40 for v in gates.values())
+    assert ac.shares(dict(z, wq=np.array([0.0, 1e-30, 0.0])), z, gates)["wq"] > 1.0 and ac.shares(z, z, gates)["wq"] == 0.0
+    assert ac.shares(dict(z, bq=np.array([0.0, np.nan, 0.0])), z, gates)["bq"] == float("inf")
+    assert "wk" not in ac.shares(dict(z, wk=None), z, gates)
+
+
+# ---------------------------------------------------------------------------------------------------- sizes and refusals (no device work)
+def _align(n):
+    return (n + 255) & ~255
+
+
+def test_sizes(lib):
+    L, so = lib
+    assert so.ns_ag_abi_version() == 1
+    for B, S, d, H in ((2, 1, 256, 2), (3, 343, 512, 8), (16, 1000, 256, 2)):
+        s = L.NsAgShape(B, S, d, H)
+        M = B * S
+        assert so.ns_ag_saved_bytes(C.byref(s)) == (5 * M * d + B * H * S) * 4
+        plan = (C.c_int32 * 8)()
+        assert so.ns_pg_plan_wgrad(M, d, d, 1, plan) == 0
+        want = (2 * _align(12 * d * d) + _align(12 * d) + _align(4 * d * d) + _align(4 * plan[5]) + _align(8 * 2 * ((M + 63) // 64) * 5 * d)
+                + 3 * _align(4 * M * d) + _align(12 * M * d) + _align(4 * B * H * S))
+        assert so.ns_ag_ws_bytes(C.byref(s)) == want
+
+
+def test_every_refusal_precedes_the_first_hip_call(lib):
+    L, so = lib
+    err = lambda: so.ns_last_error().decode()  # noqa: E731
+    P = lambda a: C.c_void_p(a) if a else None  # noqa: E731  (made-up device addresses: never dereferenced)
+    ok_shape = dict(B=2, S=8, d=256, H=2)
+
+    def weights(**over):
+        w = L.NsAgWeights()
+        for i, n in enumerate(L.AG_NAMES):
+            setattr(w, n, over.get(n, 0x100000 + 0x100000 * i))
+        return w
+
+    def fwd(shape=None, w=None, x=0x9000000, lens=0x9100000, keep=None, p=0.0, y=0xA000000, saved=0xB000000, ws=0xC000000, nbytes=1 << 40):
+        s = L.NsAgShape(**dict(ok_shape, **(shape or {})))
+        return so.ns_ag_forward(C.byref(s), C.byref(w or weights()), P(x), P(lens), P(keep), p, P(y), P(saved), P(ws), nbytes, None)
+
+    def bwd(shape=None, w=None, x=0x9000000, lens=0x9100000, keep=None, p=0.0, saved=0xB000000, g=0xD000000, grads=None, ws=0xC000000, nbytes=1 << 40):
+        s = L.NsAgShape(**dict(ok_shape, **(shape or {})))
+        d = grads or L.NsAgGrads()
+        return so.ns_ag_backward(C.byref(s), C.byref(w or weights()), P(x), P(lens), P(keep), p, P(saved), P(g), C.byref(d), P(ws), nbytes, None)
+
+    for call in (fwd, bwd):
+        for kw, msg in ((dict(x=0), "null argument"), (dict(ws=0), "null argument"), (dict(x=0x9000004), "16-byte aligned"),
+                        (dict(lens=0x9100004), "lens must be 8-byte aligned"), (dict(shape=dict(d=128)), "d must be 256 or 512"),
+                        (dict(shape=dict(d=384)), "d must be 256 or 512"), (dict(shape=dict(H=3)), "d must be a multiple of H"),
+                        (dict(shape=dict(H=0)), "d must be a multiple of H"), (dict(shape=dict(H=1)), "d / H must be 32, 64 or 128"),
+                        (dict(shape=dict(H=16)), "d / H must be 32, 64 or 128"), (dict(shape=dict(B=0)), "must be positive"),
+                        (dict(shape=dict(B=1 << 11, S=1 << 11)), "problem too large"), (dict(p=1.0), "p_drop must lie in [0, 1)"),
+                        (dict(p=-0.1), "p_drop must lie in [0, 1)"), (dict(p=float("nan")), "p_drop must lie in [0, 1)"),
+                        (dict(p=0.5), "needs a keep-mask"), (dict(keep=0xE000000), "although p_drop == 0"),
+                        (dict(p=0.5, keep=0xE000004), "16-byte aligned"), (dict(w=weights(wk=0)), "null weights->wk"),
+                        (dict(w=weights(ln_g=0x100004)), "weights->ln_g must be 16-byte aligned"), (dict(nbytes=1024), "workspace too small")):
+            assert call(**kw) != 0 and msg in err(), (call.__name__, kw, err())
+    assert fwd(lens=0, nbytes=64) != 0 and "workspace too small" in err()  # lens is nullable
+    assert fwd(y=0) != 0 and "null argument" in err()
+    assert fwd(y=0xA000004) != 0 and "16-byte aligned" in err()
+    assert bwd(saved=0) != 0 and "null argument" in err()
+    assert bwd(g=0) != 0 and "null argument" in err()
+    d = L.NsAgGrads()
+    d.wq = 0x1000004
+    assert bwd(grads=d) != 0 and "every gradient must be 16-byte aligned" in err()
+    assert bwd() == 0 and so.ns_ag_last_launches() == 0  # nothing wanted: nothing launched, no HIP call
+
+    def lse(qkv=0x100000, lens=0x200000, B=2, S=8, d=256, H=2, out=0x300000):
+        return so.ns_ag_op_lse(P(qkv), P(lens), B, S, d, H, P(out), None)
+
+    def attn(qkv=0x100000, ctx=0x200000, lse_=0x300000, dctx=0x400000, lens=0x500000, B=2, S=8, d=256, H=2, out=0x600000, ws=0x700000, nbytes=1 << 40):
+        return so.ns_ag_op_attention_backward(P(qkv), P(ctx), P(lse_), P(dctx), P(lens), B, S, d, H, P(out), P(ws), nbytes, None)
+
+    for call in (lse, attn):
+        for kw, msg in ((dict(qkv=0), "null argument"), (dict(out=0), "null argument"), (dict(qkv=0x100008), "16-byte aligned"), (dict(d=300), "d must be 256 or 512"),
+                        (dict(H=7), "d must be a multiple of H"), (dict(H=1), "d / H must be 32, 64 or 128"), (dict(S=0), "must be positive"),
+                        (dict(B=1 << 11, S=1 << 11), "problem too large")):
+            assert call(**kw) != 0 and msg in err(), (call.__name__, kw, err())
+    assert attn(nbytes=16) != 0 and "workspace too small" in err()
+    assert attn(ctx=0) != 0 and "null argument" in err()
+
+    def row(dy=0x100000, z=0x200000, ln_g=0x210000, keep=None, p=0.0, M=16, d=256, o=(0x300000, 0x310000, 0x320000, 0x330000, 0x340000), ws=0x500000,
+            nbytes=1 << 40):
+        return so.ns_ag_op_row_backward(P(dy), P(z), P(ln_g), P(keep), p, M, d, *[P(q) for q in o], P(ws), nbytes, None)
+
+    for kw, msg in ((dict(z=0), "null argument"), (dict(dy=0), "null argument"), (dict(o=(0x300000, 0, 0x320000, 0x330000, 0x340000)), "null argument"),
+                    (dict(d=128), "d must be 256 or 512"), (dict(M=0), "must be positive"), (dict(p=0.3), "needs a keep-mask"),
+                    (dict(keep=0x600000), "although p_drop == 0"), (dict(z=0x200004), "16-byte aligned"), (dict(nbytes=8), "workspace too small")):
+        assert row(**kw) != 0 and msg in err(), (kw, err())
+    assert so.ns_ag_ws_bytes(None) == 0 and "null argument" in err()
+    s = L.NsAgShape(2, 8, 100, 2)
+    assert so.ns_ag_ws_bytes(C.byref(s)) == 0 and "d must be 256 or 512" in err()
+    assert so.ns_ag_saved_bytes(C.byref(s)) == 0 and "d must be 256 or 512" in err()
+
+
+def test_header_is_plain_c_and_validation_works_from_c(lib, tmp_path):
+    L, so = lib
+    exe = tmp_path / "ag_host_only"
+    src = os.path.join(ROOT, "tests", "cabi", "ag_host_only.c")
+    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
+    r = subprocess.run([str(exe), L.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
+# ---------------------------------------------------------------------------------------------------- the Python surface
+def test_module_has_the_reference_names_and_no_cpu_path(lib):
+    import smart_nar_fast_tts_amd as pkg
+    import smart_nar_fast_tts_amd.workload as wl
+    from smart_nar_fast_tts_amd import sublayers
+    from tests.util import weights_for
+
+    assert pkg.MultiHeadAttention is sublayers.MultiHeadAttention
+    cfg, sd = weights_for(dict(config="tiny", weight_seed=0, frames_per_phoneme=4.0, dur_weight_scale=0.25))
+    t = wl.model_config("tiny")["transformer"]
+    d, H = t["encoder_hidden"], t["encoder_head"]
+    m = sublayers.MultiHeadAttention(H, d, d // H, d // H, dropout=t["encoder_dropout"])
+    assert sorted(n for n, _ in m.named_parameters()) == sorted(sublayers.PARAM_NAMES)
+    n_loaded = 0
+    for stack, key in (("encoder", "txt_encoder"), ("decoder", "mel_decoder")):
+        if (t[f"{stack}_hidden"], t[f"{stack}_head"]) != (d, H):
+            continue
+        for i in range(t[f"{stack}_layer"]):
+            prefix = f"{key}.layer_stack.{i}.slf_attn."
+            sub = {k[len(prefix):]: torch.as_tensor(np.asarray(v)) for k, v in sd.items() if k.startswith(prefix)}
+            if not sub:
+                continue
+            assert set(sub) == set(sublayers.PARAM_NAMES), (prefix, sorted(sub))
+            m.load_state_dict(sub)  # strict: the checkpoint's subtree, unchanged
+            n_loaded += 1
+    assert n_loaded == 2
+    assert m.training
+    x = torch.zeros(2, 5, d)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        m(x, x, x)
+    with pytest.raises(NotImplementedError, match="self-attention only"):
+        m(x, x.clone(), x)
+    with pytest.raises(ValueError, match="d_k must equal d_v"):
+        sublayers.MultiHeadAttention(2, 256, 128, 64)
+    with pytest.raises(ValueError, match=r"dropout must lie in \[0, 1\)"):
+        sublayers.MultiHeadAttention(2, 256, 128, 128, dropout=1.0)
+    with pytest.raises(ValueError, match="d_model must be 256 or 512"):
+        sublayers.MultiHeadAttention(2, 128, 64, 64)

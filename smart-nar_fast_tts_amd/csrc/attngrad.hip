@@ -2,7 +2,7 @@
 //   k_ag_lse            lse[b, h, i] = log sum_{j < lens[b]} exp(c q_i . k_j): one sweep of Q K^T with a running row maximum
 //   k_ag_bwd_q          owns 128 queries of one (b, h), sweeps the key tiles: D[i] = dctx_i . ctx_i (float64, rounded once) and dQ
 //   k_ag_bwd_kv         owns 128 keys of one (b, h), sweeps the query tiles: dK and dV; reads the D that k_ag_bwd_q left
-//   k_ag_row_forward    z = u * keep / (1 - p) + x, y = LayerNorm(z)
+//   k_ag_row_forward    z = u * keep / (1 - p) + x, y = LayerNorm(z)  (row kernels over train_rows.h, as predgrad.hip's)
 //   k_ag_row_backward   LayerNorm backward from z: dz, du = dz * keep / (1 - p), float64 column partials (d_ln_g, d_ln_b, d_bfc)
 //   k_ag_colsum3        column partials of the three thirds of dqkv (d_bq, d_bk, d_bv), in the layout k_pg_col_final sums
 //   k_ag_pack           Wq | Wk | Wv -> one [3d][d] weight + [3d] bias (forward) and the transposed forms the data gradients read
@@ -17,10 +17,10 @@
 // conflict-free ds_read_b32.  The tile is staged through registers (k_pg_wgrad's pattern): the next tile's 16-byte global loads are
 // issued before this tile's MFMAs and stored behind them.
 #include "kernels.h"
+#include "train_rows.h"
 
 namespace ns {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr float AG_LOG2E = 1.4426950408889634f, AG_LN2 = 0.6931471805599453f;
@@ -313,38 +313,7 @@ hipError_t launch_ag_attention_backward(const float* qkv, const float* ctx, cons
 }
 
 // ------------------------------------------------------------------------------------------------------------------ row kernels
-// One wave per row, lane l owns the 16-byte groups (64 i + l), as predgrad.hip's row kernels; statistics and row-local sums in float64.
-constexpr double AG_LN_EPS = 1e-5;
-
-__device__ inline double ag_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-template <int NV>
-__device__ inline void ag_row_stats(const f32x4 (&x)[NV], double* mean, double* rstd) {
-  constexpr int F = 256 * NV;
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s += (double)x[i][e];
-  const double mu = ag_wave_sum(s) / F;
-  double q = 0.0;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const double dd = (double)x[i][e] - mu; q += dd * dd; }
-  *mean = mu;
-  *rstd = 1.0 / sqrt(ag_wave_sum(q) / F + AG_LN_EPS);
-}
-__device__ inline void ag_keep4(const uint8_t* keep, size_t off, float scale, double (&k)[4]) {
-  unsigned w = 0x01010101u;
-  if (keep) w = *reinterpret_cast<const unsigned*>(keep + off);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) k[e] = ((w >> (8 * e)) & 0xffu) ? (double)scale : 0.0;
-}
-
+// One wave per row; the lane layout, the float64 row statistics, keep4 and the column-partial flush are train_rows.h's.
 template <int NV>
 __global__ __launch_bounds__(256) void k_ag_row_forward(const float* __restrict__ u, const float* __restrict__ x, const uint8_t* __restrict__ keep,
                                                        float scale, const float* __restrict__ ln_g, const float* __restrict__ ln_b,
@@ -359,13 +328,13 @@ __global__ __launch_bounds__(256) void k_ag_row_forward(const float* __restrict_
     const size_t off = (size_t)m * F + (64 * i + lane) * 4;
     const f32x4 uu = *reinterpret_cast<const f32x4*>(u + off), xx = *reinterpret_cast<const f32x4*>(x + off);
     double k[4];
-    ag_keep4(keep, off, scale, k);
+    keep4(keep, off, scale, k);
 #pragma unroll
     for (int e = 0; e < 4; ++e) zr[i][e] = (float)((double)uu[e] * k[e] + (double)xx[e]);
     if (z) *reinterpret_cast<f32x4*>(z + off) = zr[i];
   }
   double mu, rs;
-  ag_row_stats<NV>(zr, &mu, &rs);
+  row_stats<NV>(zr, &mu, &rs);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int col = (64 * i + lane) * 4;
@@ -395,12 +364,7 @@ __global__ __launch_bounds__(256) void k_ag_row_backward(AgRowBackward a) {
   __shared__ double red[4][F];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double cs[3][NV][4];
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) cs[s][i][e] = 0.0;
+  NS_COL_ZERO(cs, 3, NV);
   f32x4 g4[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) g4[i] = *reinterpret_cast<const f32x4*>(a.ln_g + (64 * i + lane) * 4);
@@ -411,7 +375,7 @@ __global__ __launch_bounds__(256) void k_ag_row_backward(AgRowBackward a) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) x[i] = *reinterpret_cast<const f32x4*>(a.z + (size_t)m * F + (64 * i + lane) * 4);
     double mu, rs;
-    ag_row_stats<NV>(x, &mu, &rs);
+    row_stats<NV>(x, &mu, &rs);
     double xh[NV][4], dyh[NV][4], s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -427,12 +391,12 @@ __global__ __launch_bounds__(256) void k_ag_row_backward(AgRowBackward a) {
         s2 += dyh[i][e] * xh[i][e];
       }
     }
-    const double m1 = ag_wave_sum(s1) / F, m2 = ag_wave_sum(s2) / F;
+    const double m1 = wave_sum(s1) / F, m2 = wave_sum(s2) / F;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const size_t off = (size_t)m * F + (64 * i + lane) * 4;
       double k[4];
-      ag_keep4(a.keep, off, a.scale, k);
+      keep4(a.keep, off, a.scale, k);
       f32x4 o, w;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -445,16 +409,7 @@ __global__ __launch_bounds__(256) void k_ag_row_backward(AgRowBackward a) {
     }
   }
   double* part = a.part + (size_t)blockIdx.x * PG_SLOTS * F;
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[wave][(64 * i + lane) * 4 + e] = cs[s][i][e];
-    __syncthreads();
-    for (int col = threadIdx.x; col < F; col += 256) part[s * F + col] = ((red[0][col] + red[1][col]) + red[2][col]) + red[3][col];
-  }
+  col_flush(cs, red, part);
 }
 
 hipError_t launch_ag_row_backward(const AgRowBackward& a, hipStream_t st) {

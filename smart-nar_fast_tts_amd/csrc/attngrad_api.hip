@@ -2,9 +2,9 @@
 // No handle: the weights are the caller's live tensors in checkpoint layout, the workspace and the saved activations belong to the
 // caller.  Host-side only; every argument is validated before the first HIP call.  The four Linears run on what predgrad.hip and
 // gemm_conv.hip already have (launch_conv_gemm at KW = 1, launch_pg_wgrad, launch_pg_col_final); the launch counts are stated in the
-// header.
+// header.  The checks, the counted GEMM launch and the column-partial finish it shares with predgrad_api.hip are train_api.h's.
 #include "../../include/nar_fs2.h"
-#include "host_core.h"
+#include "train_api.h"
 
 using namespace ns;
 
@@ -22,8 +22,6 @@ struct Ws {  // the workspace of one shape, carved in this order
   float* wide;                 // [M, 3d]: dqkv (backward), qkv of a forward that saves nothing
   float* stat;                 // [B, H, S]: D (backward)
 };
-
-bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
 int check_dims(int B, int S, int d, int H, const std::string& w) {
   if (B <= 0 || S <= 0) return api_fail(w + "B and S must be positive, got " + std::to_string(B) + " x " + std::to_string(S));
@@ -51,44 +49,26 @@ int carve(const ns_ag_shape& s, void* base, Ws* ws, size_t* bytes, const std::st
   return 0;
 }
 
-int check_drop(const uint8_t* keep, float p, const std::string& w) {
-  if (!(p >= 0.f && p < 1.f)) return api_fail(w + "p_drop must lie in [0, 1)");
-  if (p > 0.f && !keep) return api_fail(w + "p_drop > 0 needs a keep-mask");
-  if (p == 0.f && keep) return api_fail(w + "keep-mask given although p_drop == 0");
-  if (misaligned(keep)) return api_fail(w + "the keep-mask must be 16-byte aligned");
-  return 0;
-}
-
-int check_weights(const ns_ag_weights* k, const std::string& w) {
-  const void* p[10] = {k->wq, k->bq, k->wk, k->bk, k->wv, k->bv, k->wfc, k->bfc, k->ln_g, k->ln_b};
-  const char* names[10] = {"wq", "bq", "wk", "bk", "wv", "bv", "wfc", "bfc", "ln_g", "ln_b"};
-  for (int i = 0; i < 10; ++i) {
-    if (!p[i]) return api_fail(w + "null weights->" + names[i]);
-    if (misaligned(p[i])) return api_fail(w + "weights->" + names[i] + " must be 16-byte aligned");
-  }
-  return 0;
+// the ten parameters of ns_ag_weights or ns_ag_grads, in ABI order
+template <class T>
+std::vector<NamedPtr> ten(const T& k) {
+  return {{"wq", k.wq}, {"bq", k.bq}, {"wk", k.wk}, {"bk", k.bk}, {"wv", k.wv}, {"bv", k.bv}, {"wfc", k.wfc}, {"bfc", k.bfc}, {"ln_g", k.ln_g},
+          {"ln_b", k.ln_b}};
 }
 
 // Y [M, N] = X [M, K] W[N][K]^T + bias + resid through the forward's dispatch; counts its launches
 int gemm(const float* X, const float* W, const float* bias, const float* resid, float* Y, int M, int S, int N, int K, hipStream_t st) {
-  ConvGemm p;
-  memset(&p, 0, sizeof(p));
-  p.X = X; p.ldx = K; p.W = W; p.bias = bias; p.resid = resid; p.ldr = N; p.Y = Y; p.ldy = N;
-  p.M = M; p.N = N; p.Cin = K; p.KW = 1; p.pad = 0; p.S = S; p.act = ACT_NONE; p.epi = EPI_NONE;
-  int rec[2][8];
-  const int n = conv_gemm_describe(M, N, K, 1, 0, rec);
-  if (n <= 0) return api_fail("ns_ag: the Conv1D-as-GEMM dispatch refuses this shape");
-  NS_HIP(launch_conv_gemm(p, st));
-  t_launches += n;
-  return 0;
+  ConvGemm p = conv_gemm_args(X, W, bias, Y, M, S, N, K, 1, 0, ACT_NONE);
+  p.resid = resid; p.ldr = N;
+  return counted_conv_gemm(p, "ns_ag", &t_launches, st);
 }
 
 int common(const char* who, const ns_ag_shape* s, const ns_ag_weights* k, const float* x, const int64_t* lens, const uint8_t* keep, float p_drop,
            const void* saved, void* ws_mem, size_t ws_bytes, Ws* ws) {
   const std::string w = std::string(who) + ": ";
   NS_TRY(check_dims(s->B, s->S, s->d, s->H, w));
-  NS_TRY(check_weights(k, w));
-  NS_TRY(check_drop(keep, p_drop, w));
+  NS_TRY(check_weights(ten(*k), w));
+  NS_TRY(check_drop({keep}, p_drop, w));
   if (misaligned(x) || misaligned(saved) || misaligned(ws_mem)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
   if ((uintptr_t)lens & 7) return api_fail(w + "lens must be 8-byte aligned");
   size_t need = 0;
@@ -152,13 +132,12 @@ extern "C" int ns_ag_backward(const ns_ag_shape* s, const ns_ag_weights* k, cons
   t_launches = 0;
   if (!s || !k || !x || !saved || !g || !dg || !ws_mem) return api_fail(w + "null argument");
   if (misaligned(g)) return api_fail(w + "g must be 16-byte aligned");
-  float* outs[11] = {dg->wq, dg->bq, dg->wk, dg->bk, dg->wv, dg->bv, dg->wfc, dg->bfc, dg->ln_g, dg->ln_b, dg->dx};
-  for (int i = 0; i < 11; ++i)
-    if (misaligned(outs[i])) return api_fail(w + "every gradient must be 16-byte aligned");
+  std::vector<NamedPtr> outs = ten(*dg);
+  outs.push_back({"dx", dg->dx});
+  bool any = false;
+  NS_TRY(check_grads(outs, w, &any));
   Ws ws;
   NS_TRY(common("ns_ag_backward", s, k, x, lens, keep, p_drop, saved, ws_mem, ws_bytes, &ws));
-  bool any = false;
-  for (int i = 0; i < 11; ++i) any = any || outs[i];
   if (!any) return 0;
   const int M = s->B * s->S, d = s->d, H = s->H, dk = d / H, nblk = pg_row_blocks(M);
   const size_t md = (size_t)M * d;
@@ -178,10 +157,7 @@ extern "C" int ns_ag_backward(const ns_ag_shape* s, const ns_ag_weights* k, cons
     NS_HIP(launch_ag_pack(AgPack{k->wq, k->wk, k->wv, k->bq, k->bk, k->bv, k->wfc, nullptr, nullptr, dg->dx ? ws.wt : nullptr, ws.wfct, d}, st));
     ++t_launches;
   }
-  AgRowBackward r;
-  memset(&r, 0, sizeof(r));
-  r.M = M; r.F = d; r.scale = 1.f / (1.f - p_drop); r.dy = g; r.z = z; r.ln_g = k->ln_g; r.keep = keep; r.dz = dz; r.du = du; r.part = part_row;
-  NS_HIP(launch_ag_row_backward(r, st));
+  NS_HIP(launch_ag_row_backward(ag_row_backward_args(M, d, p_drop, g, z, k->ln_g, keep, dz, du, part_row), st));
   ++t_launches;
   if (dg->wfc) {
     NS_HIP(launch_pg_wgrad(du, ctx, M, s->S, d, d, 1, pl, ws.partial, dg->wfc, st));
@@ -203,17 +179,7 @@ extern "C" int ns_ag_backward(const ns_ag_shape* s, const ns_ag_weights* k, cons
     }
     if (dg->dx) NS_TRY(gemm(dqkv, ws.wt, nullptr, dz, dg->dx, M, s->S, d, 3 * d, st));
   }
-  PgColFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.out[0] = dg->bq; fin.out[1] = dg->bk; fin.out[2] = dg->bv;
-  fin.out[PG_SLOTS + 0] = dg->ln_g; fin.out[PG_SLOTS + 1] = dg->ln_b; fin.out[PG_SLOTS + 2] = dg->bfc;
-  any = false;
-  for (int i = 0; i < 2 * PG_SLOTS; ++i) any = any || fin.out[i];
-  if (any) {
-    NS_HIP(launch_pg_col_final(ws.colpart, nblk, d, fin, st));
-    ++t_launches;
-  }
-  return 0;
+  return col_finish(ws.colpart, nblk, d, {dg->bq, dg->bk, dg->bv}, {dg->ln_g, dg->ln_b, dg->bfc}, &t_launches, st);
 }
 
 extern "C" int ns_ag_op_lse(const float* qkv, const int64_t* lens, int B, int S, int d, int H, float* lse, void* stream) {
@@ -252,21 +218,15 @@ extern "C" int ns_ag_op_row_backward(const float* dy, const float* z, const floa
   if (M <= 0) return api_fail(w + "M must be positive");
   if (d != 256 && d != 512) return api_fail(w + "d must be 256 or 512, got " + std::to_string(d));
   if ((long long)M * d >= (1ll << 31)) return api_fail(w + "problem too large");
-  NS_TRY(check_drop(keep, p_drop, w));
+  NS_TRY(check_drop({keep}, p_drop, w));
   const void* al[] = {dy, z, ln_g, dz, du, d_ln_g, d_ln_b, d_bfc, ws_mem};
   for (const void* p : al)
     if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
   const size_t need = (size_t)pg_row_blocks(M) * PG_SLOTS * d * sizeof(double);
   if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
-  AgRowBackward r;
-  memset(&r, 0, sizeof(r));
-  r.M = M; r.F = d; r.scale = 1.f / (1.f - p_drop); r.dy = dy; r.z = z; r.ln_g = ln_g; r.keep = keep; r.dz = dz; r.du = du; r.part = (double*)ws_mem;
   hipStream_t st = (hipStream_t)stream;
-  NS_HIP(launch_ag_row_backward(r, st));
-  PgColFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.out[0] = d_ln_g; fin.out[1] = d_ln_b; fin.out[2] = d_bfc;
-  NS_HIP(launch_pg_col_final(r.part, pg_row_blocks(M), d, fin, st));
-  t_launches += 2;
-  return 0;
+  double* part = (double*)ws_mem;
+  NS_HIP(launch_ag_row_backward(ag_row_backward_args(M, d, p_drop, dy, z, ln_g, keep, dz, du, part), st));
+  ++t_launches;
+  return col_finish(part, pg_row_blocks(M), d, {d_ln_g, d_ln_b, d_bfc}, {}, &t_launches, st);
 }

@@ -6,12 +6,13 @@
 //   k_pg_row_forward                 LayerNorm * keep / (1 - p) of a row, and the Linear(F, 1) + masked_fill of the tail
 //   k_pg_row_backward                LayerNorm + ReLU backward of a row, per-workgroup column partials in float64
 //   k_pg_colsum / k_pg_col_final     column sums of a matrix alone; the fixed-order sum of the partials
-// No atomics, no host reads; every sum has one order that depends on the shape alone.
+// No atomics, no host reads; every sum has one order that depends on the shape alone.  The row kernels' float64 helpers (wave_sum,
+// row_stats, keep4, the column-partial flush) are train_rows.h's, shared with attngrad.hip's row kernels.
 #include "kernels.h"
+#include "train_rows.h"
 
 namespace ns {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ------------------------------------------------------------------------------------------------------------------ weight gradient
@@ -196,45 +197,7 @@ hipError_t launch_pg_pack(const PgPack& a, const PgPack& b, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ row kernels
-// One wave per row, lane l owns the 16-byte groups (64 i + l) of the row, i < NV = F / 256.  The row statistics and every row-local sum are
-// float64 (two-pass variance, xor-shuffle tree: one order), so a stored value is the float64 expression of its fp32 inputs rounded once.
-constexpr double PG_LN_EPS = 1e-5;  // nn.LayerNorm's default, which the reference keeps
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int NV>
-__device__ inline void row_stats(const f32x4 (&x)[NV], int F, double* mean, double* rstd) {
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s += (double)x[i][e];
-  const double mu = wave_sum(s) / F;
-  double q = 0.0;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const double d = (double)x[i][e] - mu; q += d * d; }
-  *mean = mu;
-  *rstd = 1.0 / sqrt(wave_sum(q) / F + PG_LN_EPS);
-}
-
-// keep bytes of this lane's group i as four scale factors (all `scale` without a mask: p = 0 passes scale = 1)
-__device__ inline void keep4(const uint8_t* keep, size_t off, float scale, double (&k)[4]) {
-  if (keep) {
-    const unsigned w = *reinterpret_cast<const unsigned*>(keep + off);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) k[e] = ((w >> (8 * e)) & 0xffu) ? (double)scale : 0.0;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) k[e] = (double)scale;
-  }
-}
-
+// One wave per row; the lane layout, the float64 row statistics, keep4 and the column-partial flush are train_rows.h's.
 template <int NV>
 __global__ __launch_bounds__(256) void k_pg_row_forward(const float* __restrict__ v, const float* __restrict__ ln_g, const float* __restrict__ ln_b,
                                                         const uint8_t* __restrict__ keep, float scale, float* __restrict__ h,
@@ -248,7 +211,7 @@ __global__ __launch_bounds__(256) void k_pg_row_forward(const float* __restrict_
 #pragma unroll
   for (int i = 0; i < NV; ++i) x[i] = *reinterpret_cast<const f32x4*>(v + (size_t)m * F + (64 * i + lane) * 4);
   double mu, rs;
-  row_stats<NV>(x, F, &mu, &rs);
+  row_stats<NV>(x, &mu, &rs);
   double dot = 0.0;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -291,12 +254,7 @@ __global__ __launch_bounds__(256) void k_pg_row_backward(PgRowBackward a) {
   __shared__ double red[4][F];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double cs[NS][NV][4];
-#pragma unroll
-  for (int s = 0; s < NS; ++s)
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) cs[s][i][e] = 0.0;
+  NS_COL_ZERO(cs, NS, NV);
   double sum_dp = 0.0;
   f32x4 g4[NV], b4[NV], w4[NV];
 #pragma unroll
@@ -312,7 +270,7 @@ __global__ __launch_bounds__(256) void k_pg_row_backward(PgRowBackward a) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) x[i] = *reinterpret_cast<const f32x4*>(a.v + (size_t)m * F + (64 * i + lane) * 4);
     double mu, rs;
-    row_stats<NV>(x, F, &mu, &rs);
+    row_stats<NV>(x, &mu, &rs);
     double dp = 0.0;
     if (TAIL) {
       float gm = 0.f;
@@ -353,16 +311,7 @@ __global__ __launch_bounds__(256) void k_pg_row_backward(PgRowBackward a) {
     }
   }
   double* part = a.part + (size_t)blockIdx.x * PG_SLOTS * F;
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[wave][(64 * i + lane) * 4 + e] = cs[s][i][e];
-    __syncthreads();
-    for (int col = threadIdx.x; col < F; col += 256) part[s * F + col] = ((red[0][col] + red[1][col]) + red[2][col]) + red[3][col];
-  }
+  col_flush(cs, red, part);
   if (TAIL) {
     __syncthreads();
     if (lane == 0) red[wave][0] = sum_dp;

@@ -1,8 +1,9 @@
 // C-ABI of the VariancePredictor training forward and backward (include/nar_fs2.h ns_pg_*; model/modules.py:233-286).  No handle:
 // the weights are the caller's live tensors in checkpoint layout, the workspace and the saved activations belong to the caller.
-// Host-side only; every argument is validated before the first HIP call.
+// Host-side only; every argument is validated before the first HIP call.  The checks, the counted GEMM launch and the column-partial
+// finish it shares with attngrad_api.hip are train_api.h's.
 #include "../../include/nar_fs2.h"
-#include "host_core.h"
+#include "train_api.h"
 
 using namespace ns;
 
@@ -43,37 +44,32 @@ int carve(const ns_pg_shape& s, void* base, Ws* ws, size_t* bytes, const std::st
   return 0;
 }
 
-bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
-
-int check_drop(const uint8_t* keep1, const uint8_t* keep2, float p, const std::string& w) {
-  if (!(p >= 0.f && p < 1.f)) return api_fail(w + "p_drop must lie in [0, 1)");
-  if (p > 0.f && (!keep1 || !keep2)) return api_fail(w + "p_drop > 0 needs both keep-masks");
-  if (p == 0.f && (keep1 || keep2)) return api_fail(w + "keep-masks given although p_drop == 0");
-  if (misaligned(keep1) || misaligned(keep2)) return api_fail(w + "keep-masks must be 16-byte aligned");
-  return 0;
-}
-
-int check_weights(const ns_pg_weights* k, const std::string& w) {
-  const void* p[10] = {k->w1, k->b1, k->ln1_g, k->ln1_b, k->w2, k->b2, k->ln2_g, k->ln2_b, k->wlin, k->blin};
-  const char* names[10] = {"w1", "b1", "ln1_g", "ln1_b", "w2", "b2", "ln2_g", "ln2_b", "wlin", "blin"};
-  for (int i = 0; i < 10; ++i) {
-    if (!p[i]) return api_fail(w + "null weights->" + names[i]);
-    if (i < 9 ? misaligned(p[i]) : ((uintptr_t)p[i] & 3) != 0) return api_fail(w + "weights->" + names[i] + " must be 16-byte aligned");
-  }
-  return 0;
+// the ten parameters of ns_pg_weights or ns_pg_grads, in ABI order (blin is one float)
+template <class T>
+std::vector<NamedPtr> ten(const T& k) {
+  return {{"w1", k.w1}, {"b1", k.b1}, {"ln1_g", k.ln1_g}, {"ln1_b", k.ln1_b}, {"w2", k.w2}, {"b2", k.b2}, {"ln2_g", k.ln2_g}, {"ln2_b", k.ln2_b},
+          {"wlin", k.wlin}, {"blin", k.blin, 4}};
 }
 
 // Y [M, N] = act(conv(X [M, Cin], W packed [N][KW * Cin]) + bias) through the forward's dispatch; counts its launches
 int conv(const float* X, const float* W, const float* bias, float* Y, int M, int S, int N, int Cin, int KW, int pad, int act, hipStream_t st) {
-  ConvGemm p;
-  memset(&p, 0, sizeof(p));
-  p.X = X; p.ldx = Cin; p.W = W; p.bias = bias; p.Y = Y; p.ldy = N;
-  p.M = M; p.N = N; p.Cin = Cin; p.KW = KW; p.pad = pad; p.S = S; p.act = act; p.epi = EPI_NONE;
-  int rec[2][8];
-  const int n = conv_gemm_describe(M, N, Cin, KW, 0, rec);
-  if (n <= 0) return api_fail("ns_pg: the Conv1D-as-GEMM dispatch refuses this shape");
-  NS_HIP(launch_conv_gemm(p, st));
-  t_launches += n;
+  return counted_conv_gemm(conv_gemm_args(X, W, bias, Y, M, S, N, Cin, KW, pad, act), "ns_pg", &t_launches, st);
+}
+
+// what ns_pg_forward and ns_pg_backward check alike, in this order; `scalar` is pred or g, a [B, S] tensor of floats
+int common(const std::string& w, const ns_pg_shape* s, const ns_pg_weights* k, const float* x, const uint8_t* keep1, const uint8_t* keep2,
+           float p_drop, const void* saved, const void* ws_mem, const float* scalar) {
+  NS_TRY(check_dims(s->B, s->S, s->F, s->Cin, s->K, 16, w));
+  NS_TRY(check_weights(ten(*k), w));
+  NS_TRY(check_drop({keep1, keep2}, p_drop, w));
+  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem) || misaligned(scalar, 4)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
+  return 0;
+}
+
+int carve_checked(const ns_pg_shape& s, void* ws_mem, size_t ws_bytes, Ws* ws, const std::string& w) {
+  size_t need = 0;
+  NS_TRY(carve(s, ws_mem, ws, &need, w));
+  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_pg_ws_bytes)");
   return 0;
 }
 }  // namespace
@@ -111,13 +107,9 @@ extern "C" int ns_pg_forward(const ns_pg_shape* s, const ns_pg_weights* k, const
   const std::string w = "ns_pg_forward: ";
   t_launches = 0;
   if (!s || !k || !x || !pred || !ws_mem) return api_fail(w + "null argument");
-  NS_TRY(check_dims(s->B, s->S, s->F, s->Cin, s->K, 16, w));
-  NS_TRY(check_weights(k, w));
-  NS_TRY(check_drop(keep1, keep2, p_drop, w));
-  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem) || ((uintptr_t)pred & 3)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
-  Ws ws; size_t need = 0;
-  NS_TRY(carve(*s, ws_mem, &ws, &need, w));
-  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_pg_ws_bytes)");
+  NS_TRY(common(w, s, k, x, keep1, keep2, p_drop, saved, ws_mem, pred));
+  Ws ws;
+  NS_TRY(carve_checked(*s, ws_mem, ws_bytes, &ws, w));
   const int M = s->B * s->S, F = s->F, K = s->K, pad = (K - 1) / 2;
   const size_t mf = (size_t)M * F;
   float* v1 = saved ? (float*)saved : ws.a;
@@ -142,22 +134,17 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
   const std::string w = "ns_pg_backward: ";
   t_launches = 0;
   if (!s || !k || !x || !saved || !g || !d || !ws_mem) return api_fail(w + "null argument");
-  NS_TRY(check_dims(s->B, s->S, s->F, s->Cin, s->K, 16, w));
-  NS_TRY(check_weights(k, w));
-  NS_TRY(check_drop(keep1, keep2, p_drop, w));
-  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem) || ((uintptr_t)g & 3)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
-  float* outs[11] = {d->w1, d->b1, d->ln1_g, d->ln1_b, d->w2, d->b2, d->ln2_g, d->ln2_b, d->wlin, d->blin, d->dx};
-  for (int i = 0; i < 11; ++i)
-    if (i == 9 ? ((uintptr_t)outs[i] & 3) != 0 : misaligned(outs[i])) return api_fail(w + "every gradient must be 16-byte aligned");
-  Ws ws; size_t need = 0;
-  NS_TRY(carve(*s, ws_mem, &ws, &need, w));
-  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_pg_ws_bytes)");
+  NS_TRY(common(w, s, k, x, keep1, keep2, p_drop, saved, ws_mem, g));
+  std::vector<NamedPtr> outs = ten(*d);
+  outs.push_back({"dx", d->dx});
+  NS_TRY(check_grads(outs, w));
+  Ws ws;
+  NS_TRY(carve_checked(*s, ws_mem, ws_bytes, &ws, w));
   const int M = s->B * s->S, F = s->F, Cin = s->Cin, K = s->K, padT = K - 1 - (K - 1) / 2;
   const size_t mf = (size_t)M * F;
   const float* v1 = (const float*)saved;
   const float* h1 = v1 + mf;
   const float* v2 = v1 + 2 * mf;
-  const float scale = 1.f / (1.f - p_drop);
   hipStream_t st = (hipStream_t)stream;
   const bool stage1 = d->w1 || d->b1 || d->ln1_g || d->ln1_b || d->dx;  // anything upstream of conv1d_2's input
   const bool stage2 = stage1 || d->w2 || d->b2 || d->ln2_g || d->ln2_b || d->wlin || d->blin;
@@ -171,11 +158,7 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
     NS_HIP(launch_pg_pack(PgPack{d->dx ? k->w1 : nullptr, nullptr, ws.w1t, F, Cin, K}, PgPack{stage1 ? k->w2 : nullptr, nullptr, ws.w2t, F, F, K}, st));
     ++t_launches;
   }
-  PgRowBackward r;
-  memset(&r, 0, sizeof(r));
-  r.tail = 1; r.M = M; r.F = F; r.scale = scale; r.g = g; r.mask = mask; r.v = v2; r.ln_g = k->ln2_g; r.ln_b = k->ln2_b; r.wlin = k->wlin;
-  r.keep = keep2; r.dz = ws.a; r.part = ws.colpart;
-  NS_HIP(launch_pg_row_backward(r, st));
+  NS_HIP(launch_pg_row_backward(pg_row_backward_args(1, M, F, p_drop, nullptr, g, mask, v2, k->ln2_g, k->ln2_b, k->wlin, keep2, ws.a, ws.colpart), st));
   ++t_launches;
   if (d->w2) {
     NS_HIP(launch_pg_wgrad(ws.a, h1, M, s->S, F, F, K, p2, ws.partial, d->w2, st));
@@ -183,10 +166,8 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
   }
   if (stage1) {
     NS_TRY(conv(ws.a, ws.w2t, nullptr, ws.b, M, s->S, F, F, K, padT, ACT_NONE, st));
-    memset(&r, 0, sizeof(r));
-    r.tail = 0; r.M = M; r.F = F; r.scale = scale; r.dy = ws.b; r.v = v1; r.ln_g = k->ln1_g; r.keep = keep1; r.dz = ws.c;
-    r.part = ws.colpart + (size_t)nblk * PG_SLOTS * F;
-    NS_HIP(launch_pg_row_backward(r, st));
+    NS_HIP(launch_pg_row_backward(pg_row_backward_args(0, M, F, p_drop, ws.b, nullptr, nullptr, v1, k->ln1_g, nullptr, nullptr, keep1, ws.c,
+                                                       ws.colpart + (size_t)nblk * PG_SLOTS * F), st));
     ++t_launches;
     if (d->w1) {
       NS_HIP(launch_pg_wgrad(ws.c, x, M, s->S, F, Cin, K, p1, ws.partial, d->w1, st));
@@ -194,17 +175,8 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
     }
     if (d->dx) NS_TRY(conv(ws.c, ws.w1t, nullptr, d->dx, M, s->S, Cin, F, K, padT, ACT_NONE, st));
   }
-  PgColFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.out[0] = d->ln2_g; fin.out[1] = d->ln2_b; fin.out[2] = d->b2; fin.out[3] = d->wlin; fin.out[4] = d->blin;
-  if (stage1) { fin.out[PG_SLOTS + 0] = d->ln1_g; fin.out[PG_SLOTS + 1] = d->ln1_b; fin.out[PG_SLOTS + 2] = d->b1; }
-  bool any = false;
-  for (int i = 0; i < 2 * PG_SLOTS; ++i) any = any || fin.out[i];
-  if (any) {
-    NS_HIP(launch_pg_col_final(ws.colpart, nblk, F, fin, st));
-    ++t_launches;
-  }
-  return 0;
+  // (a wanted d->ln1_g, ln1_b or b1 implies stage1, so stage 1 of the partials was written)
+  return col_finish(ws.colpart, nblk, F, {d->ln2_g, d->ln2_b, d->b2, d->wlin, d->blin}, {d->ln1_g, d->ln1_b, d->b1}, &t_launches, st);
 }
 
 extern "C" int ns_pg_op_wgrad(const float* dz, const float* X, int B, int S, int N, int Cin, int KW, float* dW, float* db, void* ws_mem,
@@ -226,11 +198,8 @@ extern "C" int ns_pg_op_wgrad(const float* dz, const float* X, int B, int S, int
   t_launches += 2;
   if (db) {
     NS_HIP(launch_pg_colsum(dz, M, N, colpart, st));
-    PgColFinal fin;
-    memset(&fin, 0, sizeof(fin));
-    fin.out[0] = db;
-    NS_HIP(launch_pg_col_final(colpart, pg_row_blocks(M), N, fin, st));
-    t_launches += 2;
+    ++t_launches;
+    NS_TRY(col_finish(colpart, pg_row_blocks(M), N, {db}, {}, &t_launches, st));
   }
   return 0;
 }
@@ -260,23 +229,15 @@ extern "C" int ns_pg_op_row_backward(int tail, const float* dy, const float* g, 
   if (!v || !ln_g || !dz || !d_ln_g || !d_ln_b || !d_b || !ws_mem) return api_fail(w + "null argument");
   if (tail ? (!g || !ln_b || !wlin || !d_wlin || !d_blin) : !dy) return api_fail(w + "null argument");
   NS_TRY(check_dims(M, 1, F, 4, 1, 4, w));
-  NS_TRY(check_drop(keep, keep, p_drop, w));
+  NS_TRY(check_drop({keep, keep}, p_drop, w));  // (the texts of the two-mask entry points)
   const void* al[] = {dy, v, ln_g, ln_b, wlin, dz, d_ln_g, d_ln_b, d_b, d_wlin, ws_mem};
   for (const void* p : al)
     if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
   const size_t need = (size_t)pg_row_blocks(M) * PG_SLOTS * F * sizeof(double);
   if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
-  PgRowBackward r;
-  memset(&r, 0, sizeof(r));
-  r.tail = tail != 0; r.M = M; r.F = F; r.scale = 1.f / (1.f - p_drop); r.dy = dy; r.g = g; r.mask = tail ? mask : nullptr; r.v = v;
-  r.ln_g = ln_g; r.ln_b = ln_b; r.wlin = wlin; r.keep = keep; r.dz = dz; r.part = (double*)ws_mem;
   hipStream_t st = (hipStream_t)stream;
-  NS_HIP(launch_pg_row_backward(r, st));
-  PgColFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.out[0] = d_ln_g; fin.out[1] = d_ln_b; fin.out[2] = d_b;
-  if (tail) { fin.out[3] = d_wlin; fin.out[4] = d_blin; }
-  NS_HIP(launch_pg_col_final(r.part, pg_row_blocks(M), F, fin, st));
-  t_launches += 2;
-  return 0;
+  double* part = (double*)ws_mem;
+  NS_HIP(launch_pg_row_backward(pg_row_backward_args(tail, M, F, p_drop, dy, g, tail ? mask : nullptr, v, ln_g, ln_b, wlin, keep, dz, part), st));
+  ++t_launches;
+  return col_finish(part, pg_row_blocks(M), F, {d_ln_g, d_ln_b, d_b, tail ? d_wlin : nullptr, tail ? d_blin : nullptr}, {}, &t_launches, st);
 }

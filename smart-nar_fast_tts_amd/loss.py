@@ -10,7 +10,6 @@ No optimiser here — the optimiser half of the training step (clip, Adam, the s
 that torch's backward of the model produces from these."""
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from collections import OrderedDict
 
@@ -18,16 +17,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._train import guard
 
 _TRAINING = "training is out of scope for this path (SURVEY.md §2); only eval() is supported"
 _NINE_IN_KEEP = (4, 5, 8, 10, 12, 13, 14, 15, 16)  # mel, postnet, pitch, energy, log_d, attn[0..3] in _marshal's `keep` list
 GRAD_NAMES = ("mel_predictions", "postnet_mel_predictions", "pitch_predictions", "energy_predictions", "log_duration_predictions",
               "attn[0]", "attn[1]", "attn[2]", "attn[3]")  # what FastSpeech2TrainingLoss differentiates (model/loss.py:175-179,185)
 LOSS_NAMES = ("total", "mel", "postnet", "pitch", "energy", "duration", "attn")  # the reference's return order (model/loss.py:242-250)
-
-
-def _guard(dev):
-    return contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
 class FastSpeech2Loss:
@@ -89,7 +85,7 @@ class FastSpeech2Loss:
         if self.training:
             raise NotImplementedError(_TRAINING)
         call = self._marshal(inputs, predictions)
-        with _guard(call.device):
+        with guard(call.device):
             return self._value(call)
 
     def _value(self, call):
@@ -187,7 +183,7 @@ class FastSpeech2Loss:
             t = t.contiguous()
             return t.clone() if t.data_ptr() % 16 else t
 
-        with _guard(dev):
+        with guard(dev):
             sl, ml = lens("src_lens", src_lens), lens("mel_lens", mel_lens)
             # the two slices the reference takes go through the strides
             if not (mel_targets.stride(2) == 1 and mel_targets.stride(1) == n_mel and mel_targets.stride(0) % 4 == 0
@@ -252,7 +248,7 @@ class _LossFunction(torch.autograd.Function):
         nine = ctx.saved_tensors
         owner, call = ctx.owner, ctx.call
         need = ctx.needs_input_grad[2:]
-        with _guard(call.device):
+        with guard(call.device):
             grads = owner._backward(call, ctx.record, g, [torch.empty_like(x, memory_format=torch.contiguous_format) if n else None
                                                           for x, n in zip(nine, need)])
         return (None, None) + tuple(grads)
@@ -292,7 +288,7 @@ class FastSpeech2TrainingLoss(FastSpeech2Loss):
     def forward(self, inputs, predictions):
         call = self._marshal(inputs, predictions)
         if not (torch.is_grad_enabled() and any(t.requires_grad for t in call.nine)):
-            with _guard(call.device):
+            with guard(call.device):
                 return self._value(call)
         out = _LossFunction.apply(self, call, *call.nine)
         return tuple(out[i] for i in range(7))
@@ -301,7 +297,7 @@ class FastSpeech2TrainingLoss(FastSpeech2Loss):
         """ns_lossg_forward on the current stream of the call's device: ``(out [7], record)``.  The record is a fresh tensor per call:
         it carries the forward's counts to the backward and outlives the shared workspace."""
         dev = call.device
-        with _guard(dev):
+        with guard(dev):
             ws = self.workspace(dev, self._lib.ns_loss_ws_bytes(call.B, call.L, call.T))
             out = torch.empty(7, dtype=torch.float32, device=dev)
             record = torch.empty(self._lib.ns_lossg_record_bytes() // 8, dtype=torch.int64, device=dev)

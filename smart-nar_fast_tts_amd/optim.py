@@ -15,7 +15,6 @@ and the step number are kernel arguments), any backward pass, any change to ``ch
 stream at a time (it owns one workspace and one norm record)."""
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from collections import OrderedDict
 
@@ -23,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._train import guard
 
 CHUNK = 4096  # NS_OPT_CHUNK of include/nar_fs2.h (tests/test_optim_host.py holds the two together)
 
@@ -48,10 +48,6 @@ def _check_params(params):
     return dev
 
 
-def _guard(dev):
-    return contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
-
-
 class _Table:
     """The device chunk table of one parameter list with its workspace and norm record.  ``refresh`` rebuilds and uploads the table
     only when the tuple of gradient pointers (0 = skipped) or the lags changed: a steady-state step uploads nothing."""
@@ -66,7 +62,7 @@ class _Table:
         self.plan = _lib.NsOptPlan()
         _lib.check(self.lib.ns_opt_plan_sizes(self.numels, n, C.byref(self.plan)), "ns_opt_plan_sizes")
         self.param_ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in self.params])
-        with _guard(self.device):
+        with guard(self.device):
             self.table = torch.empty(int(self.plan.table_bytes), dtype=torch.uint8, device=self.device)
             self.ws = torch.empty(int(self.plan.ws_bytes), dtype=torch.uint8, device=self.device)
             self.record = torch.zeros(4, dtype=torch.float32, device=self.device)  # ns_opt_record: float64 norm, total_norm, clip_coef
@@ -93,7 +89,7 @@ class _Table:
             gp = (C.c_void_p * self.n)(*grads)
             lg = (C.c_int32 * self.n)(*lags) if lags is not None else None
             _lib.check(self.lib.ns_opt_build_table(self.numels, self.param_ptrs, gp, lg, self.n, C.c_void_p(host.ctypes.data), host.nbytes), "ns_opt_build_table")
-            with _guard(self.device):
+            with guard(self.device):
                 self.table.copy_(torch.from_numpy(host).view(torch.uint8))  # stream-ordered; returns once the host rows are consumed
             self._key = key
             self.uploads += 1
@@ -103,17 +99,17 @@ class _Table:
         return _lib.stream_ptr(self.device)
 
     def grad_norm(self, max_norm: float):
-        with _guard(self.device):
+        with guard(self.device):
             _lib.check(self.lib.ns_opt_grad_norm(C.byref(self.plan), _lib.ptr(self.table), self.table.numel(), float(max_norm), _lib.ptr(self.ws),
                                                  self.ws.numel(), _lib.ptr(self.record), self.st()), "ns_opt_grad_norm")
 
     def scale(self):
-        with _guard(self.device):
+        with guard(self.device):
             _lib.check(self.lib.ns_opt_scale_grads(C.byref(self.plan), _lib.ptr(self.table), self.table.numel(), _lib.ptr(self.record), self.st()),
                        "ns_opt_scale_grads")
 
     def zero(self):
-        with _guard(self.device):
+        with guard(self.device):
             _lib.check(self.lib.ns_opt_zero_grads(C.byref(self.plan), _lib.ptr(self.table), self.table.numel(), self.st()), "ns_opt_zero_grads")
 
 
@@ -174,7 +170,7 @@ class Adam:
         self._t = _Table(params)
         self.param_groups = [self._group(lr, betas, eps, weight_decay, params)]
         dev = self._t.device
-        with _guard(dev):
+        with guard(dev):
             self._exp_avg = torch.zeros(int(self._t.plan.state_floats), dtype=torch.float32, device=dev)
             self._exp_avg_sq = torch.zeros(int(self._t.plan.state_floats), dtype=torch.float32, device=dev)
         self._offsets = []
@@ -244,7 +240,7 @@ class Adam:
             if float(grad_clip_thresh) < 0:
                 raise ValueError(f"grad_clip_thresh must be >= 0, got {grad_clip_thresh}")
             t.grad_norm(grad_clip_thresh)
-        with _guard(t.device):
+        with guard(t.device):
             _lib.check(t.lib.ns_opt_adam_step(C.byref(t.plan), _lib.ptr(t.table), t.table.numel(), C.byref(h), _lib.ptr(self._exp_avg),
                                               _lib.ptr(self._exp_avg_sq), self._exp_avg.numel(), _lib.ptr(t.record), t.st()), "ns_opt_adam_step")
         return t.total_norm if grad_clip_thresh is not None else None
@@ -294,7 +290,7 @@ class Adam:
             if "max_exp_avg_sq" in s:
                 raise ValueError("amsgrad state is out of scope")
             staged[i] = (int(float(s["step"])), s["exp_avg"], s["exp_avg_sq"])
-        with _guard(self._t.device):
+        with guard(self._t.device):
             self._exp_avg.zero_()
             self._exp_avg_sq.zero_()
             self._steps = [0] * n

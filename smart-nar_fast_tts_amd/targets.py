@@ -4,7 +4,6 @@ and its ``build_from_path`` / ``remove_outlier`` / ``normalize`` (preprocessor/p
 file I/O stay outside."""
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import json
 import os
@@ -13,6 +12,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
+from ._train import guard
 
 SORT_CAPACITY = 8192  # NS_VT_SORT_CAPACITY of include/nar_fs2.h (tests/test_variance_targets_host.py holds the two together)
 
@@ -101,10 +101,6 @@ class VarianceTargets:
                 raise RuntimeError(f"{name} is on {t.device}, {next(iter(named))} on {dev}")
         return dev
 
-    @staticmethod
-    def _guard(dev):
-        return contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
-
     # ---- pass 1 --------------------------------------------------------------------------------
     def process(self, pitch, energy, durations, src_lens, fit: bool = True):
         """``pitch``, ``energy`` [B, T] fp32 (f0 0 = unvoiced), ``durations`` [B, L] int64 (a column slice of a wider tensor is read
@@ -125,7 +121,7 @@ class VarianceTargets:
                 if n > SORT_CAPACITY:
                     raise ValueError(f"{what}: {n} values per utterance exceed the sort capacity of the fit ({SORT_CAPACITY})")
         dev = self._on_gpu(dict(pitch=pitch, energy=energy, durations=durations, src_lens=src_lens))
-        with self._guard(dev):
+        with guard(dev):
             pitch, energy, src_lens = pitch.contiguous(), energy.contiguous(), src_lens.contiguous()
             if not (durations.stride(1) == 1 and durations.stride(0) >= L) and durations.numel() > 0:
                 durations = durations.contiguous()
@@ -174,7 +170,7 @@ class VarianceTargets:
         for name, t in (("pitch_targets", pitch_targets), ("energy_targets", energy_targets)):
             if not t.is_contiguous():
                 raise ValueError(f"{name} must be contiguous (it is normalised in place)")
-        with self._guard(dev):
+        with guard(dev):
             a = self._args(B, L, T)
             src_lens, frame_lens = src_lens.contiguous(), frame_lens.contiguous()
             a.src_lens, a.frame_lens = src_lens.data_ptr(), frame_lens.data_ptr()

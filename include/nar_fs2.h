@@ -271,10 +271,23 @@ int ns_op_ffn_conv1(ns_model* m, const char* prefix, const float* x, int B, int 
  * (single-utterance latency); 8 * (B*S*H*dk + 2*B*S*H) floats always suffice. */
 int ns_op_attention_core(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
                          size_t scratch_bytes, void* stream);
-/* The same with the precision mode chosen by the caller: bf16 = 0 is ns_op_attention_core, bf16 = 1 the "bf16" mode's attention
- * (Q K^T and P V from operands rounded to bf16, fp32 softmax: the kernels a bf16 model's decoder layers run). */
+/* The same with flags chosen by the caller.  Bit 0: 0 is ns_op_attention_core, 1 the "bf16" mode's attention (Q K^T and P V from
+ * operands rounded to bf16, fp32 softmax: the kernels a bf16 model's decoder layers run) — a caller that passed bf16 = 0 / 1 here
+ * keeps its meaning.  Bit 1: withhold the ticket block the op carves from the end of `scratch` (split strips then merge their key
+ * ranges by a k_attention_merge launch instead of by the last arriver).  Any other bit is refused. */
 int ns_op_attention_core_mode(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
-                              size_t scratch_bytes, void* stream, int bf16);
+                              size_t scratch_bytes, void* stream, int flags);
+/* host only: what ns_op_attention_core[_mode] makes of a scratch of scratch_bytes under `flags` (the op carves by this very
+ * function): the floats left to the split-key partials, and whether a ticket block was taken from the end */
+int ns_op_attention_carve(int B, int S, int H, size_t scratch_bytes, int flags, size_t* partial_floats, int32_t* has_tickets);
+/* host only: what the dense (grid) attention launch of this shape does, answered by the function the launch dispatches on
+ * (csrc/attention.hip attention_plan_dense).  out = {kernel: 0 k_attention_strip / 1 k_attention, key-range workgroups per 32-query
+ * strip / per 128-query tile, merge: 0 none / 1 by the last arriver of a strip's workgroups (tickets) / 2 by a k_attention_merge
+ * launch, 32-key tiles per wave of a strip / per key range of k_attention for an utterance of S keys}.  scratch_floats: floats of
+ * scratch left to the partials (0 = none); has_tickets: a ticket block is handed over.  Follows NS_PLAN.  Bad shapes (B, S, H <= 0,
+ * dk not 32 / 64 / 128, S * 3 * H * dk * 4 >= 2^31) and a null out are refused before anything else.  An addition: NS_ABI_VERSION
+ * is unchanged. */
+int ns_plan_attention_dense(int B, int S, int H, int dk, size_t scratch_floats, int has_tickets, int32_t out[4]);
 /* One named contraction alone, for tests: x [B*S, Cin] -> out [B*S, N] on the dense grid (zero padding per utterance of S rows),
  * in the model's precision mode and through the forward's own dispatch, with bias and the layer's activation (ReLU for w_1, tanh
  * for every PostNet layer but the last) and neither residual nor LayerNorm.  name: "<layer prefix>.slf_attn.qkv" (N = 3 d: Q | K |

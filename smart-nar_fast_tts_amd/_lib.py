@@ -170,6 +170,8 @@ SIGNATURES = {
     "ns_op_ffn_conv1": (_I, [_P, _S, _P, _I, _I, _P, _P]),
     "ns_op_attention_core": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "ns_op_attention_core_mode": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _Z, _P, _I]),
+    "ns_op_attention_carve": (_I, [_I, _I, _I, _Z, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "ns_plan_attention_dense": (_I, [_I, _I, _I, _I, _Z, _I, C.POINTER(C.c_int32)]),
     "ns_op_gemm": (_I, [_P, _S, _P, _I, _I, _P, _P]),
     "ns_plan_gemm_bf16": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ns_plan_gemm_bf16_ln": (_I, [_I, _I, _I, _I]),

@@ -1287,20 +1287,36 @@ extern "C" int ns_op_postnet(ns_model* m, const float* mel, int B, int T, float*
   NS_OP_PROLOGUE(B, T);
   return postnet(m, mel, B, T, nullptr, out, sc, st);
 }
+// What ns_op_attention_core[_mode] and ns_op_attention_core_packed make of a scratch of scratch_bytes (host only; the ops themselves
+// carve by this function): the floats left to the split-key partials and whether a ticket block was taken from the end.
+static int attention_carve(const char* who, int B, int S, int H, size_t scratch_bytes, int flags, size_t* partial_floats, int32_t* has_tickets) {
+  if (B <= 0 || S <= 0 || H <= 0 || !partial_floats || !has_tickets) return fail(std::string(who) + ": bad argument");
+  size_t floats = scratch_bytes / sizeof(float);
+  const size_t tk = ((size_t)attention_ticket_ints(B, S, H) + 63) & ~(size_t)63;
+  *has_tickets = 0;
+  if (!(flags & 2) && floats > tk) { floats -= tk; *has_tickets = 1; }
+  *partial_floats = floats;
+  return 0;
+}
+extern "C" int ns_op_attention_carve(int B, int S, int H, size_t scratch_bytes, int flags, size_t* partial_floats, int32_t* has_tickets) {
+  return attention_carve("ns_op_attention_carve", B, S, H, scratch_bytes, flags, partial_floats, has_tickets);
+}
+// flags: bit 0 = the bf16 mode's kernels, bit 1 = withhold the ticket block (split strips then merge by a launch of their own)
 extern "C" int ns_op_attention_core_mode(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
-                                         size_t scratch_bytes, void* stream, int bf16) {
+                                         size_t scratch_bytes, void* stream, int flags) {
+  if (flags & ~3) return fail("ns_op_attention_core_mode: unknown flag");
   // the strip kernel's tickets are carved from the END of the caller's scratch and zeroed here (a forward's opening kernel
   // does that for its own launches)
   float* sp = (float*)scratch;
   size_t floats = scratch_bytes / sizeof(float);
+  int32_t has_tk = 0;
   int* tickets = nullptr;
-  const size_t tk = ((size_t)attention_ticket_ints(B, S, H) + 63) & ~(size_t)63;
-  if (sp && B > 0 && S > 0 && floats > tk) {
-    floats -= tk;
+  if (sp && B > 0 && S > 0 && H > 0) NS_TRY(ns_op_attention_carve(B, S, H, scratch_bytes, flags, &floats, &has_tk));
+  if (has_tk) {
     tickets = (int*)(sp + floats);
-    NS_HIP(hipMemsetAsync(tickets, 0, tk * sizeof(int), (hipStream_t)stream));
+    NS_HIP(hipMemsetAsync(tickets, 0, (scratch_bytes / sizeof(float) - floats) * sizeof(int), (hipStream_t)stream));
   }
-  NS_HIP(launch_attention(qkv, (const long long*)lens, B, S, H, dk, out, sp, floats, tickets, (hipStream_t)stream, nullptr, nullptr, bf16 != 0));
+  NS_HIP(launch_attention(qkv, (const long long*)lens, B, S, H, dk, out, sp, floats, tickets, (hipStream_t)stream, nullptr, nullptr, (flags & 1) != 0));
   return 0;
 }
 extern "C" int ns_op_attention_core(const float* qkv, const int64_t* lens, int B, int S, int H, int dk, float* out, void* scratch,
@@ -1388,13 +1404,7 @@ extern "C" int ns_op_gemm_packed(ns_model* m, const char* name, const float* x_p
 // What ns_op_attention_core_packed makes of a scratch of scratch_bytes (host only; the op itself carves by this function): the floats
 // left to the split-key partials and whether a ticket block was taken from the end.
 extern "C" int ns_op_attention_packed_carve(int B, int S, int H, size_t scratch_bytes, int flags, size_t* partial_floats, int32_t* has_tickets) {
-  if (B <= 0 || S <= 0 || H <= 0 || !partial_floats || !has_tickets) return fail("ns_op_attention_packed_carve: bad argument");
-  size_t floats = scratch_bytes / sizeof(float);
-  const size_t tk = ((size_t)attention_ticket_ints(B, S, H) + 63) & ~(size_t)63;
-  *has_tickets = 0;
-  if (!(flags & 2) && floats > tk) { floats -= tk; *has_tickets = 1; }
-  *partial_floats = floats;
-  return 0;
+  return attention_carve("ns_op_attention_packed_carve", B, S, H, scratch_bytes, flags, partial_floats, has_tickets);
 }
 // flags: bit 0 = the bf16 mode's kernels, bit 1 = withhold the ticket block (the strips then merge by a launch of their own)
 extern "C" int ns_op_attention_core_packed(const float* qkv_p, const int64_t* lens, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs,
@@ -1425,6 +1435,18 @@ extern "C" int ns_plan_attention_packed(int B, int S, int H, int dk, int att_wgs
   if (B <= 0 || S <= 0 || H <= 0 || att_wgs <= 0 || Mp <= 0 || (dk != 128 && dk != 64 && dk != 32)) return fail("ns_plan_attention_packed: bad shape");
   const AttentionPackedPlan pl = attention_plan_packed(B, S, H, dk, att_wgs, (size_t)Mp, scratch_floats, has_tickets != 0);
   out[0] = pl.form; out[1] = pl.nsplit; out[2] = pl.merge; out[3] = pl.tiles;
+  return 0;
+}
+
+// the dense launch_attention's own decision (attention.hip attention_plan_dense); host only.
+// out = {kernel: 0 k_attention_strip / 1 k_attention, key ranges, merge: 0 none / 1 last arriver / 2 k_attention_merge launch,
+//        32-key tiles per wave (strips) or per range (k_attention) of an utterance of S keys}
+extern "C" int ns_plan_attention_dense(int B, int S, int H, int dk, size_t scratch_floats, int has_tickets, int32_t out[4]) {
+  if (!out) return fail("ns_plan_attention_dense: null out");
+  if (B <= 0 || S <= 0 || H <= 0 || (dk != 128 && dk != 64 && dk != 32)) return fail("ns_plan_attention_dense: bad shape");
+  if ((long long)S * 3 * H * dk * 4 >= (1ll << 31)) return fail("ns_plan_attention_dense: an utterance's qkv rows exceed 2^31 bytes");
+  const AttentionDensePlan pl = attention_plan_dense(B, S, H, dk, scratch_floats, has_tickets != 0);
+  out[0] = pl.kernel; out[1] = pl.nsplit; out[2] = pl.merge; out[3] = pl.tiles;
   return 0;
 }
 

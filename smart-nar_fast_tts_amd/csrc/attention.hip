@@ -854,6 +854,45 @@ AttentionPackedPlan attention_plan_packed(int B, int S, int H, int dk, int att_w
   return pl;
 }
 
+// The dense launch's decision (kernels.h AttentionDensePlan): launch_attention below dispatches on the answer.
+AttentionDensePlan attention_plan_dense(int B, int S, int H, int dk, size_t scratch_floats, bool has_tickets) {
+  const int d = H * dk;
+  const int qtiles = (S + 127) / 128, tiles = (S + 31) / 32;
+  const long blocks = (long)qtiles * H * B;
+  const size_t M = (size_t)B * S;
+  auto part_floats = [&](int n) { return (size_t)n * (M * d + 2 * M * H); };
+  AttentionDensePlan pl = {1, 1, 0, tiles};
+  // Few workgroups (single-utterance latency, the encoder): first choice the strip kernel (launch_strips below)
+  if (blocks < ATT_SPLIT_MAX_BLOCKS) {
+    int nsplit, tpr;
+    if (strip_plan(B, S, H, dk, M, scratch_floats, &nsplit, &tpr)) {
+      pl.kernel = 0; pl.nsplit = nsplit; pl.merge = nsplit > 1 ? (has_tickets ? 1 : 2) : 0; pl.tiles = tpr;
+      return pl;
+    }
+  }
+  // Otherwise k_attention; still few workgroups (long single utterances): split the key sweep over up to ATT_SPLIT_MAX
+  // workgroups per 128-query tile until the launch has ~256 of them, then merge the partials with k_attention_merge.
+  // Needs nsplit * (M*d + 2*M*H) floats of scratch.
+  int nsplit = 1;
+  if (scratch_floats && blocks < ATT_SPLIT_MAX_BLOCKS) {
+    nsplit = (int)(256 / blocks);
+    if (nsplit > ATT_SPLIT_MAX) nsplit = ATT_SPLIT_MAX;
+    if (nsplit > tiles) nsplit = tiles;  // at least one 32-key tile each
+    while (nsplit > 1 && part_floats(nsplit) > scratch_floats) --nsplit;
+    if (nsplit < 1) nsplit = 1;
+    const int tps = (tiles + nsplit - 1) / nsplit;
+    nsplit = (tiles + tps - 1) / tps;  // no empty ranges: 25 tiles over 16 ranges are 13 ranges of two
+  } else if (scratch_floats && launch_planner_enabled()) {
+    // a launch that fills its last round of 256 workgroups badly (plan_key_split above)
+    nsplit = plan_key_split(blocks, tiles, dk, M, d);
+    while (nsplit > 1 && part_floats(nsplit) > scratch_floats) --nsplit;
+    const int tps = (tiles + nsplit - 1) / nsplit;
+    nsplit = (tiles + tps - 1) / tps;
+  }
+  pl.nsplit = nsplit; pl.merge = nsplit > 1 ? 2 : 0; pl.tiles = (tiles + nsplit - 1) / nsplit;
+  return pl;
+}
+
 // Few workgroups (single-utterance latency, the encoder): a 128-query workgroup's time is its serial sweep over the key tiles.
 // First choice, k_attention_strip: a workgroup per 32-query strip whose four waves split the key axis, and up to nsplit such
 // workgroups per strip merged by the last arriver — taken when that leaves every wave at most 4 key tiles (beyond that the shared
@@ -920,30 +959,14 @@ hipError_t launch_attention(const float* qkv, const long long* lens, int B, int 
   if ((long long)S * 3 * d * 4 >= (1ll << 31)) return hipErrorInvalidValue;  // 31-bit descriptor offsets per utterance
   if (dk != 128 && dk != 64 && dk != 32) return hipErrorInvalidValue;
   const float c = 1.4426950408889634f / sqrtf((float)dk);
-  const int qtiles = (S + 127) / 128, tiles = (S + 31) / 32;
-  const long blocks = (long)qtiles * H * B;
+  const int qtiles = (S + 127) / 128;
   const size_t M = (size_t)B * S;
-  auto part_floats = [&](int n) { return (size_t)n * (M * d + 2 * M * H); };
-  if (blocks < ATT_SPLIT_MAX_BLOCKS && launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, nullptr, ev0, ev1, bf)) return hipGetLastError();
-  // Otherwise k_attention; still few workgroups (long single utterances): split the key sweep over up to ATT_SPLIT_MAX
-  // workgroups per 128-query tile until the launch has ~256 of them, then merge the partials with k_attention_merge.
-  // Needs nsplit * (M*d + 2*M*H) floats of scratch.
-  int nsplit = 1;
-  if (scratch && blocks < ATT_SPLIT_MAX_BLOCKS) {
-    nsplit = (int)(256 / blocks);
-    if (nsplit > ATT_SPLIT_MAX) nsplit = ATT_SPLIT_MAX;
-    if (nsplit > tiles) nsplit = tiles;  // at least one 32-key tile each
-    while (nsplit > 1 && part_floats(nsplit) > scratch_floats) --nsplit;
-    if (nsplit < 1) nsplit = 1;
-    const int tps = (tiles + nsplit - 1) / nsplit;
-    nsplit = (tiles + tps - 1) / tps;  // no empty ranges: 25 tiles over 16 ranges are 13 ranges of two
-  } else if (scratch && launch_planner_enabled()) {
-    // a launch that fills its last round of 256 workgroups badly (plan_key_split above)
-    nsplit = plan_key_split(blocks, tiles, dk, M, d);
-    while (nsplit > 1 && part_floats(nsplit) > scratch_floats) --nsplit;
-    const int tps = (tiles + nsplit - 1) / nsplit;
-    nsplit = (tiles + tps - 1) / tps;
+  const AttentionDensePlan pl = attention_plan_dense(B, S, H, dk, scratch ? scratch_floats : 0, tickets != nullptr);
+  if (pl.kernel == 0) {
+    if (!launch_strips(qkv, lens, B, S, H, dk, out, scratch, scratch_floats, tickets, st, nullptr, ev0, ev1, bf)) return hipErrorInvalidValue;
+    return hipGetLastError();
   }
+  const int nsplit = pl.nsplit;
   float* opart = nsplit > 1 ? scratch : nullptr;
   float* mlpart = nsplit > 1 ? scratch + (size_t)nsplit * M * d : nullptr;
   dim3 grid(qtiles * nsplit, H, B);

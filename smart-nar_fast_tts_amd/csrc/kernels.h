@@ -125,6 +125,11 @@ int attention_split_packed(int att_wgs, int S, int dk, size_t Mp, int d);
 // one wave's share).  scratch_floats = 0: no scratch.
 struct AttentionPackedPlan { int form, nsplit, merge, tiles; };
 AttentionPackedPlan attention_plan_packed(int B, int S, int H, int dk, int att_wgs, size_t Mp, size_t scratch_floats, bool has_tickets);
+// The same for the dense (grid) launch, rm == nullptr: kernel 0 = k_attention_strip, 1 = k_attention; nsplit = key-range workgroups
+// per strip / per 128-query tile; merge 0 = none, 1 = the last arriver of a strip's workgroups (tickets), 2 = a k_attention_merge
+// launch; tiles = 32-key tiles per wave of a strip / per range of k_attention, of an utterance of S keys.  scratch_floats = 0: no scratch.
+struct AttentionDensePlan { int kernel, nsplit, merge, tiles; };
+AttentionDensePlan attention_plan_dense(int B, int S, int H, int dk, size_t scratch_floats, bool has_tickets);
 
 // ---- row kernels (rowops.hip) -----------------------------------------------------------------
 // y = LayerNorm_C(x) * g + b ; rows with t >= lens[b] are written as zero when lens != nullptr

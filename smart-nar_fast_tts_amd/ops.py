@@ -249,26 +249,72 @@ def ffn_conv1(model, prefix, x, out=None):
     return out
 
 
-def attention_core(qkv, lens, n_head: int, split_scratch=True, bf16: bool = False):
+def plan_attention_dense(B, S, H, dk, scratch_floats: int = 0, has_tickets: bool = False):
+    """(kernel 0 k_attention_strip / 1 k_attention, key ranges, merge 0 none / 1 last arriver / 2 k_attention_merge launch, 32-key
+    tiles per wave / per range) of the dense attention launch, from the function the launch dispatches on (host only)."""
+    import ctypes
+
+    o = (ctypes.c_int32 * 4)()
+    _lib.check(_lib.load().ns_plan_attention_dense(int(B), int(S), int(H), int(dk), int(scratch_floats), int(bool(has_tickets)), o),
+               "plan_attention_dense")
+    return tuple(o)
+
+
+def attention_dense_scratch(B, S, H, dk, split_scratch=True, tickets: bool = True):
+    """(floats of scratch ``attention_core`` allocates, floats of it left to the partials, ticket block carved) for the same
+    arguments (host only).  ``True``: 8 ranges' worth of floats in all, the ticket block taken out of them; an int n: room for n key
+    ranges plus the ticket block the op takes from the end (16 = ATT_SPLIT_MAX, every split the dispatch can ask for);
+    ``"workspace"``: what a model's own workspace holds for this shape; ``False``: none."""
+    import ctypes
+
+    lib = _lib.load()
+    flags = 0 if tickets else 2
+
+    def carve(total):  # what the op makes of `total` floats, asked of the op's own function
+        part, has = ctypes.c_size_t(0), ctypes.c_int32(0)
+        _lib.check(lib.ns_op_attention_carve(int(B), int(S), int(H), total * 4, flags, ctypes.byref(part), ctypes.byref(has)), "attention_carve")
+        return part.value, bool(has.value)
+
+    one = B * S * H * dk + 2 * B * S * H
+    if isinstance(split_scratch, str):
+        assert split_scratch == "workspace", split_scratch
+        floats = int(lib.ns_op_attention_scratch_bytes(B, S, H, dk)) // 4
+    elif split_scratch is True:
+        floats = 8 * one
+    elif not split_scratch:
+        floats = 0
+    else:
+        big = int(split_scratch) * one + (1 << 28)
+        floats = int(split_scratch) * one + (big - carve(big)[0])
+    if not floats:
+        return 0, 0, False
+    return (floats,) + carve(floats)
+
+
+def attention_core(qkv, lens, n_head: int, split_scratch=True, bf16: bool = False, tickets: bool = True, out=None):
     """ScaledDotProductAttention on already-projected, head-packed q/k/v (transformer/Modules.py:14-25):
     qkv [B,S,3*d] (Q | K | V, head h at h*dk inside each) -> merged heads [B,S,d].  ``split_scratch`` hands the
-    kernel the scratch it needs to take its split-key path on small grids; ``"workspace"`` hands it what a model's own workspace
+    kernel the scratch it needs to take its split-key path (``True``: 8 ranges' worth, an int n: room for n ranges, 16 being the
+    most the dispatch asks for; see ``attention_dense_scratch``); ``"workspace"`` hands it what a model's own workspace
     holds for this shape (sized by the library, ``ns_op_attention_scratch_bytes``), so the launch splits its keys as the model's
-    attention does.  ``bf16`` runs the "bf16" precision mode's kernels (what a bf16 model's decoder layers run): Q K^T and P V
-    from operands rounded to bf16, the softmax in fp32."""
+    attention does.  ``tickets=False`` withholds the ticket block (split strips then merge by a launch of their own).  ``bf16`` runs
+    the "bf16" precision mode's kernels (what a bf16 model's decoder layers run): Q K^T and P V
+    from operands rounded to bf16, the softmax in fp32.  ``out`` (optional): a contiguous [B,S,d] fp32 tensor to write."""
     lib = _lib.load()
     B, S, d3 = qkv.shape
     d = d3 // 3
     qkv = qkv.contiguous()
-    out = torch.empty(B, S, d, dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = torch.empty(B, S, d, dtype=torch.float32, device=qkv.device)
+    assert out.shape == (B, S, d) and out.dtype == torch.float32 and out.is_contiguous() and out.device == qkv.device
     lens_p = _lib.ptr(lens.long().contiguous()) if lens is not None else _lib.ptr(None)
-    if split_scratch == "workspace":
-        floats = int(lib.ns_op_attention_scratch_bytes(B, S, n_head, d // n_head)) // 4
-    else:
-        floats = 8 * (B * S * d + 2 * B * S * n_head) if split_scratch else 0
+    floats = attention_dense_scratch(B, S, n_head, d // n_head, split_scratch, tickets)[0]
     scratch = torch.empty(floats, dtype=torch.float32, device=qkv.device) if floats else None
     args = (_lib.ptr(qkv), lens_p, B, S, n_head, d // n_head, _lib.ptr(out), _lib.ptr(scratch), floats * 4, _st(qkv))
-    _lib.check(lib.ns_op_attention_core_mode(*args, 1) if bf16 else lib.ns_op_attention_core(*args), "attention_core")
+    if bf16 or not tickets:
+        _lib.check(lib.ns_op_attention_core_mode(*args, (1 if bf16 else 0) | (0 if tickets else 2)), "attention_core")
+    else:
+        _lib.check(lib.ns_op_attention_core(*args), "attention_core")
     return out
 
 

@@ -1,7 +1,9 @@
 """Each kernel of the opt-in "bf16" mel path ALONE on the MI355X against the float64 emulation of tests/bf16_emu.py (the gates
 are proven on the CPU in tests/test_bf16_ops_host.py): k_conv_gemm_bf16 through ops.gemm at every layer shape of the ljspeech and
 d512 configs, elementwise; its rounding on exact ties; its LayerNorm tile; the BF = true attention kernels through
-ops.attention_core(bf16=True) on the parameter lists of tests/test_gpu_attention.py.  Every elementwise bound is applied to ONE
+ops.attention_core(bf16=True) on the parameter lists of tests/test_gpu_attention.py (strip kernel, forms A and B, plus k_attention
+in one sweep where a split test withholds the scratch — each asserted below through the dispatch's own plan; the other dense
+forms run in bf16 in tests/test_gpu_attention_ops.py).  Every elementwise bound is applied to ONE
 contraction whose inputs the test supplies, so no rounding flip of an earlier layer can enter; the attention gate budgets the
 flips of its own P explicitly.
 
@@ -368,6 +370,9 @@ def _check_attention(qkv, lens, H, label, **kw):
 @pytest.mark.parametrize("H,dk", [(2, 128), (8, 64), (4, 32)])
 @pytest.mark.parametrize("S,lens", [(1, [1]), (33, [33, 1, 32]), (128, [128, 97, 64, 5]), (300, [300, 257, 129])])
 def test_attention_bf16_vs_float64(H, dk, S, lens):
+    from tests.test_gpu_attention import launch_form
+
+    assert launch_form(H, dk, S, len(lens)) == (("A", 1) if S <= 128 else ("B", 2 if H == 8 else 3))
     torch.manual_seed(S * 7 + dk)
     _check_attention(torch.randn(len(lens), S, 3 * H * dk), lens, H, "ragged")
 
@@ -375,14 +380,22 @@ def test_attention_bf16_vs_float64(H, dk, S, lens):
 @pytest.mark.parametrize("H,dk,S,lens", [(2, 128, 100, [100]), (2, 128, 128, [128, 97, 64, 5] * 4), (2, 128, 788, [788]), (2, 128, 1010, [1010, 700, 33]),
                                          (8, 64, 300, [300, 257, 129]), (4, 32, 130, [130, 1])])
 def test_attention_bf16_launch_forms(H, dk, S, lens):
-    """the strip kernel without a merge (S <= 128), with the ticketed merge (one utterance, T = 788), and k_attention (T = 1010)"""
+    """the strip kernel without a merge (S <= 128, form A) and with the ticketed last-arriver merge (form B: one utterance of
+    T = 788 in 4 key-range workgroups per strip, three of T = 1010 in 2 — strips too, not k_attention)"""
+    from tests.test_gpu_attention import A5_FORMS, launch_form
+
+    assert launch_form(H, dk, S, len(lens)) == A5_FORMS[(H, dk, S)]
     torch.manual_seed(S + dk)
     _check_attention(torch.randn(len(lens), S, 3 * H * dk), lens, H, "launch form")
 
 
 @pytest.mark.parametrize("H,dk,S,lens", [(2, 128, 1000, [1000]), (2, 128, 700, [700, 130]), (8, 64, 513, [384]), (4, 32, 260, [260, 31, 0])])
 def test_attention_bf16_split_key_path(H, dk, S, lens):
-    """partials + merge, and the single sweep on the same input: both inside the gate (every launch form rounds the same P)"""
+    """partials + the last arriver's merge on strips (form B), and the single sweep on the same input (k_attention, form D; unsplit
+    strips at S = 260): both inside the gate (every launch form rounds the same P)"""
+    from tests.test_gpu_attention import SPLIT_FORMS, launch_form
+
+    assert (launch_form(H, dk, S, len(lens), True), launch_form(H, dk, S, len(lens), False)) == SPLIT_FORMS[S]
     torch.manual_seed(S + dk)
     qkv = torch.randn(len(lens), S, 3 * H * dk)
     qkv[0, S // 2 + 7, H * dk:2 * H * dk] *= 4.0  # a dominant key in a late split

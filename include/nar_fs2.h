@@ -1026,6 +1026,78 @@ int ns_ag_op_attention_backward(const float* qkv, const float* ctx, const float*
 int ns_ag_op_row_backward(const float* dy, const float* z, const float* ln_g, const uint8_t* keep, float p_drop, int M, int d, float* dz,
                           float* du, float* d_ln_g, float* d_ln_b, float* d_bfc, void* ws, size_t ws_bytes, void* stream);
 
+/* ==== MultiHeadAttention as cross-attention: a training forward and its backward (FFTBlock2.crs_attn, transformer/Layers.py:61-64) ====
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  With q = tgt [B, T, d], k = v = src [B, L, d], H heads,
+ * dk = d / H, c = 1 / sqrt(dk):
+ *   Q  = tgt Wq^T + bq                      [B*T, d]
+ *   KV = src [Wk; Wv]^T + [bk; bv]          [B*L, 2d] = K | V, head h at h * dk inside each half (what ns_aln_op_cross_attention reads)
+ *   A  = softmax_l(c Q K^T), keys l >= src_lens[b] masked     [B, H, T, L], WRITTEN: final probabilities, exact 0 at masked keys
+ *   ctx = merge_heads(A V);  z = dropout(ctx Wfc^T + bfc) + tgt;  y = LayerNorm(z)
+ * Padded QUERY rows are computed like any other and y is not masked (FFTBlock2 does that outside).  The map A is an output of the
+ * forward and an input of the backward, with an upstream gradient dA of its own (the guided-attention loss, ns_lossg_backward's
+ * d_attn).  Exact fp32 on the fp32 matrix cores; column sums, row statistics and D in float64, rounded once.  No atomic, no host read;
+ * equal inputs give equal bits.  src_lens: int64 [B] on the device, required.  An utterance with src_lens[b] == 0 has NaN in A and ctx
+ * (as the reference has). */
+#define NS_XG_ABI_VERSION 1
+int ns_xg_abi_version(void);
+typedef struct ns_xg_shape { int32_t B, T, L, d, H; } ns_xg_shape;
+/* Device pointers, 16-byte aligned, fp32, checkpoint layout: the ten of ns_ag_weights. */
+typedef struct ns_xg_weights {
+  const float* wq;    /* [d, d] w_qs.weight */
+  const float* bq;    /* [d] */
+  const float* wk;    /* [d, d] w_ks.weight */
+  const float* bk;    /* [d] */
+  const float* wv;    /* [d, d] w_vs.weight */
+  const float* bv;    /* [d] */
+  const float* wfc;   /* [d, d] fc.weight */
+  const float* bfc;   /* [d] */
+  const float* ln_g;  /* [d] layer_norm.weight */
+  const float* ln_b;  /* [d] */
+} ns_xg_weights;
+/* The outputs of ns_xg_backward: the same ten, shaped alike, dtgt [B, T, d] and dsrc [B, L, d].  16-byte aligned.  NULL = not wanted:
+ * neither computed nor written, and a launch none of whose outputs is wanted is not made. */
+typedef struct ns_xg_grads {
+  float *wq, *bq, *wk, *bk, *wv, *bv, *wfc, *bfc, *ln_g, *ln_b, *dtgt, *dsrc;
+} ns_xg_grads;
+/* Bytes of the workspace of ns_xg_forward / ns_xg_backward of this shape (0 and ns_last_error() for a refused shape), and of `saved`:
+ * q [B*T, d] | kv [B*L, 2d] | ctx [B*T, d] | z [B*T, d] floats, in this order, dense. */
+size_t ns_xg_ws_bytes(const ns_xg_shape* shape);
+size_t ns_xg_saved_bytes(const ns_xg_shape* shape);
+/* The number of query parts the key-owning backward kernel of this shape is split into, nsplit: a function of (B, H, T, L) alone, in
+ * [1, 8] (0 and ns_last_error() for a refused shape).  With W = ceil(L / 128) * H * B workgroups and Q = ceil(T / 32) query tiles:
+ * nsplit = 1, doubled while nsplit < 8, W * nsplit < 256 and Q / (2 nsplit) >= 4 (integer division).  So nsplit = 1 when T <= 224. */
+int ns_xg_kv_splits(const ns_xg_shape* shape);
+/* Kernel launches the calling thread's last ns_xg_* call enqueued. */
+int ns_xg_last_launches(void);
+/* Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a pointer that is not 16-byte
+ * aligned (src_lens: 8), d not 256 or 512, d % H != 0, dk not in {64, 128}, B * H * T * L >= 2^31, B * max(T, L) * 2d >= 2^31, p_drop
+ * outside [0, 1), a keep-mask without p_drop > 0 or p_drop > 0 without one, a workspace smaller than ns_xg_ws_bytes.
+ * y [B, T, d], attn [B, H, T, L] (both written).  saved: ns_xg_saved_bytes, or NULL (nothing kept: the no_grad forward; attn is written
+ * all the same).
+ * Launches: 1 (pack) + G(B*T, d, d) (q) + G(B*L, 2d, d) (kv) + 1 (attention) + G(B*T, d, d) (fc) + 1 (row), where G(M, N, K) is the
+ * Conv1D-as-GEMM dispatch's own launch count for that shape (ns_plan_gemm_launches, 1 or 2). */
+int ns_xg_forward(const ns_xg_shape* shape, const ns_xg_weights* weights, const float* tgt, const float* src, const int64_t* src_lens,
+                  const uint8_t* keep, float p_drop, float* y, float* attn, void* saved, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of sum g . y + sum dA . A (g [B, T, d], read on every row; dA [B, H, T, L] or NULL = zero, never read at keys l >=
+ * src_lens[b]) with respect to every non-NULL member of grads, from `saved` and `attn` as ns_xg_forward wrote them for the same arguments.
+ * Launches with every output wanted: 1 (pack) + 1 (row backward) + 2 (dWfc: GEMM, reduce) + G(B*T, d, d) (dctx) + 2 (attention
+ * backward: the query-owning and the key-owning kernel) + 1 if nsplit > 1 (the sum of the parts) + 3 * 2 (dWq, dWk, dWv) + 2 (column
+ * sums of dq and of dk | dv) + G(B*T, d, d) (dtgt, the residual branch dz added in its epilogue) + G(B*L, d, 2d) (dsrc) + 2 (final
+ * column sums: over B*L row blocks, over B*T row blocks) = 16 + (nsplit > 1) + 2 G(B*T, d, d) + G(B*L, d, 2d).  An unwanted weight
+ * gradient drops its 2 launches, dtgt / dsrc its GEMM, bq / (bk and bv) their column sums, (bk and bv) their final sum; with nothing
+ * wanted that reads dK | dV (wk, bk, wv, bv, dsrc) the key-owning kernel and the sum of its parts are dropped; with nothing wanted
+ * upstream of ctx (only wfc, bfc, ln_g, ln_b) the pack, dctx and the attention backward are dropped too. */
+int ns_xg_backward(const ns_xg_shape* shape, const ns_xg_weights* weights, const float* tgt, const float* src, const int64_t* src_lens,
+                   const uint8_t* keep, float p_drop, const void* saved, const float* attn, const float* g, const float* dA,
+                   const ns_xg_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* The new kernels alone.  dq [B*T, d] and dkv [B*L, 2d] = (dK | dV) from q, kv, ctx [B*T, d], attn, dctx [B*T, d] and dA (nullable); dK
+ * and dV rows at keys >= src_lens[b] are +0.0, and nothing those rows of kv or those columns of dA hold is read into a sum.  kv_splits
+ * in [0, 8]: the number of query parts, 0 = ns_xg_kv_splits.  ws: B * H * T floats (D), rounded up to 256 bytes, plus, for more than
+ * one part, parts * B * L * 2d floats.  Two launches, three with more than one part. */
+int ns_xg_op_attention_backward(const float* q, const float* kv, const float* ctx, const float* attn, const float* dctx, const float* dA,
+                                const int64_t* src_lens, int B, int T, int L, int d, int H, int kv_splits, float* dq, float* dkv, void* ws,
+                                size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

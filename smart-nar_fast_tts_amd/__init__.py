@@ -4,8 +4,8 @@
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
 when it is missing.  ``FastSpeech2Loss``, ``FastSpeech2TrainingLoss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
-``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``), the trainable ``VariancePredictor`` (``predictor``) and ``MultiHeadAttention`` (``sublayers``) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim", "VariancePredictor", "MultiHeadAttention"]
+``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``), the trainable ``VariancePredictor`` (``predictor``) and ``MultiHeadAttention`` / ``MultiHeadCrossAttention`` (``sublayers``) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim", "VariancePredictor", "MultiHeadAttention", "MultiHeadCrossAttention"]
 
 
 def __getattr__(name):
@@ -29,8 +29,8 @@ def __getattr__(name):
         from . import predictor
 
         return predictor.VariancePredictor
-    if name == "MultiHeadAttention":
+    if name in ("MultiHeadAttention", "MultiHeadCrossAttention"):
         from . import sublayers
 
-        return sublayers.MultiHeadAttention
+        return getattr(sublayers, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

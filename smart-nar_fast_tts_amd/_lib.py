@@ -106,6 +106,21 @@ class NsAgGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in AG_NAMES + ("dx",)]
 
 
+class NsXgShape(C.Structure):
+    """``ns_xg_shape`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "L", "d", "H")]
+
+
+class NsXgWeights(C.Structure):
+    """``ns_xg_weights`` (include/nar_fs2.h): the ten parameters in checkpoint layout, named as ``ns_ag_weights``."""
+    _fields_ = [(n, C.c_void_p) for n in AG_NAMES]
+
+
+class NsXgGrads(C.Structure):
+    """``ns_xg_grads`` (include/nar_fs2.h): the ten parameter gradients, ``dtgt`` and ``dsrc``, each nullable."""
+    _fields_ = [(n, C.c_void_p) for n in AG_NAMES + ("dtgt", "dsrc")]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -303,6 +318,15 @@ SIGNATURES = {
     "ns_ag_op_lse": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "ns_ag_op_attention_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "ns_ag_op_row_backward": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    # MultiHeadAttention as cross-attention, training forward and backward (sublayers.MultiHeadCrossAttention; handle-less)
+    "ns_xg_abi_version": (_I, []),
+    "ns_xg_ws_bytes": (_Z, [C.POINTER(NsXgShape)]),
+    "ns_xg_saved_bytes": (_Z, [C.POINTER(NsXgShape)]),
+    "ns_xg_kv_splits": (_I, [C.POINTER(NsXgShape)]),
+    "ns_xg_last_launches": (_I, []),
+    "ns_xg_forward": (_I, [C.POINTER(NsXgShape), C.POINTER(NsXgWeights), _P, _P, _P, _P, _F, _P, _P, _P, _P, _Z, _P]),
+    "ns_xg_backward": (_I, [C.POINTER(NsXgShape), C.POINTER(NsXgWeights), _P, _P, _P, _P, _F, _P, _P, _P, _P, C.POINTER(NsXgGrads), _P, _Z, _P]),
+    "ns_xg_op_attention_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -1,7 +1,8 @@
 """What the trainable HIP layers share on the Python side (predictor.VariancePredictor over ``ns_pg_*``, sublayers.MultiHeadAttention
 over ``ns_ag_*``): the device guard, the workspace cache, the one ``torch.autograd.Function`` and the module base class that marshals
 the input, the ten parameters, the keep-masks and the gradient block.  A layer keeps its constructor checks, its ``PARAM_NAMES``, its
-shape struct, its mask handling and its two ctypes calls."""
+shape struct, its mask handling and its two ctypes calls.  sublayers.MultiHeadCrossAttention (``ns_xg_*``) has two inputs and two
+outputs and brings its own function, ``CrossTrainFunction``, and its own marshalling on the same base."""
 from __future__ import annotations
 
 import contextlib
@@ -48,7 +49,7 @@ class WorkspaceCache:
 
 class Call:
     """One marshalled call: the shape, the weight block and everything that must stay alive until the launches have run."""
-    __slots__ = ("shape", "weights", "x", "mask", "lens", "keep", "p", "device", "params")
+    __slots__ = ("shape", "weights", "x", "src", "mask", "lens", "keep", "p", "device", "params")
 
 
 class TrainFunction(torch.autograd.Function):
@@ -67,6 +68,28 @@ class TrainFunction(torch.autograd.Function):
     def backward(ctx, g):
         ctx.saved_tensors  # noqa: B018  (the version check)
         grads = ctx.owner._backward(ctx.call, ctx.saved, g, ctx.needs_input_grad[2:])
+        return (None, None) + tuple(grads)
+
+
+class CrossTrainFunction(torch.autograd.Function):
+    """The same for a layer with two differentiable inputs and two outputs (sublayers.MultiHeadCrossAttention): forward = the owner's
+    ``_forward`` -> (y, attn, saved buffer), backward = its ``_backward`` from the gradients of both outputs.  The attention map is the
+    layer's own output and is saved as such, so autograd's version counter refuses a backward after an in-place change of it.  Absent
+    output gradients arrive as ``None`` (``set_materialize_grads(False)``): an unused map costs no zero tensor and no read."""
+
+    @staticmethod
+    def forward(ctx, owner, call, tgt, src, *params):
+        y, attn, saved = owner._forward(call, save=True)
+        ctx.owner, ctx.call, ctx.saved = owner, call, saved
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(tgt, src, attn, *params)
+        return y, attn
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, d_attn):
+        attn = ctx.saved_tensors[2]  # (the version check of every saved tensor)
+        grads = ctx.owner._backward(ctx.call, ctx.saved, attn, g, d_attn, ctx.needs_input_grad[2:])
         return (None, None) + tuple(grads)
 
 
@@ -105,7 +128,7 @@ class HipTrainModule(torch.nn.Module):
         call.weights = self.WEIGHTS()
         for f, p in zip(self.FIELDS, call.params):
             setattr(call.weights, f, p.data_ptr())
-        call.mask = call.lens = None
+        call.src = call.mask = call.lens = None
         return call
 
     def _keep_masks(self, given, n, shape, dev, p):

@@ -407,6 +407,22 @@ hipError_t launch_ag_colsum3(const float* dqkv, int M, int d, double* part, hipS
 // gradients' form); each output nullable
 struct AgPack { const float *wq, *wk, *wv, *bq, *bk, *bv, *wfc; float *wp, *bp, *wt, *wfct; int d; };
 hipError_t launch_ag_pack(const AgPack& p, hipStream_t st);
+// ---- MultiHeadAttention training backward, cross-attention (xattngrad.hip; FFTBlock2.crs_attn, transformer/Layers.py:61-64) -------
+// q, ctx, dctx [B*T, d]; kv [B*L, 2d] = K | V (launch_cross_attention's layout); attn, dattn [B, H, T, L] (dattn nullable); D [B, H, T];
+// lens [B] = src_lens; dk in {64, 128}.
+// the number of query parts of the key-owning kernel, a function of the shape alone, in [1, 8]
+int xg_kv_splits(int B, int H, int T, int L);
+// dq [B*T, d] and dkv [B*L, 2d] = (dK | dV), +0.0 at keys >= lens[b].  The query-owning kernel (writes D and dQ), then — unless dkv
+// is null — the key-owning kernel over nsplit query parts and, for nsplit > 1, the fixed-order sum of partial [nsplit][B*L][2d].
+hipError_t launch_xg_attention_backward(const float* q, const float* kv, const float* ctx, const float* attn, const float* dctx, const float* dattn,
+                                        const long long* lens, int B, int T, int L, int H, int dk, int nsplit, float* D, float* partial, float* dq,
+                                        float* dkv, hipStream_t st);
+// part[blk][third][:] = column sums of rows [64 blk, 64 blk + 64) of src[:, third * d .. third * d + d), src rows of thirds * d floats
+hipError_t launch_xg_colsum(const float* src, int M, int d, int thirds, double* part, hipStream_t st);
+// one launch: wkv [2d][d] = Wk | Wv and bkv [2d] (the forward's form), wkvt [d][2d] = wkv^T, wqt = Wq^T and wfct = Wfc^T [d][d] (the
+// data gradients' form); each output nullable
+struct XgPack { const float *wq, *wk, *wv, *bk, *bv, *wfc; float *wkv, *bkv, *wkvt, *wqt, *wfct; int d; };
+hipError_t launch_xg_pack(const XgPack& p, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

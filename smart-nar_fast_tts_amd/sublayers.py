@@ -12,7 +12,10 @@ path and no torch kernel between ``x`` and ``y`` or between ``grad_output`` and 
 
 Deviation from the reference: the second return value is ``None``, not the attention map.  The [B, H, S, S] map is never written to
 memory (128 MB per decoder layer at B 16, S 1000), and no caller in the reference's loss reads a SELF-attention map (the guided
-attention loss reads the cross-attention maps of ``FFTBlock2.crs_attn``, which this module does not cover)."""
+attention loss reads the cross-attention maps of ``FFTBlock2.crs_attn``, which ``MultiHeadAttention`` does not cover).
+
+``MultiHeadCrossAttention`` is that other use of the same reference class (csrc/xattngrad.hip, ``ns_xg_*``): ``q`` = mel frames,
+``k is v`` = phonemes, the [B, H, T, L] map returned and its gradient accepted."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,7 +23,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._train import HipTrainModule, WorkspaceCache, aligned, guard
+from ._train import CrossTrainFunction, HipTrainModule, WorkspaceCache, aligned, guard
 
 PARAM_NAMES = ("w_qs.weight", "w_qs.bias", "w_ks.weight", "w_ks.bias", "w_vs.weight", "w_vs.bias", "fc.weight", "fc.bias",
                "layer_norm.weight", "layer_norm.bias")  # order of ns_ag_weights
@@ -121,4 +124,132 @@ class MultiHeadAttention(HipTrainModule):
             self._done(self._lib.ns_ag_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.lens), _lib.ptr(call.keep), call.p,
                                                 _lib.ptr(saved), _lib.ptr(g), C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)),
                        "backward")
+        return outs
+
+
+class MultiHeadCrossAttention(HipTrainModule):
+    """Drop-in for ``MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=0.1)`` used as ``FFTBlock2.crs_attn``
+    (transformer/Layers.py:61-64): mel-frame queries against phoneme keys, forward AND backward in HIP (csrc/xattngrad.hip, ``ns_xg_*``).
+    The same parameter names, so ``mel_encoder.layer_stack.N.crs_attn.*`` loads strictly.
+
+        c = MultiHeadCrossAttention(n_head, d_model, d_k, d_v, dropout).to(device)
+        y, attn = c(tgt, src, src, lens=src_lens)        # or mask=crs_attn_mask
+        (loss_of(y) + guided_attention_loss(attn)).backward()
+
+    ``forward(q, k, v, mask=None, lens=None, keep_mask=None) -> (output, attn)`` with ``q`` float32 [B, T, d_model], ``k is v`` float32
+    [B, L, d_model], ``output = layer_norm(dropout(fc(attention)) + q)`` (NOT masked; FFTBlock2 does that outside) and ``attn`` the
+    final probabilities [B, H, T, L] (the reference's shape, transformer/SubLayers.py:48-49), exact 0 at masked keys.
+    ``lens`` is the SOURCE lengths, int [B] on the device: keys ``l >=
+    lens[b]`` are masked, at no host read.  ``mask`` is the reference's bool [B, T, L] ``crs_attn_mask`` with ``mask[b, t, l] = l >=
+    lens[b]`` for every ``t``; from a mask alone the lengths come from ``mask[:, 0, :]`` on the device and, while ``validate_mask`` is
+    True, the whole mask is compared with the one those lengths give: one host read per call.  With neither, every key is valid.
+
+    Under ``torch.no_grad()``, or when no input and no parameter requires grad, a call keeps nothing (the map is still returned).
+    Otherwise it is one ``torch.autograd.Function`` with two differentiable inputs and two outputs that keeps ``q``, ``kv``, ``ctx``,
+    ``z`` (3 B T d + 2 B L d floats) and its own ``attn`` output; the backward accepts the map's gradient (``None`` when the map was
+    not used: it is then never read), honours ``needs_input_grad`` and materialises an absent gradient of ``output`` as zeros.
+
+    Raises on what it cannot do: ``k is not v``, ``d_k != d_v``, ``n_head * d_k != d_model``, d_model not 256 or 512, d_k not 64 or
+    128, a mask that is not a key-padding mask."""
+
+    ABI, INPUT, PARAM_NAMES = "ns_xg", "q", PARAM_NAMES
+    FIELDS, WEIGHTS, GRADS = _lib.AG_NAMES, _lib.NsXgWeights, _lib.NsXgGrads
+    WORKSPACES = WorkspaceCache("ns_xg_ws_bytes", ("B", "T", "L", "d", "H"))
+
+    def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
+        super().__init__()
+        if d_k != d_v:
+            raise ValueError(f"MultiHeadCrossAttention: d_k must equal d_v, got {d_k} and {d_v}")
+        if n_head * d_k != d_model:
+            raise ValueError(f"MultiHeadCrossAttention: n_head * d_k must equal d_model, got {n_head} * {d_k} and {d_model}")
+        if d_model not in (256, 512) or d_k not in (64, 128):
+            raise ValueError(f"MultiHeadCrossAttention: d_model must be 256 or 512 and d_k 64 or 128, got {d_model} and {d_k}")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"MultiHeadCrossAttention: dropout must lie in [0, 1), got {dropout}")
+        self.n_head, self.d_k, self.d_v, self.d_model = n_head, d_k, d_v, d_model
+        self.p_drop = float(dropout)
+        self.w_qs = torch.nn.Linear(d_model, n_head * d_k)
+        self.w_ks = torch.nn.Linear(d_model, n_head * d_k)
+        self.w_vs = torch.nn.Linear(d_model, n_head * d_v)
+        self.layer_norm = torch.nn.LayerNorm(d_model)
+        self.fc = torch.nn.Linear(n_head * d_v, d_model)
+        self.validate_mask = True
+
+    def _marshal(self, q, k, mask, lens, keep_mask):
+        call = self._begin(q, self.d_model)
+        B, T, d = q.shape
+        dev = call.device
+        if not (isinstance(k, torch.Tensor) and k.device == dev and k.dtype == torch.float32 and k.dim() == 3 and k.shape[0] == B and k.shape[2] == d
+                and k.shape[1] > 0):
+            raise ValueError(f"k must be a float32 [B, L, {d}] tensor on {dev} with B = {B} and L > 0")
+        L = k.shape[1]
+        call.src = aligned(k.detach())
+        s = _lib.NsXgShape()
+        s.B, s.T, s.L, s.d, s.H = B, T, L, d, self.n_head
+        call.shape = s
+        if lens is not None:
+            if not isinstance(lens, torch.Tensor) or tuple(lens.shape) != (B,) or lens.device != dev or lens.dtype not in (torch.int64, torch.int32):
+                raise ValueError(f"lens must be an int64 [B] = {(B,)} tensor on {dev}")
+            call.lens = lens.to(torch.int64).contiguous()
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, T, L) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != dev:
+                raise ValueError(f"mask must be a bool [B, T, L] = {(B, T, L)} tensor on {dev}")
+            if call.lens is None:
+                with guard(dev):
+                    m = mask != 0
+                    call.lens = (L - m[:, 0, :].sum(-1)).to(torch.int64)
+                    if self.validate_mask:
+                        want = torch.arange(L, device=dev)[None, None, :] >= call.lens[:, None, None]
+                        if not bool((m == want).all()):
+                            raise ValueError("mask is not a key-padding mask: mask[b, t, l] must equal l >= lens[b] for every t")
+        if call.lens is None:
+            with guard(dev):
+                call.lens = torch.full((B,), L, dtype=torch.int64, device=dev)
+        call.p = self.p_drop if self.training else 0.0
+        call.keep = self._keep_masks(None if keep_mask is None else (keep_mask,), 1, (B, T, d), dev, call.p)[0]
+        return call
+
+    def forward(self, q, k, v, mask=None, lens=None, keep_mask=None):
+        if k is not v:
+            raise ValueError("MultiHeadCrossAttention: k and v must be the same tensor (the keys and values of crs_attn are both the source)")
+        call = self._marshal(q, k, mask, lens, keep_mask)
+        params = self.ordered_parameters()
+        if not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or any(p.requires_grad for p in params))):
+            y, attn, _ = self._forward(call, save=False)
+            return y, attn
+        return CrossTrainFunction.apply(self, call, q, k, *params)
+
+    def _forward(self, call, save):
+        s, dev = call.shape, call.device
+        with guard(dev):
+            ws, saved = self._workspace(call, save)
+            y = torch.empty((s.B, s.T, s.d), dtype=torch.float32, device=dev)
+            attn = torch.empty((s.B, s.H, s.T, s.L), dtype=torch.float32, device=dev)
+            self._done(self._lib.ns_xg_forward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.src), _lib.ptr(call.lens),
+                                               _lib.ptr(call.keep), call.p, _lib.ptr(y), _lib.ptr(attn), _lib.ptr(saved), _lib.ptr(ws), ws.numel(),
+                                               _lib.stream_ptr(dev)), "forward")
+        return y, attn, saved
+
+    def _backward(self, call, saved, attn, g, d_attn, need):
+        """Gradients of ``(g * y).sum() + (d_attn * attn).sum()``: a list (dtgt, dsrc, then the ten of PARAM_NAMES) with None where
+        ``need`` is False.  ``g`` None = zeros; ``d_attn`` None = the map was not used."""
+        s, dev = call.shape, call.device
+        with guard(dev):
+            if g is None:
+                g = torch.zeros((s.B, s.T, s.d), dtype=torch.float32, device=dev)
+            if tuple(g.shape) != (s.B, s.T, s.d) or g.dtype != torch.float32 or g.device != dev:
+                raise ValueError(f"grad_output must be a float32 {(s.B, s.T, s.d)} tensor on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+            if d_attn is not None and (tuple(d_attn.shape) != (s.B, s.H, s.T, s.L) or d_attn.dtype != torch.float32 or d_attn.device != dev):
+                raise ValueError(f"the map's gradient must be a float32 {(s.B, s.H, s.T, s.L)} tensor on {dev}")
+            g, attn = aligned(g), aligned(attn.detach())
+            d_attn = None if d_attn is None else aligned(d_attn)
+            outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None
+                    for t, n in zip([call.x, call.src] + call.params, need)]
+            d = self.GRADS()
+            for f, o in zip(("dtgt", "dsrc") + tuple(self.FIELDS), outs):
+                setattr(d, f, o.data_ptr() if o is not None else None)
+            ws, _ = self._workspace(call, save=False)
+            self._done(self._lib.ns_xg_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.src), _lib.ptr(call.lens),
+                                                _lib.ptr(call.keep), call.p, _lib.ptr(saved), _lib.ptr(attn), _lib.ptr(g), _lib.ptr(d_attn),
+                                                C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward")
         return outs

@@ -1098,6 +1098,87 @@ int ns_xg_op_attention_backward(const float* q, const float* kv, const float* ct
                                 const int64_t* src_lens, int B, int T, int L, int d, int H, int kv_splits, float* dq, float* dkv, void* ws,
                                 size_t ws_bytes, void* stream);
 
+/* ==== PostNet: a training forward with train-mode BatchNorm1d and its backward (transformer/Layers.py:107-177) ====================
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  x [B, T, n_mel], M = B * T rows, layers i = 0 .. n - 1
+ * with channels C_0 = n_mel, C_1 .. C_{n-1} = emb, C_n = n_mel, K taps ("same" padding (K - 1) / 2 per utterance), h_{-1} = x:
+ *   u_i = conv_i(h_{i-1}) + b_i
+ *   training: mu_i, var_i = mean and BIASED variance of u_i over ALL M rows (no mask); running_mean = 0.9 running_mean + 0.1 mu,
+ *             running_var = 0.9 running_var + 0.1 var M / (M - 1), num_batches_tracked += 1, written by the kernels of the forward
+ *   else:     mu_i, var_i = running_mean, running_var, which are only read
+ *   n_i = gamma_i (u_i - mu_i) / sqrt(var_i + 1e-5) + beta_i
+ *   h_i = keep_i / (1 - p_drop) * tanh(n_i) for i < n - 1, h_{n-1} = keep_{n-1} / (1 - p_drop) * n_{n-1};  y = h_{n-1} (no residual)
+ * The weights are LIVE device tensors in checkpoint layout; dropout is n uint8 keep-masks [M, C_{i+1}] (1 = kept) and p_drop.  Exact
+ * fp32 GEMMs on the fp32 matrix cores; every column sum, mu and rstd in float64, every stored value rounded once.  No atomic, no host
+ * read; equal inputs give equal bits. */
+#define NS_PN_ABI_VERSION 1
+#define NS_PN_MAX_LAYERS 5
+int ns_pn_abi_version(void);
+typedef struct ns_pn_shape { int32_t B, T, n_mel, emb, K, n; } ns_pn_shape;
+/* Device pointers of one layer, 16-byte aligned (num_batches_tracked: 8), fp32, checkpoint layout.  The three buffers are written by
+ * ns_pn_forward with training != 0 and are never written otherwise. */
+typedef struct ns_pn_layer {
+  const float* w;      /* [C_{i+1}, C_i, K] convolutions.{i}.0.conv.weight */
+  const float* b;      /* [C_{i+1}] convolutions.{i}.0.conv.bias */
+  const float* gamma;  /* [C_{i+1}] convolutions.{i}.1.weight */
+  const float* beta;   /* [C_{i+1}] convolutions.{i}.1.bias */
+  float* running_mean; /* [C_{i+1}] */
+  float* running_var;  /* [C_{i+1}] */
+  int64_t* num_batches_tracked; /* [] int64 */
+} ns_pn_layer;
+typedef struct ns_pn_weights { ns_pn_layer layer[NS_PN_MAX_LAYERS]; } ns_pn_weights;  /* layers >= n are ignored */
+/* The outputs of ns_pn_backward, shaped like the parameters, and dx [B, T, n_mel].  16-byte aligned.  NULL = not wanted: neither
+ * computed nor written, and a launch none of whose outputs is wanted is not made. */
+typedef struct ns_pn_layer_grads { float *w, *b, *gamma, *beta; } ns_pn_layer_grads;
+typedef struct ns_pn_grads { ns_pn_layer_grads layer[NS_PN_MAX_LAYERS]; float* dx; } ns_pn_grads;
+/* Bytes of the workspace of every ns_pn_forward / ns_pn_backward of this shape (0 and ns_last_error() for a refused shape), and of
+ * `saved`: u_0 | h_0 | u_1 | h_1 | ... | u_{n-1} as floats ([M, C_{i+1}] each; h_{n-1} is y and is not kept), then per layer mu [emb] and
+ * rstd [emb] as float64: 4 M (2 (n - 1) emb + n_mel) + 16 n emb bytes. */
+size_t ns_pn_ws_bytes(const ns_pn_shape* shape);
+size_t ns_pn_saved_bytes(const ns_pn_shape* shape);
+/* Kernel launches the calling thread's last ns_pn_* call enqueued. */
+int ns_pn_last_launches(void);
+/* Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a pointer that is not 16-byte
+ * aligned, emb not 256 or 512, n_mel not a multiple of 16 in [16, 128], K even or above 9, n outside [2, 5], B * T * emb >= 2^31,
+ * training with B * T == 1, a shape the Conv1D-as-GEMM dispatch or the weight gradient's plan refuses, p_drop outside [0, 1),
+ * keep-masks without p_drop > 0 or p_drop > 0 without all n of them, a workspace smaller than ns_pn_ws_bytes.
+ * y [B, T, n_mel].  keep: n pointers (NULL itself allowed when p_drop == 0).  saved: ns_pn_saved_bytes, or NULL (nothing kept).
+ * Launches: ceil(n / 2) (pack) + per layer G(M, C_{i+1}, K C_i) (the dispatch's own count, ns_plan_gemm_launches) + 1 (column sums,
+ * training only) + 1 (finish) + 1 (apply). */
+int ns_pn_forward(const ns_pn_shape* shape, const ns_pn_weights* weights, int training, const float* x, const uint8_t* const* keep,
+                  float p_drop, float* y, void* saved, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of sum g . y (g [B, T, n_mel]) with respect to every non-NULL member of grads, from `saved` as ns_pn_forward wrote it
+ * for the same arguments.  training != 0: the batch statistics are differentiated; else mu and var are constants.  No buffer is
+ * written.  Layers are walked from the last to the first and the walk stops below the lowest layer anything is wanted from.
+ * Per visited layer: 1 (column sums of dy and dy xhat) + 1 (finish) — both dropped when training == 0 and neither gamma nor beta is
+ * wanted — + 1 (dz) + 2 (d_weight: GEMM, reduce; 3 on the last layer, whose dz is padded to 128 columns and whose first n_mel rows
+ * are copied out) + G (dh_{i-1}, or dx on layer 0; not on the lowest visited layer unless that is layer 0 and dx is wanted); plus
+ * ceil(k / 2) pack launches for the k data gradients and 1 for all wanted d_bias. */
+int ns_pn_backward(const ns_pn_shape* shape, const ns_pn_weights* weights, int training, const float* x, const uint8_t* const* keep,
+                   float p_drop, const void* saved, const float* g, const ns_pn_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* Each new kernel alone, on M rows of C columns (C a multiple of 16 up to 512).  stats [2][C] float64 = mu | rstd.
+ * training != 0: from u [M, C], and running_mean / running_var / num_batches_tracked (all three or none) updated; ws: ceil(M / 32) * 2
+ * * C doubles; two launches.  training == 0: from running_mean / running_var alone (u unused); one launch. */
+int ns_pn_op_stats(const float* u, int M, int C, int training, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                   double* stats, void* ws, size_t ws_bytes, void* stream);
+/* h [M, C] = keep / (1 - p) * tanh(gamma (u - mu) rstd + beta); last != 0: without the tanh.  keep [M, C] iff p_drop > 0.  One launch. */
+int ns_pn_op_apply(const float* u, const double* stats, const float* gamma, const float* beta, const uint8_t* keep, float p_drop, int last,
+                   int M, int C, float* h, void* stream);
+/* With dy = dh keep / (1 - p) (1 - (h (1 - p))^2) (last != 0: without the tanh factor, h unused) and xhat = (u - mu) rstd:
+ * d_beta = sum dy, d_gamma = sum dy xhat (both required), means [2][C] float64 = their means over M.  ws as ns_pn_op_stats.  Two launches. */
+int ns_pn_op_bwd_reduce(const float* dh, const float* u, const float* h, const double* stats, const uint8_t* keep, float p_drop, int last,
+                        int M, int C, float* d_gamma, float* d_beta, double* means, void* ws, size_t ws_bytes, void* stream);
+/* dz [M, ldz] = gamma rstd (dy - means[0] - xhat means[1]), or gamma rstd dy when means is NULL (eval); ldz = C, or 128 >= C with
+ * columns [C, 128) written as zeros.  d_bias [C] (nullable) = column sums of the unrounded float64 dz.  ws: ceil(M / 32) * C doubles.
+ * One launch, two with d_bias. */
+int ns_pn_op_bwd_apply(const float* dh, const float* u, const float* h, const double* stats, const double* means, const float* gamma,
+                       const uint8_t* keep, float p_drop, int last, int M, int C, int ldz, float* dz, float* d_bias, void* ws,
+                       size_t ws_bytes, void* stream);
+/* dW [N, Cin, KW] for N < 128 (a multiple of 16) from dz [B*S, 128] whose columns [N, 128) are zero: the N = 128 plan of
+ * ns_pg_plan_wgrad into a scratch, the first N rows copied out.  ws: the plan's floats + 128 * Cin * KW floats, each rounded up to
+ * 256 bytes.  Three launches. */
+int ns_pn_op_wgrad_narrow(const float* dz, const float* X, int B, int S, int N, int Cin, int KW, float* dW, void* ws, size_t ws_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

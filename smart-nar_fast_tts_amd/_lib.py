@@ -121,6 +121,26 @@ class NsXgGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in AG_NAMES + ("dtgt", "dsrc")]
 
 
+class NsPnShape(C.Structure):
+    """``ns_pn_shape`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "n_mel", "emb", "K", "n")]
+
+
+PN_MAX_LAYERS = 5
+PN_PARAMS = ("w", "b", "gamma", "beta")                                   # per layer, the order of ns_pn_layer_grads
+PN_BUFFERS = ("running_mean", "running_var", "num_batches_tracked")       # what follows them in ns_pn_layer
+
+
+class NsPnWeights(C.Structure):
+    """``ns_pn_weights`` (include/nar_fs2.h): five ``ns_pn_layer`` blocks, flattened as ``w0, b0, gamma0, ..., num_batches_tracked4``."""
+    _fields_ = [(f"{n}{i}", C.c_void_p) for i in range(PN_MAX_LAYERS) for n in PN_PARAMS + PN_BUFFERS]
+
+
+class NsPnGrads(C.Structure):
+    """``ns_pn_grads`` (include/nar_fs2.h): five ``ns_pn_layer_grads`` blocks flattened the same way, then ``dx``; each nullable."""
+    _fields_ = [(f"{n}{i}", C.c_void_p) for i in range(PN_MAX_LAYERS) for n in PN_PARAMS] + [("dx", C.c_void_p)]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -327,6 +347,18 @@ SIGNATURES = {
     "ns_xg_forward": (_I, [C.POINTER(NsXgShape), C.POINTER(NsXgWeights), _P, _P, _P, _P, _F, _P, _P, _P, _P, _Z, _P]),
     "ns_xg_backward": (_I, [C.POINTER(NsXgShape), C.POINTER(NsXgWeights), _P, _P, _P, _P, _F, _P, _P, _P, _P, C.POINTER(NsXgGrads), _P, _Z, _P]),
     "ns_xg_op_attention_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    # PostNet with train-mode BatchNorm, training forward and backward (postnet.PostNet; handle-less)
+    "ns_pn_abi_version": (_I, []),
+    "ns_pn_ws_bytes": (_Z, [C.POINTER(NsPnShape)]),
+    "ns_pn_saved_bytes": (_Z, [C.POINTER(NsPnShape)]),
+    "ns_pn_last_launches": (_I, []),
+    "ns_pn_forward": (_I, [C.POINTER(NsPnShape), C.POINTER(NsPnWeights), _I, _P, C.POINTER(_P), _F, _P, _P, _P, _Z, _P]),
+    "ns_pn_backward": (_I, [C.POINTER(NsPnShape), C.POINTER(NsPnWeights), _I, _P, C.POINTER(_P), _F, _P, _P, C.POINTER(NsPnGrads), _P, _Z, _P]),
+    "ns_pn_op_stats": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "ns_pn_op_apply": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P]),
+    "ns_pn_op_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "ns_pn_op_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ns_pn_op_wgrad_narrow": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

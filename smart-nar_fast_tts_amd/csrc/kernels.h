@@ -423,6 +423,48 @@ hipError_t launch_xg_colsum(const float* src, int M, int d, int thirds, double* 
 // data gradients' form); each output nullable
 struct XgPack { const float *wq, *wk, *wv, *bk, *bv, *wfc; float *wkv, *bkv, *wkvt, *wqt, *wfct; int d; };
 hipError_t launch_xg_pack(const XgPack& p, hipStream_t st);
+// ---- PostNet training forward / backward with train-mode BatchNorm (postnetgrad.hip; transformer/Layers.py:107-177) ----------------
+// Activations are row-major [M, C], C a multiple of 16 up to 512.  A column reduction gives every workgroup PN_ROW_BLOCK rows and all
+// columns: thread (r, cg) owns the 16-byte column group cg and the rows r, r + 256 / (C / 4), ... of the block, sums in float64, and the
+// row lanes are added in ascending order through LDS: part [pn_row_blocks(M)][slots][C] doubles, uninitialised.  The finish adds the
+// blocks as 16 ascending segments, the segments in ascending order.  No atomics; every order depends on the shape alone.
+constexpr int PN_ROW_BLOCK = 32;
+constexpr int PN_MAX_LAYERS = 5;
+constexpr int PN_PAD_N = 128;  // width the last layer's dz is padded to: the narrowest N pg_plan_wgrad takes
+inline int pn_row_blocks(int M) { return (M + PN_ROW_BLOCK - 1) / PN_ROW_BLOCK; }
+// part[blk][0][:] = sum u, part[blk][1][:] = sum u^2 over the block's rows
+hipError_t launch_pn_stats(const float* u, int M, int C, double* part, hipStream_t st);
+// What follows a column reduction.  mode PN_FIN_TRAIN: stats [2][C] doubles = mu, 1 / sqrt(biased var + 1e-5) from the two sums, and
+// (running_mean non-null) running_mean = 0.9 running_mean + 0.1 mu, running_var = 0.9 running_var + 0.1 var M / (M - 1),
+// *num_batches_tracked += 1.  PN_FIN_EVAL: stats from running_mean / running_var, no partials read, nothing else written.
+// PN_FIN_BWD: from sum dy and sum dy xhat: out0 = d_beta, out1 = d_gamma (floats, nullable), stats = the two means (nullable).
+enum PnFinMode : int { PN_FIN_TRAIN = 0, PN_FIN_EVAL = 1, PN_FIN_BWD = 2 };
+struct PnFinish {
+  int mode, nblk, C, M;
+  const double* part; double* stats;
+  float *running_mean, *running_var; long long* num_batches_tracked;
+  float *out0, *out1;
+};
+hipError_t launch_pn_finish(const PnFinish& a, hipStream_t st);
+// h [M, C] = keep * scale * tanh(gamma (u - mu) rstd + beta), without the tanh when last; keep uint8 [M, C] nullable
+hipError_t launch_pn_apply(const float* u, const double* stats, const float* gamma, const float* beta, const uint8_t* keep, float scale, int last,
+                           int M, int C, float* h, hipStream_t st);
+// dy = dh keep scale (1 - (h / scale)^2) (last: dy = dh keep scale; h is not read), xhat = (u - mu) rstd.
+// reduce: part[blk][0][:] = sum dy, part[blk][1][:] = sum dy xhat.
+// apply:  dz [M, ldz] = gamma rstd (dy - means[0] - xhat means[1]), or gamma rstd dy when means is null (eval); columns [C, ldz) are
+//         written as zeros; bias_part [blk][C] (nullable) = column sums of the unrounded float64 dz.  ldz = C, or PN_PAD_N >= C.
+struct PnBackward {
+  int M, C, ldz, last; float scale;
+  const float *dh, *u, *h, *gamma; const double *stats, *means; const uint8_t* keep;
+  double* part; float* dz; double* bias_part;
+};
+hipError_t launch_pn_bwd_reduce(const PnBackward& a, hipStream_t st);
+hipError_t launch_pn_bwd_apply(const PnBackward& a, hipStream_t st);
+// out[l][:] = the ascending sum over blocks of part[l] [nblk][C[l]] for every layer with a non-null out; one launch (none when all null)
+struct PnBiasFinish { const double* part[PN_MAX_LAYERS]; float* out[PN_MAX_LAYERS]; int C[PN_MAX_LAYERS]; int nblk; };
+hipError_t launch_pn_bias_finish(const PnBiasFinish& a, hipStream_t st);
+// dst[i] = src[i], i < n, n a multiple of 4, both 16-byte aligned
+hipError_t launch_pn_copy(const float* src, float* dst, long long n, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

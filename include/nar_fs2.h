@@ -1179,6 +1179,41 @@ int ns_pn_op_bwd_apply(const float* dh, const float* u, const float* h, const do
 int ns_pn_op_wgrad_narrow(const float* dz, const float* X, int B, int S, int N, int Cin, int KW, float* dW, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ==== VarianceAdaptor: the two pieces its training path lacked, forward and backward (model/modules.py:17-159, 195-230) ============
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  The three predictors are ns_pg_*; these are the
+ * variance embedding (bucketize + nn.Embedding + add) and the length regulator.  Every sum is float64 in an order that depends on the
+ * shape alone and is rounded once: no atomic, no host read; equal inputs give equal bits.
+ * Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a misaligned pointer (16 bytes
+ * for the float tensors and the workspace, 8 for int64, 4 for int32, target and bins), a non-positive size, D not a multiple of 4,
+ * n_bins < 2, rows * D >= 2^31, a shape ns_va_plan_embed refuses, a workspace smaller than ns_va_embed_ws_bytes. */
+#define NS_VA_ABI_VERSION 1
+int ns_va_abi_version(void);
+/* Kernel launches the calling thread's last ns_va_* call enqueued. */
+int ns_va_last_launches(void);
+/* The embedding gradient's plan, without a GPU: out = { row blocks, rows per block, slab width (columns per workgroup), column slabs,
+ * LDS bytes per workgroup (n_bins * slab * 8, at most 65536), launches, threads per workgroup, 0 }.  Row blocks are ceil(M / 512); the
+ * slab is the widest power of two up to 64 whose table fits.  Returns 0, or nonzero with ns_last_error() for a shape it cannot hold
+ * (D % 4 != 0, n_bins < 2, n_bins > 2048: a table past the limit even at 4 columns); there is no fall-back. */
+int ns_va_plan_embed(int M, int D, int n_bins, int32_t out[8]);
+/* Bytes of ns_va_op_embed_bwd's workspace: float64 partials [row blocks][n_bins][D]; 0 and ns_last_error() for a refused shape. */
+size_t ns_va_embed_ws_bytes(int M, int D, int n_bins);
+/* y [M, D] = x + table[idx], idx [M] (int32, written) = torch.bucketize(target [M], bins [n_bins - 1]) with right=False, NaN ->
+ * n_bins - 1: the index ns_op_bucketize gives.  Unmasked: every row takes the embedding of its target.  One launch. */
+int ns_va_op_embed_fwd(const float* x, const float* target, const float* bins, const float* table, int M, int D, int n_bins, float* y,
+                       int32_t* idx, void* stream);
+/* d_table [n_bins, D] = the sum of g [M, D]'s rows per index, over all M rows; a bin no row hits is +0.0; an index outside [0, n_bins)
+ * contributes nothing.  (The gradient of x is g itself.)  Two launches. */
+int ns_va_op_embed_bwd(const float* g, const int32_t* idx, int M, int D, int n_bins, float* d_table, void* ws, size_t ws_bytes, void* stream);
+/* duration [B, L] int64 non-NULL: cum [B, L] (int32, inclusive prefix sums of max(d, 0), saturated at 2^31 - 1) and mel_len [B] (int64,
+ * the uncropped total) are written (one launch).  out [B, T, D] non-NULL: frame t of utterance b = x [B, L, D]'s row of the phoneme
+ * whose [cum[l-1], cum[l]) holds t, +0.0 at and past the total; frames at or past T are dropped (one launch; reads cum, which the same
+ * call may have written).  At least one of the two; duration NULL takes cum as input and leaves mel_len alone. */
+int ns_va_op_lr_fwd(const float* x, const int64_t* duration, int B, int L, int D, int T, float* out, int32_t* cum, int64_t* mel_len,
+                    void* stream);
+/* d_x [B, L, D] = the sum of g [B, T, D] over t in [cum[l-1], min(cum[l], T)) in t order; +0.0 for duration 0.  Frames at or past an
+ * utterance's total are never read.  One launch. */
+int ns_va_op_lr_bwd(const float* g, const int32_t* cum, int B, int L, int D, int T, float* d_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -359,6 +359,15 @@ SIGNATURES = {
     "ns_pn_op_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ns_pn_op_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "ns_pn_op_wgrad_narrow": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    # VarianceAdaptor: variance embedding and length regulator, forward and backward (adaptor.py; handle-less)
+    "ns_va_abi_version": (_I, []),
+    "ns_va_last_launches": (_I, []),
+    "ns_va_plan_embed": (_I, [_I, _I, _I, C.POINTER(C.c_int32)]),
+    "ns_va_embed_ws_bytes": (_Z, [_I, _I, _I]),
+    "ns_va_op_embed_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "ns_va_op_embed_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "ns_va_op_lr_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "ns_va_op_lr_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -465,6 +465,26 @@ struct PnBiasFinish { const double* part[PN_MAX_LAYERS]; float* out[PN_MAX_LAYER
 hipError_t launch_pn_bias_finish(const PnBiasFinish& a, hipStream_t st);
 // dst[i] = src[i], i < n, n a multiple of 4, both 16-byte aligned
 hipError_t launch_pn_copy(const float* src, float* dst, long long n, hipStream_t st);
+// ---- VarianceAdaptor training pieces (adaptorgrad.hip; model/modules.py:17-159, 195-230) --------------------
+// The embedding gradient's plan, a function of the shape alone: row blocks of VA_ROW_BLOCK rows, column slabs of `slab` columns (the
+// widest power of two up to 64 whose n_bins x slab float64 table fits VA_LDS_LIMIT), one 64-thread workgroup per (row block, slab).
+constexpr int VA_ROW_BLOCK = 512;
+constexpr int VA_LDS_LIMIT = 65536;
+struct VaEmbedPlan { int row_blocks, rows_per_block, slab, n_slabs, lds_bytes, launches; long long ws_bytes; };
+bool va_plan_embed(int M, int D, int n_bins, VaEmbedPlan* plan);  // false: D % 4 != 0, n_bins < 2, a table past the limit, M <= 0
+// y[m, :] = x[m, :] + table[idx[m], :], idx[m] = wave_bucketize(bins, n_bins - 1, target[m]) written as int32; one wave per row
+hipError_t launch_va_embed_fwd(const float* x, const float* target, const float* bins, const float* table, int M, int D, int n_bins, float* y,
+                               int32_t* idx, hipStream_t st);
+// d_table[k, :] = the sum of g[m, :] over the rows with idx[m] == k, in float64: part [row_blocks][n_bins][D] doubles (uninitialised)
+// hold each block's sums in row order, the finish adds the blocks in ascending order and rounds once.  A bin no row hits is +0.0; an
+// index outside [0, n_bins) contributes nothing.  Two launches, no atomics.
+hipError_t launch_va_embed_bwd(const float* g, const int32_t* idx, int M, int D, int n_bins, const VaEmbedPlan& plan, double* part, float* d_table,
+                               hipStream_t st);
+// cum[b][l] = the inclusive prefix sum of max(duration[b][l], 0), saturated at INT32_MAX; mel_len[b] = the whole sum (int64)
+hipError_t launch_va_duration_scan(const long long* duration, int B, int L, int32_t* cum, long long* mel_len, hipStream_t st);
+// d_x[b, l, :] = the sum of g[b, t, :] over t in [cum[l-1], min(cum[l], T)) in t order, float64, rounded once; +0.0 for an empty range.
+// One wave per phoneme, 16-byte lanes.
+hipError_t launch_va_lr_bwd(const float* g, const int32_t* cum, int B, int L, int D, int T, float* d_x, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

@@ -1,8 +1,9 @@
-"""What the trainable HIP layers share on the Python side (predictor.VariancePredictor over ``ns_pg_*``, sublayers.MultiHeadAttention
-over ``ns_ag_*``): the device guard, the workspace cache, the one ``torch.autograd.Function`` and the module base class that marshals
-the input, the ten parameters, the keep-masks and the gradient block.  A layer keeps its constructor checks, its ``PARAM_NAMES``, its
-shape struct, its mask handling and its two ctypes calls.  sublayers.MultiHeadCrossAttention (``ns_xg_*``) has two inputs and two
-outputs and brings its own function, ``CrossTrainFunction``, and its own marshalling on the same base."""
+"""What the trainable HIP layers share on the Python side (predictor.VariancePredictor over ``ns_pg_*``, the two attentions of
+sublayers.py over ``ns_ag_*`` / ``ns_xg_*``, postnet.PostNet over ``ns_pn_*``, the embedding and the length regulator of adaptor.py
+over ``ns_va_*``): the device guards, the launch bookkeeping (``CountedModule``), the workspace cache, the autograd Functions and the
+module base class that marshals the inputs, the parameters, the keep-masks and the gradient block.  A layer keeps its constructor
+checks, its ``PARAM_NAMES``, its shape struct, its mask handling and its two ctypes calls.  The cross-attention has two outputs, one of
+them saved for the backward, and so brings ``CrossTrainFunction`` next to ``TrainFunction``; everything else it takes from the base."""
 from __future__ import annotations
 
 import contextlib
@@ -21,6 +22,11 @@ def guard(dev):
 def aligned(t):
     t = t.contiguous()
     return t.clone() if t.data_ptr() % 16 else t
+
+
+def need_gpu(who, name, t):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"{who}: {name} must live on the MI355X (there is no CPU path)")
 
 
 class WorkspaceCache:
@@ -48,13 +54,15 @@ class WorkspaceCache:
 
 
 class Call:
-    """One marshalled call: the shape, the weight block and everything that must stay alive until the launches have run."""
-    __slots__ = ("shape", "weights", "x", "src", "mask", "lens", "keep", "p", "device", "params")
+    """One marshalled call: the shape, the weight block and everything that must stay alive until the launches have run.  ``inputs``
+    are the differentiable inputs in the order of the layer's ``INPUT_GRADS`` (``x`` first; the cross-attention adds ``src``);
+    ``training`` and ``buffers`` are the BatchNorm mode and the live running statistics of a layer that has them."""
+    __slots__ = ("shape", "weights", "x", "src", "inputs", "mask", "lens", "keep", "p", "training", "buffers", "device", "params")
 
 
 class TrainFunction(torch.autograd.Function):
     """forward = the owner's ``_forward`` (keeps its saved buffer), backward = its ``_backward``; the differentiable tensors are x and
-    the ten parameters."""
+    the parameters."""
 
     @staticmethod
     def forward(ctx, owner, call, x, *params):
@@ -93,17 +101,33 @@ class CrossTrainFunction(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
-class HipTrainModule(torch.nn.Module):
-    """Base of a layer whose forward and backward are one handle-less C ABI.  It holds no parameter, buffer or submodule of its own.
-    A subclass sets ``ABI`` ("ns_pg"), ``PARAM_NAMES`` (checkpoint names, ABI order), ``FIELDS`` (the same ten as struct fields),
-    ``WEIGHTS`` / ``GRADS`` (the ctypes structs), ``WORKSPACES`` (its WorkspaceCache) and ``INPUT`` (what messages call ``x``), and
-    defines ``_forward(call, save) -> (y, saved)`` and ``_backward(call, saved, g, need) -> [dx, ten gradients]``."""
+class CountedModule(torch.nn.Module):
+    """Launch bookkeeping of a module over one handle-less C ABI, named by the subclass's ``ABI`` ("ns_pg"): ``launches`` enqueued so
+    far and ``last_launches`` per direction, as the C side counted them (``ns_*_last_launches``)."""
 
     def __init__(self):
         super().__init__()
         self._lib = _lib.load()
-        self.launches = 0          # kernel launches enqueued so far, as the C side counted them (ns_*_last_launches)
+        self.launches = 0
         self.last_launches = {}    # {"forward": n, "backward": n} of the latest calls
+
+    def _done(self, rc, which, entry=None, add=False):
+        """Raises on a failed entry point (``ns_*_forward`` / ``ns_*_backward`` unless ``entry`` names another), else books its
+        launches under ``which``; ``add``: on top of the call before, for a direction made of two calls."""
+        _lib.check(rc, entry or f"{self.ABI}_{which}")
+        n = getattr(self._lib, self.ABI + "_last_launches")()
+        self.launches += n
+        self.last_launches[which] = n + (self.last_launches.get(which, 0) if add else 0)
+
+
+class HipTrainModule(CountedModule):
+    """Base of a layer whose forward and backward are one handle-less C ABI.  It holds no parameter, buffer or submodule of its own.
+    A subclass sets ``ABI`` ("ns_pg"), ``PARAM_NAMES`` (checkpoint names, ABI order), ``FIELDS`` (the same as struct fields),
+    ``WEIGHTS`` / ``GRADS`` (the ctypes structs), ``WORKSPACES`` (its WorkspaceCache), ``INPUT`` (what messages call ``x``) and, where
+    it has more differentiable inputs than ``x``, ``INPUT_GRADS`` (their fields in GRADS), and defines ``_forward(call, save) -> (y,
+    saved)`` and ``_backward(call, saved, g, need) -> [input gradients, parameter gradients]``."""
+
+    INPUT_GRADS = ("dx",)
 
     def ordered_parameters(self):
         named = dict(self.named_parameters())
@@ -111,8 +135,7 @@ class HipTrainModule(torch.nn.Module):
 
     def _begin(self, x, width) -> Call:
         """Checks ``x`` (float32 [B, S, width] on the GPU) and the parameters; a Call with device, x, params and the weight block."""
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            raise RuntimeError(f"{type(self).__name__}: {self.INPUT} must live on the MI355X (there is no CPU path)")
+        need_gpu(type(self).__name__, self.INPUT, x)
         if x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != width:
             raise ValueError(f"{self.INPUT} must be float32 [B, S, {width}], got {x.dtype} {tuple(x.shape)}")
         if x.shape[0] == 0 or x.shape[1] == 0:
@@ -124,32 +147,36 @@ class HipTrainModule(torch.nn.Module):
                 raise ValueError(f"{n} must be a float32 tensor on {dev}, got {p.dtype} on {p.device}")
         call = Call()
         call.device, call.x = dev, aligned(x.detach())
+        call.inputs = [call.x]
         call.params = [aligned(p.detach()) for p in params]
         call.weights = self.WEIGHTS()
         for f, p in zip(self.FIELDS, call.params):
             setattr(call.weights, f, p.data_ptr())
-        call.src = call.mask = call.lens = None
+        call.src = call.mask = call.lens = call.buffers = None
+        call.training = False
         return call
 
-    def _keep_masks(self, given, n, shape, dev, p):
-        """The ``n`` keep-masks (uint8 ``shape``) of a call at drop probability ``p``: the ``given`` ones validated, else one
-        ``torch.bernoulli`` draw of all ``n``, else ``n`` Nones."""
+    def _keep_masks(self, given, shapes, dev, p, stacked=False):
+        """The keep-masks (uint8, one per entry of ``shapes``) of a call at drop probability ``p``: the ``given`` ones validated, else
+        drawn with ``torch.bernoulli`` — one draw per mask in order, or, ``stacked`` (the shapes are equal), one draw of all of them —
+        else Nones."""
+        n = len(shapes)
         arg, one = ("keep_masks", "a keep-mask") if n > 1 else ("keep_mask", "keep_mask")
         if given is not None:
             if p == 0.0:
                 raise ValueError(f"{arg} given although no dropout applies (eval() or dropout == 0)")
-            ks = []
-            for k in given:
+            given = list(given)
+            if len(given) != n:
+                raise ValueError(f"keep_masks must hold {n} masks, got {len(given)}")
+            for k, shape in zip(given, shapes):
                 if tuple(k.shape) != shape or k.device != dev:
                     raise ValueError(f"{one} must have shape {shape} on {dev}, got {tuple(k.shape)} on {k.device}")
-                ks.append(aligned((k != 0).contiguous().view(torch.uint8)))
-            if len(ks) != n:
-                raise ValueError("keep_masks must be a pair (dropout_1, dropout_2)")
-            return tuple(ks)
+            return tuple(aligned((k != 0).contiguous().view(torch.uint8)) for k in given)
         if p > 0.0:
+            draws = [(n,) + shapes[0]] if stacked else shapes
             with guard(dev):
-                k = torch.bernoulli(torch.full((n,) + shape if n > 1 else shape, 1.0 - p, dtype=torch.float32, device=dev)).to(torch.uint8)
-            return tuple(k[i] for i in range(n)) if n > 1 else (k,)
+                ks = [torch.bernoulli(torch.full(s, 1.0 - p, dtype=torch.float32, device=dev)).to(torch.uint8) for s in draws]
+            return tuple(ks[0]) if stacked else tuple(ks)
         return (None,) * n
 
     def _dispatch(self, call, x):
@@ -168,16 +195,10 @@ class HipTrainModule(torch.nn.Module):
         return ws, torch.empty(n, dtype=torch.float32, device=call.device)
 
     def _grad_block(self, call, need):
-        """(outs, GRADS struct): a fresh tensor for dx and each parameter that ``need`` asks for, None and a null pointer elsewhere."""
-        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip([call.x] + call.params, need)]
+        """(outs, GRADS struct): a fresh tensor for each input and each parameter that ``need`` asks for, None and a null pointer
+        elsewhere."""
+        outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(call.inputs + call.params, need)]
         d = self.GRADS()
-        for f, o in zip(("dx",) + tuple(self.FIELDS), outs):
+        for f, o in zip(self.INPUT_GRADS + tuple(self.FIELDS), outs):
             setattr(d, f, o.data_ptr() if o is not None else None)
         return outs, d
-
-    def _done(self, rc, which):
-        """Raises on a failed ``ns_*_forward`` / ``ns_*_backward``, else books its launches."""
-        _lib.check(rc, f"{self.ABI}_{which}")
-        n = getattr(self._lib, self.ABI + "_last_launches")()
-        self.launches += n
-        self.last_launches[which] = n

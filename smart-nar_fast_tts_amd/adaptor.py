@@ -23,31 +23,10 @@ import torch
 
 from . import _lib
 from . import workload as wl
-from ._train import aligned, guard
+from ._train import CountedModule, aligned, guard, need_gpu
 from .predictor import VariancePredictor
 
 LEVELS = ("phoneme_level", "frame_level")
-
-
-def _need_gpu(who, name, t):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise RuntimeError(f"{who}: {name} must live on the MI355X (there is no CPU path)")
-
-
-class _Counted(torch.nn.Module):
-    """Launch bookkeeping of a module over ``ns_va_*``: ``launches`` so far and ``last_launches`` per direction, as the C side counted."""
-
-    def __init__(self):
-        super().__init__()
-        self._lib = _lib.load()
-        self.launches = 0
-        self.last_launches = {}
-
-    def _done(self, rc, what, which, add=False):
-        _lib.check(rc, what)
-        n = self._lib.ns_va_last_launches()
-        self.launches += n
-        self.last_launches[which] = n + (self.last_launches.get(which, 0) if add else 0)
 
 
 class _EmbedFunction(torch.autograd.Function):
@@ -65,7 +44,7 @@ class _EmbedFunction(torch.autograd.Function):
         return None, dx, None, None, dw
 
 
-class VarianceEmbedding(_Counted):
+class VarianceEmbedding(CountedModule):
     """``x + weight[torch.bucketize(target, bins)]``: the reference's ``nn.Embedding(n_bins, d)`` (state-dict key ``weight``) together with
     the bucketize in front of it and the add behind it (model/modules.py:80-100, 121-149), one launch forward.
 
@@ -74,6 +53,8 @@ class VarianceEmbedding(_Counted):
     target too, and its gradient row is summed into the table.  One autograd Function; ``target`` and ``bins`` take no gradient, the
     gradient of ``x`` is ``grad_output`` itself, and the table's gradient is two launches (float64 sums in a fixed order, rounded once)
     that a frozen table (``weight.requires_grad == False``) does not make.  Refuses ``d % 4 != 0`` and ``n_bins`` outside [2, 2048]."""
+
+    ABI = "ns_va"
 
     def __init__(self, n_bins, d):
         super().__init__()
@@ -84,7 +65,7 @@ class VarianceEmbedding(_Counted):
         self.weight = torch.nn.Parameter(torch.randn(self.n_bins, self.d))  # nn.Embedding's initialisation
 
     def forward(self, x, target, bins):
-        _need_gpu("VarianceEmbedding", "x", x)
+        need_gpu("VarianceEmbedding", "x", x)
         dev, lead = x.device, tuple(x.shape[:-1])
         if x.dtype != torch.float32 or x.dim() < 2 or x.shape[-1] != self.d or x.numel() == 0:
             raise ValueError(f"x must be a non-empty float32 [..., {self.d}] tensor, got {x.dtype} {tuple(x.shape)}")
@@ -106,7 +87,7 @@ class VarianceEmbedding(_Counted):
             y = torch.empty_like(xa)
             idx = torch.empty(tuple(x.shape[:-1]), dtype=torch.int32, device=dev)
             self._done(self._lib.ns_va_op_embed_fwd(_lib.ptr(xa), _lib.ptr(ta), _lib.ptr(ba), _lib.ptr(wa), M, self.d, self.n_bins, _lib.ptr(y),
-                                                    _lib.ptr(idx), _lib.stream_ptr(dev)), "ns_va_op_embed_fwd", "forward")
+                                                    _lib.ptr(idx), _lib.stream_ptr(dev)), "forward", "ns_va_op_embed_fwd")
         return y, idx
 
     def _backward(self, g, idx):
@@ -122,7 +103,7 @@ class VarianceEmbedding(_Counted):
             ws = torch.empty(n, dtype=torch.uint8, device=dev)
             dw = torch.empty((self.n_bins, self.d), dtype=torch.float32, device=dev)
             self._done(self._lib.ns_va_op_embed_bwd(_lib.ptr(g), _lib.ptr(idx), M, self.d, self.n_bins, _lib.ptr(dw), _lib.ptr(ws), ws.numel(),
-                                                    _lib.stream_ptr(dev)), "ns_va_op_embed_bwd", "backward")
+                                                    _lib.stream_ptr(dev)), "backward", "ns_va_op_embed_bwd")
         return dw
 
 
@@ -141,7 +122,7 @@ class _RegulateFunction(torch.autograd.Function):
         return None, dx, None, None
 
 
-class LengthRegulator(_Counted):
+class LengthRegulator(CountedModule):
     """The reference's ``LengthRegulator`` (model/modules.py:195-230): ``forward(x [B, L, d], duration [B, L], max_len) -> (out [B, max_len, d],
     mel_len [B] int64)``.  Phoneme ``l`` of utterance ``b`` is repeated ``max(duration[b, l], 0)`` times; frames at or past an utterance's
     total are ``+0.0``; frames at or past ``max_len`` are dropped, while ``mel_len`` stays the uncropped total, as the reference returns it.
@@ -152,8 +133,10 @@ class LengthRegulator(_Counted):
     in float64, rounded once; a phoneme of duration 0 gets ``+0.0`` and frames past an utterance's total are never read.  ``duration``
     is an integer tensor (a floating one is truncated, as the reference's ``int()`` does) and takes no gradient."""
 
+    ABI = "ns_va"
+
     def forward(self, x, duration, max_len=None):
-        _need_gpu("LengthRegulator", "x", x)
+        need_gpu("LengthRegulator", "x", x)
         if x.dtype != torch.float32 or x.dim() != 3 or x.numel() == 0 or x.shape[2] % 4 != 0:
             raise ValueError(f"x must be a non-empty float32 [B, L, d] tensor with d a multiple of 4, got {x.dtype} {tuple(x.shape)}")
         if tuple(duration.shape) != tuple(x.shape[:2]) or duration.device != x.device or duration.dtype == torch.bool:
@@ -175,14 +158,14 @@ class LengthRegulator(_Counted):
             st = _lib.stream_ptr(dev)
             first = _lib.ptr(da)
             if T is None:  # the scan alone, then the one read of the batch maximum
-                self._done(self._lib.ns_va_op_lr_fwd(None, first, B, L, D, 0, None, _lib.ptr(cum), _lib.ptr(mel_len), st), "ns_va_op_lr_fwd", "forward")
+                self._done(self._lib.ns_va_op_lr_fwd(None, first, B, L, D, 0, None, _lib.ptr(cum), _lib.ptr(mel_len), st), "forward", "ns_va_op_lr_fwd")
                 T = int(mel_len.max().item())
                 if T <= 0:
                     raise ValueError("LengthRegulator: every duration is zero and max_len is None: there is no frame to pad to")
                 first = None
             out = torch.empty((B, T, D), dtype=torch.float32, device=dev)
             self._done(self._lib.ns_va_op_lr_fwd(_lib.ptr(xa), first, B, L, D, T, _lib.ptr(out), _lib.ptr(cum), _lib.ptr(mel_len), st),
-                       "ns_va_op_lr_fwd", "forward", add=first is None)
+                       "forward", "ns_va_op_lr_fwd", add=first is None)
         return out, mel_len, cum
 
     def _backward(self, g, cum, dims):
@@ -194,7 +177,7 @@ class LengthRegulator(_Counted):
         with guard(dev):
             dx = torch.empty((B, L, D), dtype=torch.float32, device=dev)
             self._done(self._lib.ns_va_op_lr_bwd(_lib.ptr(g), _lib.ptr(cum), B, L, D, g.shape[1], _lib.ptr(dx), _lib.stream_ptr(dev)),
-                       "ns_va_op_lr_bwd", "backward")
+                       "backward", "ns_va_op_lr_bwd")
         return dx
 
 
@@ -259,7 +242,7 @@ class VarianceAdaptor(torch.nn.Module):
                                       "be given.  Synthesis from the model's own predictions is model.FastSpeech2Align (the inference path).")
         if (p_control, e_control, d_control) != (1.0, 1.0, 1.0):
             raise NotImplementedError("the controls scale predictions on the inference path only (model.FastSpeech2Align); with targets given they must be 1.0")
-        _need_gpu("VarianceAdaptor", "x", x)
+        need_gpu("VarianceAdaptor", "x", x)
         km = keep_masks or {}
         log_duration_prediction = self.duration_predictor(x, src_mask, keep_masks=km.get("duration"))
         pitch_prediction = energy_prediction = None

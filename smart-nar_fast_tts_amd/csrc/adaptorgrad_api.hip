@@ -33,12 +33,6 @@ int check_lr(const std::string& w, int B, int L, int D, int T, bool need_T) {
   if (need_T) NS_TRY(check_rows(w, "B * T", (long long)B * T, D));
   return 0;
 }
-
-int check_aligned(const std::string& w, std::initializer_list<NamedPtr> t) {
-  for (const NamedPtr& e : t)
-    if (misaligned(e.p, e.align)) return api_fail(w + e.name + " must be " + std::to_string(e.align) + "-byte aligned");
-  return 0;
-}
 }  // namespace
 
 extern "C" int ns_va_abi_version(void) { return NS_VA_ABI_VERSION; }

@@ -4,7 +4,6 @@
 //   k_ag_bwd_kv         owns 128 keys of one (b, h), sweeps the query tiles: dK and dV; reads the D that k_ag_bwd_q left
 //   k_ag_row_forward    z = u * keep / (1 - p) + x, y = LayerNorm(z)  (row kernels over train_rows.h, as predgrad.hip's)
 //   k_ag_row_backward   LayerNorm backward from z: dz, du = dz * keep / (1 - p), float64 column partials (d_ln_g, d_ln_b, d_bfc)
-//   k_ag_colsum3        column partials of the three thirds of dqkv (d_bq, d_bk, d_bv), in the layout k_pg_col_final sums
 //   k_ag_pack           Wq | Wk | Wv -> one [3d][d] weight + [3d] bias (forward) and the transposed forms the data gradients read
 // Both backward kernels recompute S = Q K^T and dP = dO V^T for their own tiles on the fp32 matrix cores (v_mfma_f32_32x32x2_f32);
 // the [S, S] matrices never reach memory.  No atomics, no host reads; every sum has one order that depends on the shape alone.
@@ -337,22 +336,6 @@ hipError_t launch_ag_row_backward(const AgRowBackward& a, hipStream_t st) {
   const dim3 grid(pg_row_blocks(a.M)), block(256);
   if (a.F == 256) hipLaunchKernelGGL(k_ag_row_backward<1>, grid, block, 0, st, a);
   else hipLaunchKernelGGL(k_ag_row_backward<2>, grid, block, 0, st, a);
-  return hipGetLastError();
-}
-
-// part[blk][third][col] = sum of rows [64 blk, 64 blk + 64) of dqkv[:, third * d + col], ascending
-__global__ __launch_bounds__(256) void k_ag_colsum3(const float* __restrict__ dqkv, int M, int d, double* __restrict__ part) {
-  const int m0 = blockIdx.x * PG_ROW_BLOCK, m1 = min(M, m0 + PG_ROW_BLOCK), third = blockIdx.y;
-  for (int col = threadIdx.x; col < d; col += 256) {
-    double s = 0.0;
-    for (int m = m0; m < m1; ++m) s += (double)dqkv[(size_t)m * 3 * d + third * d + col];
-    part[((size_t)blockIdx.x * PG_SLOTS + third) * d + col] = s;
-  }
-}
-
-hipError_t launch_ag_colsum3(const float* dqkv, int M, int d, double* part, hipStream_t st) {
-  if (M <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_ag_colsum3, dim3(pg_row_blocks(M), 3), dim3(256), 0, st, dqkv, M, d, part);
   return hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 // No handle: the weights are the caller's live tensors in checkpoint layout, the workspace and the saved activations belong to the
 // caller.  Host-side only; every argument is validated before the first HIP call.  The four Linears run on what predgrad.hip and
 // gemm_conv.hip already have (launch_conv_gemm at KW = 1, launch_pg_wgrad, launch_pg_col_final); the launch counts are stated in the
-// header.  The checks, the counted GEMM launch and the column-partial finish it shares with predgrad_api.hip are train_api.h's.
+// header.  The checks, the parameter table, the size queries, the counted GEMM launch and the column-partial finish it shares with the
+// other training ABIs are train_api.h's.
 #include "../../include/nar_fs2.h"
 #include "train_api.h"
 
@@ -13,6 +14,7 @@ static_assert(sizeof(ns_ag_weights) == 10 * sizeof(void*) && sizeof(ns_ag_grads)
 
 namespace {
 thread_local int t_launches = 0;
+thread_local const Counted counted{"ns_ag", &t_launches};
 
 struct Ws {  // the workspace of one shape, carved in this order
   float *wp, *bp, *wt, *wfct;  // [3d][d] and [3d] (forward), [d][3d] and [d][d] (data gradients)
@@ -49,32 +51,16 @@ int carve(const ns_ag_shape& s, void* base, Ws* ws, size_t* bytes, const std::st
   return 0;
 }
 
-// the ten parameters of ns_ag_weights or ns_ag_grads, in ABI order
-template <class T>
-std::vector<NamedPtr> ten(const T& k) {
-  return {{"wq", k.wq}, {"bq", k.bq}, {"wk", k.wk}, {"bk", k.bk}, {"wv", k.wv}, {"bv", k.bv}, {"wfc", k.wfc}, {"bfc", k.bfc}, {"ln_g", k.ln_g},
-          {"ln_b", k.ln_b}};
-}
+int check_shape(const ns_ag_shape& s, const std::string& w) { return check_dims(s.B, s.S, s.d, s.H, w); }
 
-// Y [M, N] = X [M, K] W[N][K]^T + bias + resid through the forward's dispatch; counts its launches
-int gemm(const float* X, const float* W, const float* bias, const float* resid, float* Y, int M, int S, int N, int K, hipStream_t st) {
-  ConvGemm p = conv_gemm_args(X, W, bias, Y, M, S, N, K, 1, 0, ACT_NONE);
-  p.resid = resid; p.ldr = N;
-  return counted_conv_gemm(p, "ns_ag", &t_launches, st);
-}
-
-int common(const char* who, const ns_ag_shape* s, const ns_ag_weights* k, const float* x, const int64_t* lens, const uint8_t* keep, float p_drop,
+// what ns_ag_forward and ns_ag_backward check alike, in this order, and the carved workspace
+int common(const std::string& w, const ns_ag_shape* s, const ns_ag_weights* k, const float* x, const int64_t* lens, const uint8_t* keep, float p_drop,
            const void* saved, void* ws_mem, size_t ws_bytes, Ws* ws) {
-  const std::string w = std::string(who) + ": ";
-  NS_TRY(check_dims(s->B, s->S, s->d, s->H, w));
-  NS_TRY(check_weights(ten(*k), w));
+  NS_TRY(check_shape(*s, w));
+  NS_TRY(check_weights(attn_params(*k), w));
   NS_TRY(check_drop({keep}, p_drop, w));
-  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
-  if ((uintptr_t)lens & 7) return api_fail(w + "lens must be 8-byte aligned");
-  size_t need = 0;
-  NS_TRY(carve(*s, ws_mem, ws, &need, w));
-  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_ag_ws_bytes)");
-  return 0;
+  NS_TRY(check_aligned(w, {{"x", x}, {"saved", saved}, {"the workspace", ws_mem}, {"lens", lens, 8}}));
+  return carve_checked(carve, counted.abi, *s, ws_mem, ws_bytes, ws, w);
 }
 }  // namespace
 
@@ -82,28 +68,23 @@ extern "C" int ns_ag_abi_version(void) { return NS_AG_ABI_VERSION; }
 extern "C" int ns_ag_last_launches(void) { return t_launches; }
 
 extern "C" size_t ns_ag_ws_bytes(const ns_ag_shape* s) {
-  const std::string w = "ns_ag_ws_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(s->B, s->S, s->d, s->H, w)) return 0;
-  Ws ws; size_t bytes = 0;
-  if (carve(*s, nullptr, &ws, &bytes, w)) return 0;
-  return bytes;
+  return size_query("ns_ag_ws_bytes", s, check_shape, [](const ns_ag_shape& s, const std::string& w) { return carved_bytes(carve, s, w); });
 }
 
 extern "C" size_t ns_ag_saved_bytes(const ns_ag_shape* s) {
-  const std::string w = "ns_ag_saved_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(s->B, s->S, s->d, s->H, w)) return 0;
-  return ((size_t)5 * s->B * s->S * s->d + (size_t)s->B * s->H * s->S) * sizeof(float);
+  return size_query("ns_ag_saved_bytes", s, check_shape, [](const ns_ag_shape& s, const std::string&) {
+    return ((size_t)5 * s.B * s.S * s.d + (size_t)s.B * s.H * s.S) * sizeof(float);
+  });
 }
 
 extern "C" int ns_ag_forward(const ns_ag_shape* s, const ns_ag_weights* k, const float* x, const int64_t* lens, const uint8_t* keep, float p_drop,
                              float* y, void* saved, void* ws_mem, size_t ws_bytes, void* stream) {
+  const std::string w = "ns_ag_forward: ";
   t_launches = 0;
-  if (!s || !k || !x || !y || !ws_mem) return api_fail("ns_ag_forward: null argument");
-  if (misaligned(y)) return api_fail("ns_ag_forward: y must be 16-byte aligned");
+  if (!s || !k || !x || !y || !ws_mem) return api_fail(w + "null argument");
+  NS_TRY(check_aligned(w, {{"y", y}}));
   Ws ws;
-  NS_TRY(common("ns_ag_forward", s, k, x, lens, keep, p_drop, saved, ws_mem, ws_bytes, &ws));
+  NS_TRY(common(w, s, k, x, lens, keep, p_drop, saved, ws_mem, ws_bytes, &ws));
   const int M = s->B * s->S, d = s->d, H = s->H, dk = d / H;
   const size_t md = (size_t)M * d;
   float* qkv = saved ? (float*)saved : ws.wide;
@@ -113,14 +94,14 @@ extern "C" int ns_ag_forward(const ns_ag_shape* s, const ns_ag_weights* k, const
   hipStream_t st = (hipStream_t)stream;
   NS_HIP(launch_ag_pack(AgPack{k->wq, k->wk, k->wv, k->bq, k->bk, k->bv, k->wfc, ws.wp, ws.bp, nullptr, nullptr, d}, st));
   ++t_launches;
-  NS_TRY(gemm(x, ws.wp, ws.bp, nullptr, qkv, M, s->S, 3 * d, d, st));
+  NS_TRY(counted.gemm(x, ws.wp, ws.bp, nullptr, qkv, M, s->S, 3 * d, d, st));
   NS_HIP(launch_attention(qkv, (const long long*)lens, s->B, s->S, H, dk, ctx, nullptr, 0, nullptr, st));
   ++t_launches;
   if (lse) {
     NS_HIP(launch_ag_lse(qkv, (const long long*)lens, s->B, s->S, H, dk, lse, st));
     ++t_launches;
   }
-  NS_TRY(gemm(ctx, k->wfc, k->bfc, nullptr, ws.a, M, s->S, d, d, st));
+  NS_TRY(counted.gemm(ctx, k->wfc, k->bfc, nullptr, ws.a, M, s->S, d, d, st));
   NS_HIP(launch_ag_row_forward(ws.a, x, keep, 1.f / (1.f - p_drop), k->ln_g, k->ln_b, z, y, M, d, st));
   ++t_launches;
   return 0;
@@ -131,13 +112,13 @@ extern "C" int ns_ag_backward(const ns_ag_shape* s, const ns_ag_weights* k, cons
   const std::string w = "ns_ag_backward: ";
   t_launches = 0;
   if (!s || !k || !x || !saved || !g || !dg || !ws_mem) return api_fail(w + "null argument");
-  if (misaligned(g)) return api_fail(w + "g must be 16-byte aligned");
-  std::vector<NamedPtr> outs = ten(*dg);
+  NS_TRY(check_aligned(w, {{"g", g}}));
+  std::vector<NamedPtr> outs = attn_params(*dg);
   outs.push_back({"dx", dg->dx});
   bool any = false;
   NS_TRY(check_grads(outs, w, &any));
   Ws ws;
-  NS_TRY(common("ns_ag_backward", s, k, x, lens, keep, p_drop, saved, ws_mem, ws_bytes, &ws));
+  NS_TRY(common(w, s, k, x, lens, keep, p_drop, saved, ws_mem, ws_bytes, &ws));
   if (!any) return 0;
   const int M = s->B * s->S, d = s->d, H = s->H, dk = d / H, nblk = pg_row_blocks(M);
   const size_t md = (size_t)M * d;
@@ -164,7 +145,7 @@ extern "C" int ns_ag_backward(const ns_ag_shape* s, const ns_ag_weights* k, cons
     t_launches += 2;
   }
   if (upstream) {
-    NS_TRY(gemm(du, ws.wfct, nullptr, nullptr, dctx, M, s->S, d, d, st));
+    NS_TRY(counted.gemm(du, ws.wfct, nullptr, nullptr, dctx, M, s->S, d, d, st));
     NS_HIP(launch_ag_attention_backward(qkv, ctx, lse, dctx, (const long long*)lens, s->B, s->S, H, dk, ws.stat, dqkv, st));
     t_launches += 2;
     float* dw[3] = {dg->wq, dg->wk, dg->wv};
@@ -174,12 +155,12 @@ extern "C" int ns_ag_backward(const ns_ag_shape* s, const ns_ag_weights* k, cons
         t_launches += 2;
       }
     if (bias3) {
-      NS_HIP(launch_ag_colsum3(dqkv, M, d, ws.colpart, st));
+      NS_HIP(launch_pg_colsum(dqkv, M, d, 3, ws.colpart, st));
       ++t_launches;
     }
-    if (dg->dx) NS_TRY(gemm(dqkv, ws.wt, nullptr, dz, dg->dx, M, s->S, d, 3 * d, st));
+    if (dg->dx) NS_TRY(counted.gemm(dqkv, ws.wt, nullptr, dz, dg->dx, M, s->S, d, 3 * d, st));
   }
-  return col_finish(ws.colpart, nblk, d, {dg->bq, dg->bk, dg->bv}, {dg->ln_g, dg->ln_b, dg->bfc}, &t_launches, st);
+  return counted.col_finish(ws.colpart, nblk, d, {dg->bq, dg->bk, dg->bv}, {dg->ln_g, dg->ln_b, dg->bfc}, st);
 }
 
 extern "C" int ns_ag_op_lse(const float* qkv, const int64_t* lens, int B, int S, int d, int H, float* lse, void* stream) {
@@ -187,7 +168,7 @@ extern "C" int ns_ag_op_lse(const float* qkv, const int64_t* lens, int B, int S,
   t_launches = 0;
   if (!qkv || !lse) return api_fail(w + "null argument");
   NS_TRY(check_dims(B, S, d, H, w));
-  if (misaligned(qkv) || ((uintptr_t)lse & 3) || ((uintptr_t)lens & 7)) return api_fail(w + "qkv must be 16-byte aligned (lens: 8, lse: 4)");
+  NS_TRY(check_aligned(w, {{"qkv", qkv}, {"lse", lse, 4}, {"lens", lens, 8}}));
   NS_HIP(launch_ag_lse(qkv, (const long long*)lens, B, S, H, d / H, lse, (hipStream_t)stream));
   ++t_launches;
   return 0;
@@ -199,10 +180,7 @@ extern "C" int ns_ag_op_attention_backward(const float* qkv, const float* ctx, c
   t_launches = 0;
   if (!qkv || !ctx || !lse || !dctx || !dqkv || !ws_mem) return api_fail(w + "null argument");
   NS_TRY(check_dims(B, S, d, H, w));
-  const void* al[] = {qkv, ctx, dctx, dqkv, ws_mem};
-  for (const void* p : al)
-    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
-  if (((uintptr_t)lse & 3) || ((uintptr_t)lens & 7)) return api_fail(w + "lse must be 4-byte, lens 8-byte aligned");
+  NS_TRY(check_aligned(w, {{"qkv", qkv}, {"ctx", ctx}, {"dctx", dctx}, {"dqkv", dqkv}, {"the workspace", ws_mem}, {"lse", lse, 4}, {"lens", lens, 8}}));
   const size_t need = (size_t)B * H * S * sizeof(float);
   if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
   NS_HIP(launch_ag_attention_backward(qkv, ctx, lse, dctx, (const long long*)lens, B, S, H, d / H, (float*)ws_mem, dqkv, (hipStream_t)stream));
@@ -219,14 +197,13 @@ extern "C" int ns_ag_op_row_backward(const float* dy, const float* z, const floa
   if (d != 256 && d != 512) return api_fail(w + "d must be 256 or 512, got " + std::to_string(d));
   if ((long long)M * d >= (1ll << 31)) return api_fail(w + "problem too large");
   NS_TRY(check_drop({keep}, p_drop, w));
-  const void* al[] = {dy, z, ln_g, dz, du, d_ln_g, d_ln_b, d_bfc, ws_mem};
-  for (const void* p : al)
-    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
+  NS_TRY(check_aligned(w, {{"dy", dy}, {"z", z}, {"ln_g", ln_g}, {"dz", dz}, {"du", du}, {"d_ln_g", d_ln_g}, {"d_ln_b", d_ln_b}, {"d_bfc", d_bfc},
+                           {"the workspace", ws_mem}}));
   const size_t need = (size_t)pg_row_blocks(M) * PG_SLOTS * d * sizeof(double);
   if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)ws_mem;
   NS_HIP(launch_ag_row_backward(ag_row_backward_args(M, d, p_drop, dy, z, ln_g, keep, dz, du, part), st));
   ++t_launches;
-  return col_finish(part, pg_row_blocks(M), d, {d_ln_g, d_ln_b, d_bfc}, {}, &t_launches, st);
+  return counted.col_finish(part, pg_row_blocks(M), d, {d_ln_g, d_ln_b, d_bfc}, {}, st);
 }

@@ -376,8 +376,9 @@ struct PgRowBackward {
   float* dz; double* part;
 };
 hipError_t launch_pg_row_backward(const PgRowBackward& a, hipStream_t st);
-// part[blk][0][:] = column sums of rows [64 blk, 64 blk + 64) of dz [M, F]
-hipError_t launch_pg_colsum(const float* dz, int M, int F, double* part, hipStream_t st);
+// part[blk][slot][:] = column sums of rows [64 blk, 64 blk + 64) of src[:, slot * F .. slot * F + F), src rows of parts * F floats,
+// parts in [1, PG_SLOTS]: a matrix alone (1), dQ | dK | dV of the self-attention (3), dQ (1) and dK | dV (2) of the cross-attention
+hipError_t launch_pg_colsum(const float* src, int M, int F, int parts, double* part, hipStream_t st);
 // out[i][:] = sum over blocks, ascending, of part[i / PG_SLOTS][blk][i % PG_SLOTS][:] for the up to 2 * PG_SLOTS non-null outputs
 // (slot 4 is a scalar: column 0 only); part holds `stages` arrays of [nblk][PG_SLOTS][F] doubles
 struct PgColFinal { float* out[2 * PG_SLOTS]; };
@@ -401,8 +402,6 @@ struct AgRowBackward {
   float *dz, *du; double* part;
 };
 hipError_t launch_ag_row_backward(const AgRowBackward& a, hipStream_t st);
-// part[blk][third][:] = column sums of rows [64 blk, 64 blk + 64) of dqkv[:, third * d .. third * d + d): launch_pg_col_final at F = d
-hipError_t launch_ag_colsum3(const float* dqkv, int M, int d, double* part, hipStream_t st);
 // one launch: wp [3d][d] = Wq | Wk | Wv and bp [3d] (the forward's form), wt [d][3d] = wp^T and wfct [d][d] = Wfc^T (the data
 // gradients' form); each output nullable
 struct AgPack { const float *wq, *wk, *wv, *bq, *bk, *bv, *wfc; float *wp, *bp, *wt, *wfct; int d; };
@@ -417,8 +416,6 @@ int xg_kv_splits(int B, int H, int T, int L);
 hipError_t launch_xg_attention_backward(const float* q, const float* kv, const float* ctx, const float* attn, const float* dctx, const float* dattn,
                                         const long long* lens, int B, int T, int L, int H, int dk, int nsplit, float* D, float* partial, float* dq,
                                         float* dkv, hipStream_t st);
-// part[blk][third][:] = column sums of rows [64 blk, 64 blk + 64) of src[:, third * d .. third * d + d), src rows of thirds * d floats
-hipError_t launch_xg_colsum(const float* src, int M, int d, int thirds, double* part, hipStream_t st);
 // one launch: wkv [2d][d] = Wk | Wv and bkv [2d] (the forward's form), wkvt [d][2d] = wkv^T, wqt = Wq^T and wfct = Wfc^T [d][d] (the
 // data gradients' form); each output nullable
 struct XgPack { const float *wq, *wk, *wv, *bk, *bv, *wfc; float *wkv, *bkv, *wkvt, *wqt, *wfct; int d; };

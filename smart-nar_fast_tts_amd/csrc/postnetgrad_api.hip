@@ -14,6 +14,7 @@ static_assert(NS_PN_MAX_LAYERS == PN_MAX_LAYERS, "layer count");
 
 namespace {
 thread_local int t_launches = 0;
+thread_local const Counted counted{"ns_pn", &t_launches};
 
 struct Ws {  // the workspace of one shape, carved in this order
   float* wp[PN_MAX_LAYERS];       // packed weights, the forward's form
@@ -87,62 +88,19 @@ Saved saved_pointers(const ns_pn_shape& s, void* saved) {
   return v;
 }
 
-int check_keep(const uint8_t* const* keep, int n, float p, const std::string& w) {
-  if (!(p >= 0.f && p < 1.f)) return api_fail(w + "p_drop must lie in [0, 1)");
-  bool all = keep != nullptr, any = false, skew = false;
-  for (int i = 0; keep && i < n; ++i) { all = all && keep[i]; any = any || keep[i]; skew = skew || misaligned(keep[i]); }
-  if (p > 0.f && !all) return api_fail(w + "p_drop > 0 needs all n keep-masks");
-  if (p == 0.f && any) return api_fail(w + "keep-masks given although p_drop == 0");
-  if (skew) return api_fail(w + "keep-masks must be 16-byte aligned");
-  return 0;
-}
-
-int check_layers(const ns_pn_shape& s, const ns_pn_weights& k, const std::string& w) {
-  for (int i = 0; i < s.n; ++i) {
-    const ns_pn_layer& l = k.layer[i];
-    const std::string at = "weights->layer[" + std::to_string(i) + "].";
-    const NamedPtr t[] = {{"w", l.w}, {"b", l.b}, {"gamma", l.gamma}, {"beta", l.beta}, {"running_mean", l.running_mean},
-                          {"running_var", l.running_var}, {"num_batches_tracked", l.num_batches_tracked, 8}};
-    for (const NamedPtr& e : t) {
-      if (!e.p) return api_fail(w + "null " + at + e.name);
-      if (misaligned(e.p, e.align)) return api_fail(w + at + e.name + " must be " + std::to_string(e.align) + "-byte aligned");
-    }
-  }
-  return 0;
-}
-
-// what ns_pn_forward and ns_pn_backward check alike, in this order; `io` is y or g
+// what ns_pn_forward and ns_pn_backward check alike, in this order; `io` names y or g
 int common(const std::string& w, const ns_pn_shape* s, const ns_pn_weights* k, int training, const float* x, const uint8_t* const* keep, float p_drop,
-           const void* saved, const void* ws_mem, const float* io) {
+           const void* saved, const void* ws_mem, NamedPtr io) {
   NS_TRY(check_dims(*s, w));
   if (training && (long long)s->B * s->T == 1) return api_fail(w + "training needs more than one row: the batch variance of B * T == 1 value per channel is undefined");
-  NS_TRY(check_layers(*s, *k, w));
-  NS_TRY(check_keep(keep, s->n, p_drop, w));
-  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem) || misaligned(io)) return api_fail(w + "x, y or g, saved and the workspace must be 16-byte aligned");
-  return 0;
-}
-
-int carve_checked(const ns_pn_shape& s, void* ws_mem, size_t ws_bytes, Ws* ws, const std::string& w) {
-  size_t need = 0;
-  NS_TRY(carve(s, ws_mem, ws, &need, w));
-  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_pn_ws_bytes)");
-  return 0;
-}
-
-// Y [M, N] = conv(X [M, Cin] at row stride ldx, W packed [N][KW * Cin]) + bias through the forward's dispatch; counts its launches
-int conv(const float* X, int ldx, const float* W, const float* bias, float* Y, int M, int S, int N, int Cin, int KW, int pad, hipStream_t st) {
-  ConvGemm p = conv_gemm_args(X, W, bias, Y, M, S, N, Cin, KW, pad, ACT_NONE);
-  p.ldx = ldx;
-  return counted_conv_gemm(p, "ns_pn", &t_launches, st);
-}
-
-int pack(const PgPack* v, int count, hipStream_t st) {
-  const PgPack none{nullptr, nullptr, nullptr, 0, 0, 0};
-  for (int i = 0; i < count; i += 2) {
-    NS_HIP(launch_pg_pack(v[i], i + 1 < count ? v[i + 1] : none, st));
-    ++t_launches;
+  for (int i = 0; i < s->n; ++i) {
+    const ns_pn_layer& l = k->layer[i];
+    NS_TRY(check_weights({{"w", l.w}, {"b", l.b}, {"gamma", l.gamma}, {"beta", l.beta}, {"running_mean", l.running_mean},
+                          {"running_var", l.running_var}, {"num_batches_tracked", l.num_batches_tracked, 8}},
+                         w, "layer[" + std::to_string(i) + "]."));
   }
-  return 0;
+  NS_TRY(check_drop(keep, s->n, p_drop, w));
+  return check_aligned(w, {{"x", x}, {"saved", saved}, {"the workspace", ws_mem}, io});
 }
 
 // the weight gradient at the padded width: dz [M, 128] with zero columns [N, 128) -> dwpad [128][Cin][KW] -> dW = its first N rows
@@ -155,14 +113,12 @@ int wgrad_narrow(const float* dz, const float* X, int M, int S, int N, int Cin, 
   return 0;
 }
 
-int check_op(const std::string& w, int M, int C, float p_drop, const uint8_t* keep, std::initializer_list<const void*> al) {
+int check_op(const std::string& w, int M, int C, float p_drop, const uint8_t* keep, std::initializer_list<NamedPtr> al) {
   if (M <= 0) return api_fail(w + "M must be positive, got " + std::to_string(M));
   if (C <= 0 || C % 16 != 0 || C > 512) return api_fail(w + "C must be a multiple of 16 up to 512, got " + std::to_string(C));
   if ((long long)M * C >= (1ll << 31)) return api_fail(w + "problem too large: M * C must stay below 2^31");
   NS_TRY(check_drop({keep}, p_drop, w));
-  for (const void* p : al)
-    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
-  return 0;
+  return check_aligned(w, al);
 }
 }  // namespace
 
@@ -170,19 +126,13 @@ extern "C" int ns_pn_abi_version(void) { return NS_PN_ABI_VERSION; }
 extern "C" int ns_pn_last_launches(void) { return t_launches; }
 
 extern "C" size_t ns_pn_ws_bytes(const ns_pn_shape* s) {
-  const std::string w = "ns_pn_ws_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(*s, w)) return 0;
-  Ws ws; size_t bytes = 0;
-  if (carve(*s, nullptr, &ws, &bytes, w)) return 0;
-  return bytes;
+  return size_query("ns_pn_ws_bytes", s, check_dims, [](const ns_pn_shape& s, const std::string& w) { return carved_bytes(carve, s, w); });
 }
 
 extern "C" size_t ns_pn_saved_bytes(const ns_pn_shape* s) {
-  const std::string w = "ns_pn_saved_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(*s, w)) return 0;
-  return saved_floats(*s) * sizeof(float) + (size_t)s->n * 2 * s->emb * sizeof(double);
+  return size_query("ns_pn_saved_bytes", s, check_dims, [](const ns_pn_shape& s, const std::string&) {
+    return saved_floats(s) * sizeof(float) + (size_t)s.n * 2 * s.emb * sizeof(double);
+  });
 }
 
 extern "C" int ns_pn_forward(const ns_pn_shape* s, const ns_pn_weights* k, int training, const float* x, const uint8_t* const* keep, float p_drop,
@@ -190,9 +140,9 @@ extern "C" int ns_pn_forward(const ns_pn_shape* s, const ns_pn_weights* k, int t
   const std::string w = "ns_pn_forward: ";
   t_launches = 0;
   if (!s || !k || !x || !y || !ws_mem) return api_fail(w + "null argument");
-  NS_TRY(common(w, s, k, training, x, keep, p_drop, saved, ws_mem, y));
+  NS_TRY(common(w, s, k, training, x, keep, p_drop, saved, ws_mem, {"y", y}));
   Ws ws;
-  NS_TRY(carve_checked(*s, ws_mem, ws_bytes, &ws, w));
+  NS_TRY(carve_checked(carve, counted.abi, *s, ws_mem, ws_bytes, &ws, w));
   const int M = s->B * s->T, K = s->K, n = s->n, pad = (K - 1) / 2, nblk = pn_row_blocks(M);
   const float scale = 1.f / (1.f - p_drop);
   hipStream_t st = (hipStream_t)stream;
@@ -200,7 +150,7 @@ extern "C" int ns_pn_forward(const ns_pn_shape* s, const ns_pn_weights* k, int t
   if (saved) sv = saved_pointers(*s, saved);
   PgPack packs[PN_MAX_LAYERS];
   for (int i = 0; i < n; ++i) packs[i] = PgPack{k->layer[i].w, ws.wp[i], nullptr, cout_of(*s, i), cin_of(*s, i), K};
-  NS_TRY(pack(packs, n, st));
+  NS_TRY(counted.pack(packs, n, st));
   const float* h_in = x;
   for (int i = 0; i < n; ++i) {
     const ns_pn_layer& l = k->layer[i];
@@ -208,7 +158,7 @@ extern "C" int ns_pn_forward(const ns_pn_shape* s, const ns_pn_weights* k, int t
     float* u = saved ? sv.u[i] : ws.a;
     float* h = last ? y : (saved ? sv.h[i] : ws.b);
     double* stats = saved ? sv.stats[i] : ws.stats + (size_t)i * 2 * s->emb;
-    NS_TRY(conv(h_in, ci, ws.wp[i], l.b, u, M, s->T, co, ci, K, pad, st));
+    NS_TRY(counted.conv(h_in, ci, ws.wp[i], l.b, nullptr, u, M, s->T, co, ci, K, pad, ACT_NONE, st));
     PnFinish fin;
     memset(&fin, 0, sizeof(fin));
     fin.mode = training ? PN_FIN_TRAIN : PN_FIN_EVAL; fin.nblk = nblk; fin.C = co; fin.M = M; fin.part = ws.colpart; fin.stats = stats;
@@ -231,7 +181,7 @@ extern "C" int ns_pn_backward(const ns_pn_shape* s, const ns_pn_weights* k, int 
   const std::string w = "ns_pn_backward: ";
   t_launches = 0;
   if (!s || !k || !x || !saved || !g || !d || !ws_mem) return api_fail(w + "null argument");
-  NS_TRY(common(w, s, k, training, x, keep, p_drop, saved, ws_mem, g));
+  NS_TRY(common(w, s, k, training, x, keep, p_drop, saved, ws_mem, {"g", g}));
   const int n = s->n;
   std::vector<NamedPtr> outs = {{"dx", d->dx}};
   for (int i = 0; i < n; ++i) {
@@ -240,7 +190,7 @@ extern "C" int ns_pn_backward(const ns_pn_shape* s, const ns_pn_weights* k, int 
   }
   NS_TRY(check_grads(outs, w));
   Ws ws;
-  NS_TRY(carve_checked(*s, ws_mem, ws_bytes, &ws, w));
+  NS_TRY(carve_checked(carve, counted.abi, *s, ws_mem, ws_bytes, &ws, w));
   const int M = s->B * s->T, K = s->K, padT = K - 1 - (K - 1) / 2, nblk = pn_row_blocks(M);
   const float scale = 1.f / (1.f - p_drop);
   hipStream_t st = (hipStream_t)stream;
@@ -257,7 +207,7 @@ extern "C" int ns_pn_backward(const ns_pn_shape* s, const ns_pn_weights* k, int 
   int npack = 0;
   for (int i = 0; i < n; ++i)
     if (dgrad_wanted(i)) packs[npack++] = PgPack{k->layer[i].w, nullptr, ws.wt[i], cout_of(*s, i), cin_of(*s, i), K};
-  NS_TRY(pack(packs, npack, st));
+  NS_TRY(counted.pack(packs, npack, st));
 
   PnBiasFinish bias;
   memset(&bias, 0, sizeof(bias));
@@ -298,7 +248,7 @@ extern "C" int ns_pn_backward(const ns_pn_shape* s, const ns_pn_weights* k, int 
       }
     }
     if (dgrad_wanted(i)) {
-      NS_TRY(conv(ws.a, a.ldz, ws.wt[i], nullptr, i == 0 ? d->dx : ws.b, M, s->T, ci, co, K, padT, st));
+      NS_TRY(counted.conv(ws.a, a.ldz, ws.wt[i], nullptr, nullptr, i == 0 ? d->dx : ws.b, M, s->T, ci, co, K, padT, ACT_NONE, st));
       dh = ws.b;
     }
   }
@@ -318,8 +268,8 @@ extern "C" int ns_pn_op_stats(const float* u, int M, int C, int training, float*
   if (!stats || (training ? (!u || !ws_mem) : (!running_mean || !running_var))) return api_fail(w + "null argument");
   const bool buffers = running_mean || running_var || num_batches_tracked;
   if (training && buffers && !(running_mean && running_var && num_batches_tracked)) return api_fail(w + "the three buffers come together or not at all");
-  NS_TRY(check_op(w, M, C, 0.f, nullptr, {u, running_mean, running_var, stats, ws_mem}));
-  if (misaligned(num_batches_tracked, 8)) return api_fail(w + "num_batches_tracked must be 8-byte aligned");
+  NS_TRY(check_op(w, M, C, 0.f, nullptr, {{"u", u}, {"running_mean", running_mean}, {"running_var", running_var}, {"stats", stats}, {"the workspace", ws_mem},
+                                           {"num_batches_tracked", num_batches_tracked, 8}}));
   if (training && M == 1) return api_fail(w + "training needs more than one row");
   const size_t need = (size_t)pn_row_blocks(M) * 2 * C * sizeof(double);
   if (training && ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
@@ -342,7 +292,7 @@ extern "C" int ns_pn_op_apply(const float* u, const double* stats, const float* 
   const std::string w = "ns_pn_op_apply: ";
   t_launches = 0;
   if (!u || !stats || !gamma || !beta || !h) return api_fail(w + "null argument");
-  NS_TRY(check_op(w, M, C, p_drop, keep, {u, stats, gamma, beta, h}));
+  NS_TRY(check_op(w, M, C, p_drop, keep, {{"u", u}, {"stats", stats}, {"gamma", gamma}, {"beta", beta}, {"h", h}}));
   NS_HIP(launch_pn_apply(u, stats, gamma, beta, keep, 1.f / (1.f - p_drop), last != 0, M, C, h, (hipStream_t)stream));
   ++t_launches;
   return 0;
@@ -353,7 +303,8 @@ extern "C" int ns_pn_op_bwd_reduce(const float* dh, const float* u, const float*
   const std::string w = "ns_pn_op_bwd_reduce: ";
   t_launches = 0;
   if (!dh || !u || (!last && !h) || !stats || !d_gamma || !d_beta || !means || !ws_mem) return api_fail(w + "null argument");
-  NS_TRY(check_op(w, M, C, p_drop, keep, {dh, u, h, stats, d_gamma, d_beta, means, ws_mem}));
+  NS_TRY(check_op(w, M, C, p_drop, keep, {{"dh", dh}, {"u", u}, {"h", h}, {"stats", stats}, {"d_gamma", d_gamma}, {"d_beta", d_beta}, {"means", means},
+                                              {"the workspace", ws_mem}}));
   const size_t need = (size_t)pn_row_blocks(M) * 2 * C * sizeof(double);
   if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
   hipStream_t st = (hipStream_t)stream;
@@ -376,7 +327,8 @@ extern "C" int ns_pn_op_bwd_apply(const float* dh, const float* u, const float* 
   const std::string w = "ns_pn_op_bwd_apply: ";
   t_launches = 0;
   if (!dh || !u || (!last && !h) || !stats || !gamma || !dz || (d_bias && !ws_mem)) return api_fail(w + "null argument");
-  NS_TRY(check_op(w, M, C, p_drop, keep, {dh, u, h, stats, means, gamma, dz, d_bias, ws_mem}));
+  NS_TRY(check_op(w, M, C, p_drop, keep, {{"dh", dh}, {"u", u}, {"h", h}, {"stats", stats}, {"means", means}, {"gamma", gamma}, {"dz", dz},
+                                              {"d_bias", d_bias}, {"the workspace", ws_mem}}));
   if (ldz != C && !(ldz == PN_PAD_N && C < PN_PAD_N)) return api_fail(w + "ldz must be C, or 128 for C below 128, got " + std::to_string(ldz));
   const size_t need = (size_t)pn_row_blocks(M) * C * sizeof(double);
   if (d_bias && ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
@@ -407,7 +359,7 @@ extern "C" int ns_pn_op_wgrad_narrow(const float* dz, const float* X, int B, int
   if (N < 16 || N >= PN_PAD_N || N % 16 != 0) return api_fail(w + "N must be a multiple of 16 below 128, got " + std::to_string(N));
   if (Cin <= 0 || Cin % 4 != 0) return api_fail(w + "Cin must be a multiple of 4, got " + std::to_string(Cin));
   if (KW <= 0 || KW % 2 == 0) return api_fail(w + "K must be odd, got " + std::to_string(KW));
-  if (misaligned(dz) || misaligned(X) || misaligned(dW) || misaligned(ws_mem)) return api_fail(w + "every pointer must be 16-byte aligned");
+  NS_TRY(check_aligned(w, {{"dz", dz}, {"X", X}, {"dW", dW}, {"the workspace", ws_mem}}));
   if ((long long)B * S >= (1ll << 31)) return api_fail(w + "problem too large for the weight gradient's split");
   const int M = B * S;
   PgWgradPlan pl;

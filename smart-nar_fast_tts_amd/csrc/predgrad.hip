@@ -5,7 +5,9 @@
 //                                    transposed, tap-flipped [c][j*N + n] (both feed launch_conv_gemm, gemm_conv.hip)
 //   k_pg_row_forward                 LayerNorm * keep / (1 - p) of a row, and the Linear(F, 1) + masked_fill of the tail
 //   k_pg_row_backward                LayerNorm + ReLU backward of a row, per-workgroup column partials in float64
-//   k_pg_colsum / k_pg_col_final     column sums of a matrix alone; the fixed-order sum of the partials
+//   k_pg_colsum / k_pg_col_final     column sums of a matrix alone, of 1 to PG_SLOTS column parts per row (a bias gradient here, the
+//                                    thirds of dqkv in attngrad_api.hip, dQ and dK | dV in xattngrad_api.hip); the fixed-order sum of
+//                                    the partials
 // No atomics, no host reads; every sum has one order that depends on the shape alone.  The row kernels' float64 helpers (wave_sum,
 // row_stats, keep4, the column-partial flush) are train_rows.h's, shared with attngrad.hip's row kernels.
 #include "kernels.h"
@@ -334,18 +336,20 @@ hipError_t launch_pg_row_backward(const PgRowBackward& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void k_pg_colsum(const float* __restrict__ dz, int M, int F, double* __restrict__ part) {
-  const int m0 = blockIdx.x * PG_ROW_BLOCK, m1 = min(M, m0 + PG_ROW_BLOCK);
+// part[blk][slot][col] = sum of rows [64 blk, 64 blk + 64) of src[:, slot * F + col] (rows of `parts * F` floats), ascending
+__global__ __launch_bounds__(256) void k_pg_colsum(const float* __restrict__ src, int M, int F, int parts, double* __restrict__ part) {
+  const int m0 = blockIdx.x * PG_ROW_BLOCK, m1 = min(M, m0 + PG_ROW_BLOCK), slot = blockIdx.y;
   for (int col = threadIdx.x; col < F; col += 256) {
     double s = 0.0;
-    for (int m = m0; m < m1; ++m) s += (double)dz[(size_t)m * F + col];
-    part[(size_t)blockIdx.x * PG_SLOTS * F + col] = s;
+    for (int m = m0; m < m1; ++m) s += (double)src[(size_t)m * parts * F + slot * F + col];
+    part[((size_t)blockIdx.x * PG_SLOTS + slot) * F + col] = s;
   }
 }
 
-hipError_t launch_pg_colsum(const float* dz, int M, int F, double* part, hipStream_t st) {
+hipError_t launch_pg_colsum(const float* src, int M, int F, int parts, double* part, hipStream_t st) {
   if (M <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pg_colsum, dim3(pg_row_blocks(M)), dim3(256), 0, st, dz, M, F, part);
+  if (parts < 1 || parts > PG_SLOTS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pg_colsum, dim3(pg_row_blocks(M), parts), dim3(256), 0, st, src, M, F, parts, part);
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // C-ABI of the VariancePredictor training forward and backward (include/nar_fs2.h ns_pg_*; model/modules.py:233-286).  No handle:
 // the weights are the caller's live tensors in checkpoint layout, the workspace and the saved activations belong to the caller.
-// Host-side only; every argument is validated before the first HIP call.  The checks, the counted GEMM launch and the column-partial
-// finish it shares with attngrad_api.hip are train_api.h's.
+// Host-side only; every argument is validated before the first HIP call.  The checks, the size queries, the counted GEMM and pack
+// launches and the column-partial finish it shares with the other training ABIs are train_api.h's.
 #include "../../include/nar_fs2.h"
 #include "train_api.h"
 
@@ -12,6 +12,7 @@ static_assert(sizeof(ns_pg_weights) == 10 * sizeof(void*) && sizeof(ns_pg_grads)
 
 namespace {
 thread_local int t_launches = 0;
+thread_local const Counted counted{"ns_pg", &t_launches};
 
 struct Ws {  // the workspace of one shape, carved in this order
   float *w1p, *w1t, *w2p, *w2t;  // packed weights: forward form and data-gradient form of both convolutions
@@ -51,25 +52,16 @@ std::vector<NamedPtr> ten(const T& k) {
           {"wlin", k.wlin}, {"blin", k.blin, 4}};
 }
 
-// Y [M, N] = act(conv(X [M, Cin], W packed [N][KW * Cin]) + bias) through the forward's dispatch; counts its launches
-int conv(const float* X, const float* W, const float* bias, float* Y, int M, int S, int N, int Cin, int KW, int pad, int act, hipStream_t st) {
-  return counted_conv_gemm(conv_gemm_args(X, W, bias, Y, M, S, N, Cin, KW, pad, act), "ns_pg", &t_launches, st);
-}
+// the size queries take any Cin the weight gradient does; the layer itself needs a multiple of 16 (common)
+int check_shape(const ns_pg_shape& s, const std::string& w) { return check_dims(s.B, s.S, s.F, s.Cin, s.K, 4, w); }
 
-// what ns_pg_forward and ns_pg_backward check alike, in this order; `scalar` is pred or g, a [B, S] tensor of floats
+// what ns_pg_forward and ns_pg_backward check alike, in this order; `scalar` names pred or g, a [B, S] tensor of floats
 int common(const std::string& w, const ns_pg_shape* s, const ns_pg_weights* k, const float* x, const uint8_t* keep1, const uint8_t* keep2,
-           float p_drop, const void* saved, const void* ws_mem, const float* scalar) {
+           float p_drop, const void* saved, const void* ws_mem, NamedPtr scalar) {
   NS_TRY(check_dims(s->B, s->S, s->F, s->Cin, s->K, 16, w));
   NS_TRY(check_weights(ten(*k), w));
   NS_TRY(check_drop({keep1, keep2}, p_drop, w));
-  if (misaligned(x) || misaligned(saved) || misaligned(ws_mem) || misaligned(scalar, 4)) return api_fail(w + "x, saved and the workspace must be 16-byte aligned");
-  return 0;
-}
-
-int carve_checked(const ns_pg_shape& s, void* ws_mem, size_t ws_bytes, Ws* ws, const std::string& w) {
-  size_t need = 0;
-  NS_TRY(carve(s, ws_mem, ws, &need, w));
-  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_pg_ws_bytes)");
+  NS_TRY(check_aligned(w, {{"x", x}, {"saved", saved}, {"the workspace", ws_mem}, scalar}));
   return 0;
 }
 }  // namespace
@@ -87,19 +79,12 @@ extern "C" int ns_pg_plan_wgrad(int M, int N, int Cin, int KW, int32_t out[8]) {
 }
 
 extern "C" size_t ns_pg_ws_bytes(const ns_pg_shape* s) {
-  const std::string w = "ns_pg_ws_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(s->B, s->S, s->F, s->Cin, s->K, 4, w)) return 0;
-  Ws ws; size_t bytes = 0;
-  if (carve(*s, nullptr, &ws, &bytes, w)) return 0;
-  return bytes;
+  return size_query("ns_pg_ws_bytes", s, check_shape, [](const ns_pg_shape& s, const std::string& w) { return carved_bytes(carve, s, w); });
 }
 
 extern "C" size_t ns_pg_saved_bytes(const ns_pg_shape* s) {
-  const std::string w = "ns_pg_saved_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(s->B, s->S, s->F, s->Cin, s->K, 4, w)) return 0;
-  return (size_t)3 * s->B * s->S * s->F * sizeof(float);
+  return size_query("ns_pg_saved_bytes", s, check_shape,
+                    [](const ns_pg_shape& s, const std::string&) { return (size_t)3 * s.B * s.S * s.F * sizeof(float); });
 }
 
 extern "C" int ns_pg_forward(const ns_pg_shape* s, const ns_pg_weights* k, const float* x, const uint8_t* mask, const uint8_t* keep1,
@@ -107,9 +92,9 @@ extern "C" int ns_pg_forward(const ns_pg_shape* s, const ns_pg_weights* k, const
   const std::string w = "ns_pg_forward: ";
   t_launches = 0;
   if (!s || !k || !x || !pred || !ws_mem) return api_fail(w + "null argument");
-  NS_TRY(common(w, s, k, x, keep1, keep2, p_drop, saved, ws_mem, pred));
+  NS_TRY(common(w, s, k, x, keep1, keep2, p_drop, saved, ws_mem, {"pred", pred, 4}));
   Ws ws;
-  NS_TRY(carve_checked(*s, ws_mem, ws_bytes, &ws, w));
+  NS_TRY(carve_checked(carve, counted.abi, *s, ws_mem, ws_bytes, &ws, w));
   const int M = s->B * s->S, F = s->F, K = s->K, pad = (K - 1) / 2;
   const size_t mf = (size_t)M * F;
   float* v1 = saved ? (float*)saved : ws.a;
@@ -117,12 +102,12 @@ extern "C" int ns_pg_forward(const ns_pg_shape* s, const ns_pg_weights* k, const
   float* v2 = saved ? v1 + 2 * mf : ws.c;
   const float scale = 1.f / (1.f - p_drop);
   hipStream_t st = (hipStream_t)stream;
-  NS_HIP(launch_pg_pack(PgPack{k->w1, ws.w1p, nullptr, F, s->Cin, K}, PgPack{k->w2, ws.w2p, nullptr, F, F, K}, st));
-  ++t_launches;
-  NS_TRY(conv(x, ws.w1p, k->b1, v1, M, s->S, F, s->Cin, K, pad, ACT_RELU, st));
+  const PgPack packs[2] = {{k->w1, ws.w1p, nullptr, F, s->Cin, K}, {k->w2, ws.w2p, nullptr, F, F, K}};
+  NS_TRY(counted.pack(packs, 2, st));
+  NS_TRY(counted.conv(x, s->Cin, ws.w1p, k->b1, nullptr, v1, M, s->S, F, s->Cin, K, pad, ACT_RELU, st));
   NS_HIP(launch_pg_row_forward(v1, k->ln1_g, k->ln1_b, keep1, scale, h1, nullptr, nullptr, nullptr, nullptr, M, F, st));
   ++t_launches;
-  NS_TRY(conv(h1, ws.w2p, k->b2, v2, M, s->S, F, F, K, pad, ACT_RELU, st));
+  NS_TRY(counted.conv(h1, F, ws.w2p, k->b2, nullptr, v2, M, s->S, F, F, K, pad, ACT_RELU, st));
   NS_HIP(launch_pg_row_forward(v2, k->ln2_g, k->ln2_b, keep2, scale, nullptr, k->wlin, k->blin, mask, pred, M, F, st));
   ++t_launches;
   return 0;
@@ -134,12 +119,12 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
   const std::string w = "ns_pg_backward: ";
   t_launches = 0;
   if (!s || !k || !x || !saved || !g || !d || !ws_mem) return api_fail(w + "null argument");
-  NS_TRY(common(w, s, k, x, keep1, keep2, p_drop, saved, ws_mem, g));
+  NS_TRY(common(w, s, k, x, keep1, keep2, p_drop, saved, ws_mem, {"g", g, 4}));
   std::vector<NamedPtr> outs = ten(*d);
   outs.push_back({"dx", d->dx});
   NS_TRY(check_grads(outs, w));
   Ws ws;
-  NS_TRY(carve_checked(*s, ws_mem, ws_bytes, &ws, w));
+  NS_TRY(carve_checked(carve, counted.abi, *s, ws_mem, ws_bytes, &ws, w));
   const int M = s->B * s->S, F = s->F, Cin = s->Cin, K = s->K, padT = K - 1 - (K - 1) / 2;
   const size_t mf = (size_t)M * F;
   const float* v1 = (const float*)saved;
@@ -155,8 +140,8 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
   const int nblk = pg_row_blocks(M);
 
   if (stage1 || d->dx) {
-    NS_HIP(launch_pg_pack(PgPack{d->dx ? k->w1 : nullptr, nullptr, ws.w1t, F, Cin, K}, PgPack{stage1 ? k->w2 : nullptr, nullptr, ws.w2t, F, F, K}, st));
-    ++t_launches;
+    const PgPack packs[2] = {{d->dx ? k->w1 : nullptr, nullptr, ws.w1t, F, Cin, K}, {stage1 ? k->w2 : nullptr, nullptr, ws.w2t, F, F, K}};
+    NS_TRY(counted.pack(packs, 2, st));
   }
   NS_HIP(launch_pg_row_backward(pg_row_backward_args(1, M, F, p_drop, nullptr, g, mask, v2, k->ln2_g, k->ln2_b, k->wlin, keep2, ws.a, ws.colpart), st));
   ++t_launches;
@@ -165,7 +150,7 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
     t_launches += 2;
   }
   if (stage1) {
-    NS_TRY(conv(ws.a, ws.w2t, nullptr, ws.b, M, s->S, F, F, K, padT, ACT_NONE, st));
+    NS_TRY(counted.conv(ws.a, F, ws.w2t, nullptr, nullptr, ws.b, M, s->S, F, F, K, padT, ACT_NONE, st));
     NS_HIP(launch_pg_row_backward(pg_row_backward_args(0, M, F, p_drop, ws.b, nullptr, nullptr, v1, k->ln1_g, nullptr, nullptr, keep1, ws.c,
                                                        ws.colpart + (size_t)nblk * PG_SLOTS * F), st));
     ++t_launches;
@@ -173,10 +158,10 @@ extern "C" int ns_pg_backward(const ns_pg_shape* s, const ns_pg_weights* k, cons
       NS_HIP(launch_pg_wgrad(ws.c, x, M, s->S, F, Cin, K, p1, ws.partial, d->w1, st));
       t_launches += 2;
     }
-    if (d->dx) NS_TRY(conv(ws.c, ws.w1t, nullptr, d->dx, M, s->S, Cin, F, K, padT, ACT_NONE, st));
+    if (d->dx) NS_TRY(counted.conv(ws.c, F, ws.w1t, nullptr, nullptr, d->dx, M, s->S, Cin, F, K, padT, ACT_NONE, st));
   }
   // (a wanted d->ln1_g, ln1_b or b1 implies stage1, so stage 1 of the partials was written)
-  return col_finish(ws.colpart, nblk, F, {d->ln2_g, d->ln2_b, d->b2, d->wlin, d->blin}, {d->ln1_g, d->ln1_b, d->b1}, &t_launches, st);
+  return counted.col_finish(ws.colpart, nblk, F, {d->ln2_g, d->ln2_b, d->b2, d->wlin, d->blin}, {d->ln1_g, d->ln1_b, d->b1}, st);
 }
 
 extern "C" int ns_pg_op_wgrad(const float* dz, const float* X, int B, int S, int N, int Cin, int KW, float* dW, float* db, void* ws_mem,
@@ -185,7 +170,7 @@ extern "C" int ns_pg_op_wgrad(const float* dz, const float* X, int B, int S, int
   t_launches = 0;
   if (!dz || !X || !dW || !ws_mem) return api_fail(w + "null argument");
   NS_TRY(check_dims(B, S, N, Cin, KW, 4, w));
-  if (misaligned(dz) || misaligned(X) || misaligned(dW) || misaligned(db) || misaligned(ws_mem)) return api_fail(w + "every pointer must be 16-byte aligned");
+  NS_TRY(check_aligned(w, {{"dz", dz}, {"X", X}, {"dW", dW}, {"db", db}, {"the workspace", ws_mem}}));
   const int M = B * S;
   PgWgradPlan pl;
   if (!pg_plan_wgrad(M, N, Cin, KW, &pl)) return api_fail(w + "problem too large for the weight gradient's split");
@@ -197,9 +182,9 @@ extern "C" int ns_pg_op_wgrad(const float* dz, const float* X, int B, int S, int
   NS_HIP(launch_pg_wgrad(dz, X, M, S, N, Cin, KW, pl, partial, dW, st));
   t_launches += 2;
   if (db) {
-    NS_HIP(launch_pg_colsum(dz, M, N, colpart, st));
+    NS_HIP(launch_pg_colsum(dz, M, N, 1, colpart, st));
     ++t_launches;
-    NS_TRY(col_finish(colpart, pg_row_blocks(M), N, {db}, {}, &t_launches, st));
+    NS_TRY(counted.col_finish(colpart, pg_row_blocks(M), N, {db}, {}, st));
   }
   return 0;
 }
@@ -210,14 +195,14 @@ extern "C" int ns_pg_op_dgrad(const float* dz, const float* W, int B, int S, int
   t_launches = 0;
   if (!dz || !W || !dX || !ws_mem) return api_fail(w + "null argument");
   NS_TRY(check_dims(B, S, N, Cin, KW, 16, w));
-  if (misaligned(dz) || misaligned(W) || misaligned(dX) || misaligned(ws_mem)) return api_fail(w + "every pointer must be 16-byte aligned");
+  NS_TRY(check_aligned(w, {{"dz", dz}, {"W", W}, {"dX", dX}, {"the workspace", ws_mem}}));
   Bump bump(ws_mem);
   float* wt = bump.f((size_t)N * Cin * KW);
   if (ws_bytes < bump.off) return api_fail(w + "workspace too small: " + std::to_string(bump.off) + " bytes needed");
   hipStream_t st = (hipStream_t)stream;
-  NS_HIP(launch_pg_pack(PgPack{W, nullptr, wt, N, Cin, KW}, PgPack{nullptr, nullptr, nullptr, 0, 0, 0}, st));
-  ++t_launches;
-  return conv(dz, wt, nullptr, dX, B * S, S, Cin, N, KW, KW - 1 - (KW - 1) / 2, ACT_NONE, st);
+  const PgPack one{W, nullptr, wt, N, Cin, KW};
+  NS_TRY(counted.pack(&one, 1, st));
+  return counted.conv(dz, N, wt, nullptr, nullptr, dX, B * S, S, Cin, N, KW, KW - 1 - (KW - 1) / 2, ACT_NONE, st);
 }
 
 extern "C" int ns_pg_op_row_backward(int tail, const float* dy, const float* g, const uint8_t* mask, const float* v, const float* ln_g,
@@ -230,14 +215,13 @@ extern "C" int ns_pg_op_row_backward(int tail, const float* dy, const float* g, 
   if (tail ? (!g || !ln_b || !wlin || !d_wlin || !d_blin) : !dy) return api_fail(w + "null argument");
   NS_TRY(check_dims(M, 1, F, 4, 1, 4, w));
   NS_TRY(check_drop({keep, keep}, p_drop, w));  // (the texts of the two-mask entry points)
-  const void* al[] = {dy, v, ln_g, ln_b, wlin, dz, d_ln_g, d_ln_b, d_b, d_wlin, ws_mem};
-  for (const void* p : al)
-    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
+  NS_TRY(check_aligned(w, {{"dy", dy}, {"v", v}, {"ln_g", ln_g}, {"ln_b", ln_b}, {"wlin", wlin}, {"dz", dz}, {"d_ln_g", d_ln_g}, {"d_ln_b", d_ln_b},
+                           {"d_b", d_b}, {"d_wlin", d_wlin}, {"the workspace", ws_mem}}));
   const size_t need = (size_t)pg_row_blocks(M) * PG_SLOTS * F * sizeof(double);
   if (ws_bytes < need) return api_fail(w + "workspace too small: " + std::to_string(need) + " bytes needed");
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)ws_mem;
   NS_HIP(launch_pg_row_backward(pg_row_backward_args(tail, M, F, p_drop, dy, g, tail ? mask : nullptr, v, ln_g, ln_b, wlin, keep, dz, part), st));
   ++t_launches;
-  return col_finish(part, pg_row_blocks(M), F, {d_ln_g, d_ln_b, d_b, tail ? d_wlin : nullptr, tail ? d_blin : nullptr}, {}, &t_launches, st);
+  return counted.col_finish(part, pg_row_blocks(M), F, {d_ln_g, d_ln_b, d_b, tail ? d_wlin : nullptr, tail ? d_blin : nullptr}, {}, st);
 }

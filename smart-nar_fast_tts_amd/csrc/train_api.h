@@ -1,7 +1,8 @@
-// Host-side helpers shared by the handle-less training ABIs (predgrad_api.hip ns_pg_*, attngrad_api.hip ns_ag_*):
-// the argument checks whose texts the two state alike, the counted Conv1D-as-GEMM launch, the column-partial finish and the
-// row-backward argument blocks.  Host-only, no kernels.  Each ABI keeps its own thread-local launch counter and passes it in; what
-// differs between the layers (check_dims, Ws, carve) stays with the layer.
+// Host-side helpers shared by the handle-less training ABIs (ns_pg_*, ns_ag_*, ns_xg_*, ns_pn_*, ns_va_* in the five *grad_api.hip;
+// DESIGN.md section 20): the argument checks whose texts they state alike, the workspace and size-query wrappers, the counted launches
+// of the kernels they share (Conv1D-as-GEMM, weight pack, column-partial finish) and the row-backward argument blocks.  Host-only, no
+// kernels.  Each ABI keeps its own thread-local launch counter and hands it in as a Counted; what differs between the layers
+// (check_dims, Ws, carve, the forward and backward bodies) stays with the layer.
 #pragma once
 #include <initializer_list>
 
@@ -11,25 +12,37 @@ namespace ns {
 
 inline bool misaligned(const void* p, int align = 16) { return ((uintptr_t)p & (uintptr_t)(align - 1)) != 0; }
 
-// p_drop and the keep-masks of an entry point that takes one or two of them
-inline int check_drop(std::initializer_list<const uint8_t*> keep, float p, const std::string& w) {
-  const bool two = keep.size() > 1;
-  bool all = true, any = false, skew = false;
-  for (const uint8_t* k : keep) { all = all && k; any = any || k; skew = skew || misaligned(k); }
-  if (!(p >= 0.f && p < 1.f)) return api_fail(w + "p_drop must lie in [0, 1)");
-  if (p > 0.f && !all) return api_fail(w + (two ? "p_drop > 0 needs both keep-masks" : "p_drop > 0 needs a keep-mask"));
-  if (p == 0.f && any) return api_fail(w + (two ? "keep-masks given although p_drop == 0" : "keep-mask given although p_drop == 0"));
-  if (skew) return api_fail(w + (two ? "keep-masks must be 16-byte aligned" : "the keep-mask must be 16-byte aligned"));
+// one pointer an entry point takes or one field of a weights or grads block: its name in the header, the pointer, the alignment its
+// readers need (a float scalar: 4, an int64: 8)
+struct NamedPtr { const char* name; const void* p; int align = 16; };
+
+// null passes: whether a pointer may be null is the entry point's own check
+inline int check_aligned(const std::string& w, std::initializer_list<NamedPtr> t) {
+  for (const NamedPtr& e : t)
+    if (misaligned(e.p, e.align)) return api_fail(w + e.name + " must be " + std::to_string(e.align) + "-byte aligned");
   return 0;
 }
 
-// one field of a weights or grads block: its name in the header, its pointer, the alignment its readers need (a scalar: 4)
-struct NamedPtr { const char* name; const void* p; int align = 16; };
+// p_drop and the n keep-masks of an entry point; keep == nullptr = none of them given; `all` is how a refusal calls the n masks
+inline int check_drop(const uint8_t* const* keep, int n, float p, const std::string& w, const char* all = "all n keep-masks") {
+  bool every = keep != nullptr, any = false, skew = false;
+  for (int i = 0; keep && i < n; ++i) { every = every && keep[i]; any = any || keep[i]; skew = skew || misaligned(keep[i]); }
+  if (!(p >= 0.f && p < 1.f)) return api_fail(w + "p_drop must lie in [0, 1)");
+  if (p > 0.f && !every) return api_fail(w + "p_drop > 0 needs " + all);
+  if (p == 0.f && any) return api_fail(w + (n == 1 ? "keep-mask" : "keep-masks") + " given although p_drop == 0");
+  if (skew) return api_fail(w + (n == 1 ? "the keep-mask" : "keep-masks") + " must be 16-byte aligned");
+  return 0;
+}
+// an entry point that takes one or two masks as arguments of their own
+inline int check_drop(std::initializer_list<const uint8_t*> keep, float p, const std::string& w) {
+  return check_drop(keep.begin(), (int)keep.size(), p, w, keep.size() > 1 ? "both keep-masks" : "a keep-mask");
+}
 
-inline int check_weights(const std::vector<NamedPtr>& t, const std::string& w) {
+// `prefix` names the sub-block the fields sit in ("layer[2].")
+inline int check_weights(const std::vector<NamedPtr>& t, const std::string& w, const std::string& prefix = "") {
   for (const NamedPtr& e : t) {
-    if (!e.p) return api_fail(w + "null weights->" + e.name);
-    if (misaligned(e.p, e.align)) return api_fail(w + "weights->" + e.name + " must be 16-byte aligned");
+    if (!e.p) return api_fail(w + "null weights->" + prefix + e.name);
+    if (misaligned(e.p, e.align)) return api_fail(w + "weights->" + prefix + e.name + " must be " + std::to_string(e.align) + "-byte aligned");
   }
   return 0;
 }
@@ -45,41 +58,93 @@ inline int check_grads(const std::vector<NamedPtr>& t, const std::string& w, boo
   return 0;
 }
 
-// Y [M, N] = act(conv(X [M, Cin], W packed [N][KW * Cin]) + bias), dense operands, plain epilogue; a caller adds what else it needs
-inline ConvGemm conv_gemm_args(const float* X, const float* W, const float* bias, float* Y, int M, int S, int N, int Cin, int KW, int pad, int act) {
-  ConvGemm p;
-  memset(&p, 0, sizeof(p));
-  p.X = X; p.ldx = Cin; p.W = W; p.bias = bias; p.Y = Y; p.ldy = N;
-  p.M = M; p.N = N; p.Cin = Cin; p.KW = KW; p.pad = pad; p.S = S; p.act = act; p.epi = EPI_NONE;
-  return p;
+// the ten parameters of an attention-shaped weights or grads block (ns_ag_*, ns_xg_*), in ABI order
+template <class T>
+std::vector<NamedPtr> attn_params(const T& k) {
+  return {{"wq", k.wq}, {"bq", k.bq}, {"wk", k.wk}, {"bk", k.bk}, {"wv", k.wv}, {"bv", k.bv}, {"wfc", k.wfc}, {"bfc", k.bfc}, {"ln_g", k.ln_g},
+          {"ln_b", k.ln_b}};
 }
 
-// launch_conv_gemm through the forward's dispatch; adds the launches the dispatch makes for this shape to *launches
-inline int counted_conv_gemm(const ConvGemm& p, const char* abi, int* launches, hipStream_t st) {
-  int rec[2][8];
-  const int n = conv_gemm_describe(p.M, p.N, p.Cin, p.KW, 0, rec);
-  if (n <= 0) return api_fail(std::string(abi) + ": the Conv1D-as-GEMM dispatch refuses this shape");
-  NS_HIP(launch_conv_gemm(p, st));
-  *launches += n;
+// the layer's carve over the caller's workspace, refused where that is smaller than the layout
+template <class Shape, class Ws>
+int carve_checked(int (*carve)(const Shape&, void*, Ws*, size_t*, const std::string&), const char* abi, const Shape& s, void* ws_mem, size_t ws_bytes,
+                  Ws* ws, const std::string& w) {
+  size_t need = 0;
+  NS_TRY(carve(s, ws_mem, ws, &need, w));
+  if (ws_bytes < need) return api_fail(w + "workspace too small (" + abi + "_ws_bytes)");
   return 0;
 }
 
-// the fixed-order sum of the column partials into the slots of stage 0 and stage 1 (k_pg_col_final): one launch, made and counted
-// only when an output is wanted
-inline int col_finish(const double* part, int nblk, int F, std::initializer_list<float*> stage0, std::initializer_list<float*> stage1,
-                      int* launches, hipStream_t st) {
-  PgColFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  bool any = false;
-  int i = 0;
-  for (float* o : stage0) { fin.out[i++] = o; any = any || o; }
-  i = PG_SLOTS;
-  for (float* o : stage1) { fin.out[i++] = o; any = any || o; }
-  if (!any) return 0;
-  NS_HIP(launch_pg_col_final(part, nblk, F, fin, st));
-  ++*launches;
-  return 0;
+// the bytes of the layout the layer's carve makes for s; 0 where it refuses
+template <class Shape, class Ws>
+size_t carved_bytes(int (*carve)(const Shape&, void*, Ws*, size_t*, const std::string&), const Shape& s, const std::string& w) {
+  Ws ws;
+  size_t bytes = 0;
+  return carve(s, nullptr, &ws, &bytes, w) ? 0 : bytes;
 }
+
+// the body of an ns_*_ws_bytes / ns_*_saved_bytes: a null or refused shape (check(*s, w), the layer's check_dims) gives 0, else size(*s, w)
+template <class Shape, class Check, class Size>
+size_t size_query(const char* who, const Shape* s, Check check, Size size) {
+  const std::string w = std::string(who) + ": ";
+  if (!s) { api_fail(w + "null argument"); return 0; }
+  if (check(*s, w)) return 0;
+  return size(*s, w);
+}
+
+// The launches the layers share, counted into the calling ABI's own thread-local counter.
+struct Counted {
+  const char* abi;  // "ns_pg": named in a refusal
+  int* launches;
+
+  // Y [M, N] = act(conv(X [M, Cin] at row stride ldx, W packed [N][KW * Cin]) + bias) + resid, plain epilogue, through the forward's
+  // dispatch; adds the launches the dispatch makes for this shape
+  int conv(const float* X, int ldx, const float* W, const float* bias, const float* resid, float* Y, int M, int S, int N, int Cin, int KW, int pad,
+           int act, hipStream_t st) const {
+    ConvGemm p;
+    memset(&p, 0, sizeof(p));
+    p.X = X; p.ldx = ldx; p.W = W; p.bias = bias; p.resid = resid; p.ldr = N; p.Y = Y; p.ldy = N;
+    p.M = M; p.N = N; p.Cin = Cin; p.KW = KW; p.pad = pad; p.S = S; p.act = act; p.epi = EPI_NONE;
+    int rec[2][8];
+    const int n = conv_gemm_describe(M, N, Cin, KW, 0, rec);
+    if (n <= 0) return api_fail(std::string(abi) + ": the Conv1D-as-GEMM dispatch refuses this shape");
+    NS_HIP(launch_conv_gemm(p, st));
+    *launches += n;
+    return 0;
+  }
+
+  // Y [M, N] = X [M, K] W[N][K]^T + bias + resid: the same at KW = 1
+  int gemm(const float* X, const float* W, const float* bias, const float* resid, float* Y, int M, int S, int N, int K, hipStream_t st) const {
+    return conv(X, K, W, bias, resid, Y, M, S, N, K, 1, 0, ACT_NONE, st);
+  }
+
+  // k_pg_pack over `count` weights, two per launch
+  int pack(const PgPack* v, int count, hipStream_t st) const {
+    const PgPack none{nullptr, nullptr, nullptr, 0, 0, 0};
+    for (int i = 0; i < count; i += 2) {
+      NS_HIP(launch_pg_pack(v[i], i + 1 < count ? v[i + 1] : none, st));
+      ++*launches;
+    }
+    return 0;
+  }
+
+  // the fixed-order sum of the column partials into the slots of stage 0 and stage 1 (k_pg_col_final): one launch, made and counted
+  // only when an output is wanted
+  int col_finish(const double* part, int nblk, int F, std::initializer_list<float*> stage0, std::initializer_list<float*> stage1,
+                 hipStream_t st) const {
+    PgColFinal fin;
+    memset(&fin, 0, sizeof(fin));
+    bool any = false;
+    int i = 0;
+    for (float* o : stage0) { fin.out[i++] = o; any = any || o; }
+    i = PG_SLOTS;
+    for (float* o : stage1) { fin.out[i++] = o; any = any || o; }
+    if (!any) return 0;
+    NS_HIP(launch_pg_col_final(part, nblk, F, fin, st));
+    ++*launches;
+    return 0;
+  }
+};
 
 inline PgRowBackward pg_row_backward_args(int tail, int M, int F, float p_drop, const float* dy, const float* g, const uint8_t* mask, const float* v,
                                           const float* ln_g, const float* ln_b, const float* wlin, const uint8_t* keep, float* dz, double* part) {

@@ -2,7 +2,6 @@
 //   k_xg_bwd_q          owns 128 queries of one (b, h), sweeps the key tiles below src_lens[b]: D and dQ
 //   k_xg_bwd_kv         owns 128 keys of one (b, h) and one part of the query tiles: dK and dV (or their partial sums)
 //   k_xg_kv_reduce      the fixed-order sum of the parts, +0.0 at keys >= src_lens[b]; only launched when there is more than one part
-//   k_xg_colsum         column partials of dQ (over B*T rows) or of dK | dV (over B*L rows), in the layout k_pg_col_final sums
 //   k_xg_pack           Wk | Wv -> one [2d][d] weight + [2d] bias (forward) and the transposed forms the data gradients read
 // Unlike attngrad.hip nothing is recomputed: the probabilities A [B, H, T, L] are the module's own output (k_cross_attention wrote the
 // final values, exact 0 at masked keys) and carry an upstream gradient dA of their own (nullable), so both kernels READ their tile of A
@@ -334,24 +333,7 @@ hipError_t launch_xg_attention_backward(const float* q, const float* kv, const f
   return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------------------------------ column sums, pack
-// part[blk][third][col] = sum of rows [64 blk, 64 blk + 64) of src[:, third * d + col] (rows of `thirds * d` floats), ascending
-__global__ __launch_bounds__(256) void k_xg_colsum(const float* __restrict__ src, int M, int d, int thirds, double* __restrict__ part) {
-  const int m0 = blockIdx.x * PG_ROW_BLOCK, m1 = min(M, m0 + PG_ROW_BLOCK), third = blockIdx.y;
-  for (int col = threadIdx.x; col < d; col += 256) {
-    double s = 0.0;
-    for (int m = m0; m < m1; ++m) s += (double)src[(size_t)m * thirds * d + third * d + col];
-    part[((size_t)blockIdx.x * PG_SLOTS + third) * d + col] = s;
-  }
-}
-
-hipError_t launch_xg_colsum(const float* src, int M, int d, int thirds, double* part, hipStream_t st) {
-  if (M <= 0) return hipSuccess;
-  if (thirds < 1 || thirds > PG_SLOTS) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_xg_colsum, dim3(pg_row_blocks(M), thirds), dim3(256), 0, st, src, M, d, thirds, part);
-  return hipGetLastError();
-}
-
+// ------------------------------------------------------------------------------------------------------------------ weight pack
 __global__ __launch_bounds__(256) void k_xg_pack(XgPack p) {
   const long long dd = (long long)p.d * p.d, step = (long long)gridDim.x * 256, first = (long long)blockIdx.x * 256 + threadIdx.x;
   if (p.wkv || p.wkvt)

@@ -2,8 +2,8 @@
 // FFTBlock2.crs_attn, transformer/Layers.py:61-64).  No handle: the weights are the caller's live tensors in checkpoint layout, the
 // workspace, the saved activations and the attention map belong to the caller.  Host-side only; every argument is validated before the
 // first HIP call.  The forward's attention is k_cross_attention as the aligner runs it; the four Linears run on what predgrad.hip and
-// gemm_conv.hip already have, the row kernels are attngrad.hip's, the checks and the column-partial finish are train_api.h's.  The
-// launch counts are stated in the header.
+// gemm_conv.hip already have (the column sums included), the row kernels are attngrad.hip's; the checks, the parameter table, the size
+// queries, the counted GEMM launch and the column-partial finish are train_api.h's.  The launch counts are stated in the header.
 #include "../../include/nar_fs2.h"
 #include "train_api.h"
 
@@ -14,6 +14,7 @@ static_assert(sizeof(ns_xg_weights) == 10 * sizeof(void*) && sizeof(ns_xg_grads)
 
 namespace {
 thread_local int t_launches = 0;
+thread_local const Counted counted{"ns_xg", &t_launches};
 
 struct Ws {  // the workspace of one shape, carved in this order
   float *wkv, *bkv, *wkvt, *wqt, *wfct;  // [2d][d] and [2d] (forward), [d][2d], [d][d], [d][d] (data gradients)
@@ -56,32 +57,16 @@ int carve(const ns_xg_shape& s, void* base, Ws* ws, size_t* bytes, const std::st
   return 0;
 }
 
-template <class T>
-std::vector<NamedPtr> ten(const T& k) {
-  return {{"wq", k.wq}, {"bq", k.bq}, {"wk", k.wk}, {"bk", k.bk}, {"wv", k.wv}, {"bv", k.bv}, {"wfc", k.wfc}, {"bfc", k.bfc}, {"ln_g", k.ln_g},
-          {"ln_b", k.ln_b}};
-}
+int check_shape(const ns_xg_shape& s, const std::string& w) { return check_dims(s.B, s.T, s.L, s.d, s.H, w); }
 
-// Y [M, N] = X [M, K] W[N][K]^T + bias + resid through the forward's dispatch; counts its launches
-int gemm(const float* X, const float* W, const float* bias, const float* resid, float* Y, int M, int S, int N, int K, hipStream_t st) {
-  ConvGemm p = conv_gemm_args(X, W, bias, Y, M, S, N, K, 1, 0, ACT_NONE);
-  p.resid = resid; p.ldr = N;
-  return counted_conv_gemm(p, "ns_xg", &t_launches, st);
-}
-
-int common(const char* who, const ns_xg_shape* s, const ns_xg_weights* k, const float* tgt, const float* src, const int64_t* lens,
+// what ns_xg_forward and ns_xg_backward check alike, in this order, and the carved workspace
+int common(const std::string& w, const ns_xg_shape* s, const ns_xg_weights* k, const float* tgt, const float* src, const int64_t* lens,
            const uint8_t* keep, float p_drop, const void* saved, const float* attn, void* ws_mem, size_t ws_bytes, Ws* ws) {
-  const std::string w = std::string(who) + ": ";
-  NS_TRY(check_dims(s->B, s->T, s->L, s->d, s->H, w));
-  NS_TRY(check_weights(ten(*k), w));
+  NS_TRY(check_shape(*s, w));
+  NS_TRY(check_weights(attn_params(*k), w));
   NS_TRY(check_drop({keep}, p_drop, w));
-  if (misaligned(tgt) || misaligned(src) || misaligned(saved) || misaligned(attn) || misaligned(ws_mem))
-    return api_fail(w + "tgt, src, saved, attn and the workspace must be 16-byte aligned");
-  if ((uintptr_t)lens & 7) return api_fail(w + "src_lens must be 8-byte aligned");
-  size_t need = 0;
-  NS_TRY(carve(*s, ws_mem, ws, &need, w));
-  if (ws_bytes < need) return api_fail(w + "workspace too small (ns_xg_ws_bytes)");
-  return 0;
+  NS_TRY(check_aligned(w, {{"tgt", tgt}, {"src", src}, {"saved", saved}, {"attn", attn}, {"the workspace", ws_mem}, {"src_lens", lens, 8}}));
+  return carve_checked(carve, counted.abi, *s, ws_mem, ws_bytes, ws, w);
 }
 }  // namespace
 
@@ -89,35 +74,30 @@ extern "C" int ns_xg_abi_version(void) { return NS_XG_ABI_VERSION; }
 extern "C" int ns_xg_last_launches(void) { return t_launches; }
 
 extern "C" size_t ns_xg_ws_bytes(const ns_xg_shape* s) {
-  const std::string w = "ns_xg_ws_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(s->B, s->T, s->L, s->d, s->H, w)) return 0;
-  Ws ws; size_t bytes = 0;
-  if (carve(*s, nullptr, &ws, &bytes, w)) return 0;
-  return bytes;
+  return size_query("ns_xg_ws_bytes", s, check_shape, [](const ns_xg_shape& s, const std::string& w) { return carved_bytes(carve, s, w); });
 }
 
 extern "C" size_t ns_xg_saved_bytes(const ns_xg_shape* s) {
-  const std::string w = "ns_xg_saved_bytes: ";
-  if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(s->B, s->T, s->L, s->d, s->H, w)) return 0;
-  return ((size_t)3 * s->B * s->T * s->d + (size_t)2 * s->B * s->L * s->d) * sizeof(float);
+  return size_query("ns_xg_saved_bytes", s, check_shape, [](const ns_xg_shape& s, const std::string&) {
+    return ((size_t)3 * s.B * s.T * s.d + (size_t)2 * s.B * s.L * s.d) * sizeof(float);
+  });
 }
 
 extern "C" int ns_xg_kv_splits(const ns_xg_shape* s) {
   const std::string w = "ns_xg_kv_splits: ";
   if (!s) { api_fail(w + "null argument"); return 0; }
-  if (check_dims(s->B, s->T, s->L, s->d, s->H, w)) return 0;
+  if (check_shape(*s, w)) return 0;
   return xg_kv_splits(s->B, s->H, s->T, s->L);
 }
 
 extern "C" int ns_xg_forward(const ns_xg_shape* s, const ns_xg_weights* k, const float* tgt, const float* src, const int64_t* src_lens,
                              const uint8_t* keep, float p_drop, float* y, float* attn, void* saved, void* ws_mem, size_t ws_bytes, void* stream) {
+  const std::string w = "ns_xg_forward: ";
   t_launches = 0;
-  if (!s || !k || !tgt || !src || !src_lens || !y || !attn || !ws_mem) return api_fail("ns_xg_forward: null argument");
-  if (misaligned(y)) return api_fail("ns_xg_forward: y must be 16-byte aligned");
+  if (!s || !k || !tgt || !src || !src_lens || !y || !attn || !ws_mem) return api_fail(w + "null argument");
+  NS_TRY(check_aligned(w, {{"y", y}}));
   Ws ws;
-  NS_TRY(common("ns_xg_forward", s, k, tgt, src, src_lens, keep, p_drop, saved, attn, ws_mem, ws_bytes, &ws));
+  NS_TRY(common(w, s, k, tgt, src, src_lens, keep, p_drop, saved, attn, ws_mem, ws_bytes, &ws));
   const int MT = s->B * s->T, ML = s->B * s->L, d = s->d, H = s->H, dk = d / H;
   const size_t mt = (size_t)MT * d, ml = (size_t)ML * 2 * d;
   float* q = saved ? (float*)saved : ws.tq;
@@ -127,11 +107,11 @@ extern "C" int ns_xg_forward(const ns_xg_shape* s, const ns_xg_weights* k, const
   hipStream_t st = (hipStream_t)stream;
   NS_HIP(launch_xg_pack(XgPack{k->wq, k->wk, k->wv, k->bk, k->bv, k->wfc, ws.wkv, ws.bkv, nullptr, nullptr, nullptr, d}, st));
   ++t_launches;
-  NS_TRY(gemm(tgt, k->wq, k->bq, nullptr, q, MT, s->T, d, d, st));
-  NS_TRY(gemm(src, ws.wkv, ws.bkv, nullptr, kv, ML, s->L, 2 * d, d, st));
+  NS_TRY(counted.gemm(tgt, k->wq, k->bq, nullptr, q, MT, s->T, d, d, st));
+  NS_TRY(counted.gemm(src, ws.wkv, ws.bkv, nullptr, kv, ML, s->L, 2 * d, d, st));
   NS_HIP(launch_cross_attention(q, kv, (const long long*)src_lens, s->B, s->T, s->L, H, dk, ctx, attn, st));
   ++t_launches;
-  NS_TRY(gemm(ctx, k->wfc, k->bfc, nullptr, ws.a, MT, s->T, d, d, st));
+  NS_TRY(counted.gemm(ctx, k->wfc, k->bfc, nullptr, ws.a, MT, s->T, d, d, st));
   NS_HIP(launch_ag_row_forward(ws.a, tgt, keep, 1.f / (1.f - p_drop), k->ln_g, k->ln_b, z, y, MT, d, st));
   ++t_launches;
   return 0;
@@ -144,13 +124,13 @@ extern "C" int ns_xg_backward(const ns_xg_shape* s, const ns_xg_weights* k, cons
   t_launches = 0;
   if (!s || !k || !tgt || !src || !src_lens || !saved || !attn || !g || !dg || !ws_mem) return api_fail(w + "null argument");
   if (misaligned(g) || misaligned(dattn)) return api_fail(w + "g and dA must be 16-byte aligned");
-  std::vector<NamedPtr> outs = ten(*dg);
+  std::vector<NamedPtr> outs = attn_params(*dg);
   outs.push_back({"dtgt", dg->dtgt});
   outs.push_back({"dsrc", dg->dsrc});
   bool any = false;
   NS_TRY(check_grads(outs, w, &any));
   Ws ws;
-  NS_TRY(common("ns_xg_backward", s, k, tgt, src, src_lens, keep, p_drop, saved, attn, ws_mem, ws_bytes, &ws));
+  NS_TRY(common(w, s, k, tgt, src, src_lens, keep, p_drop, saved, attn, ws_mem, ws_bytes, &ws));
   if (!any) return 0;
   const int MT = s->B * s->T, ML = s->B * s->L, d = s->d, H = s->H, dk = d / H, nbt = pg_row_blocks(MT), nbl = pg_row_blocks(ML);
   const size_t mt = (size_t)MT * d, ml = (size_t)ML * 2 * d;
@@ -180,7 +160,7 @@ extern "C" int ns_xg_backward(const ns_xg_shape* s, const ns_xg_weights* k, cons
     t_launches += 2;
   }
   if (upstream) {
-    NS_TRY(gemm(du, ws.wfct, nullptr, nullptr, dctx, MT, s->T, d, d, st));
+    NS_TRY(counted.gemm(du, ws.wfct, nullptr, nullptr, dctx, MT, s->T, d, d, st));
     const int nsplit = xg_kv_splits(s->B, H, s->T, s->L);
     NS_HIP(launch_xg_attention_backward(q, kv, ctx, attn, dctx, dattn, (const long long*)src_lens, s->B, s->T, s->L, H, dk, nsplit, ws.stat,
                                         ws.kvpart, dq, side_kv ? dkv : nullptr, st));
@@ -196,18 +176,18 @@ extern "C" int ns_xg_backward(const ns_xg_shape* s, const ns_xg_weights* k, cons
         t_launches += 2;
       }
     if (dg->bq) {
-      NS_HIP(launch_xg_colsum(dq, MT, d, 1, ws.colq, st));
+      NS_HIP(launch_pg_colsum(dq, MT, d, 1, ws.colq, st));
       ++t_launches;
     }
     if (dg->bk || dg->bv) {
-      NS_HIP(launch_xg_colsum(dkv, ML, d, 2, ws.colkv, st));
+      NS_HIP(launch_pg_colsum(dkv, ML, d, 2, ws.colkv, st));
       ++t_launches;
     }
-    if (dg->dtgt) NS_TRY(gemm(dq, ws.wqt, nullptr, dz, dg->dtgt, MT, s->T, d, d, st));
-    if (dg->dsrc) NS_TRY(gemm(dkv, ws.wkvt, nullptr, nullptr, dg->dsrc, ML, s->L, d, 2 * d, st));
+    if (dg->dtgt) NS_TRY(counted.gemm(dq, ws.wqt, nullptr, dz, dg->dtgt, MT, s->T, d, d, st));
+    if (dg->dsrc) NS_TRY(counted.gemm(dkv, ws.wkvt, nullptr, nullptr, dg->dsrc, ML, s->L, d, 2 * d, st));
   }
-  NS_TRY(col_finish(ws.colkv, nbl, d, {dg->bk, dg->bv}, {}, &t_launches, st));
-  return col_finish(ws.colq, nbt, d, {dg->bq}, {dg->ln_g, dg->ln_b, dg->bfc}, &t_launches, st);
+  NS_TRY(counted.col_finish(ws.colkv, nbl, d, {dg->bk, dg->bv}, {}, st));
+  return counted.col_finish(ws.colq, nbt, d, {dg->bq}, {dg->ln_g, dg->ln_b, dg->bfc}, st);
 }
 
 extern "C" int ns_xg_op_attention_backward(const float* q, const float* kv, const float* ctx, const float* attn, const float* dctx,
@@ -218,10 +198,8 @@ extern "C" int ns_xg_op_attention_backward(const float* q, const float* kv, cons
   if (!q || !kv || !ctx || !attn || !dctx || !src_lens || !dq || !dkv || !ws_mem) return api_fail(w + "null argument");
   NS_TRY(check_dims(B, T, L, d, H, w));
   if (kv_splits < 0 || kv_splits > 8) return api_fail(w + "kv_splits must lie in [0, 8] (0 = the planned number), got " + std::to_string(kv_splits));
-  const void* al[] = {q, kv, ctx, attn, dctx, dattn, dq, dkv, ws_mem};
-  for (const void* p : al)
-    if (misaligned(p)) return api_fail(w + "every pointer must be 16-byte aligned");
-  if ((uintptr_t)src_lens & 7) return api_fail(w + "src_lens must be 8-byte aligned");
+  NS_TRY(check_aligned(w, {{"q", q}, {"kv", kv}, {"ctx", ctx}, {"attn", attn}, {"dctx", dctx}, {"dA", dattn}, {"dq", dq}, {"dkv", dkv},
+                           {"the workspace", ws_mem}, {"src_lens", src_lens, 8}}));
   const int nsplit = kv_splits ? kv_splits : xg_kv_splits(B, H, T, L);
   Bump bump(ws_mem);
   float* D = bump.f((size_t)B * H * T);

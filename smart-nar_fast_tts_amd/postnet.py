@@ -81,14 +81,13 @@ class PostNet(HipTrainModule):
         call = self._begin(x, self.n_mel)
         B, T, _ = x.shape
         dev = call.device
-        training = bool(self.training)
-        if training and B * T == 1:
+        call.training = bool(self.training)
+        if call.training and B * T == 1:
             raise ValueError("Expected more than 1 value per channel when training, got input size " + str(tuple(x.shape)))
         s = _lib.NsPnShape()
         s.B, s.T, s.n_mel, s.emb, s.K, s.n = B, T, self.n_mel, self.emb, self.kernel, self.n
         call.shape = s
-        call.mask = training  # (the Call's spare slot: this layer has no padding mask)
-        call.src = []         # the live buffers, kept alive with the call
+        call.buffers = []  # the live buffers, kept alive with the call
         for i in range(self.n):
             bn = self.convolutions[i][1]
             for name in _lib.PN_BUFFERS:
@@ -97,32 +96,13 @@ class PostNet(HipTrainModule):
                 if t.device != dev or t.dtype != want or not t.is_contiguous() or t.data_ptr() % (8 if want == torch.int64 else 16):
                     raise ValueError(f"convolutions.{i}.1.{name} must be a contiguous, aligned {want} tensor on {dev}: the kernels update it in place")
                 setattr(call.weights, f"{name}{i}", t.data_ptr())
-                call.src.append(t)
-        call.p = self.dropout if training else 0.0
-        call.keep = self._masks(keep_masks, B, T, dev, call.p)
+                call.buffers.append(t)
+        call.p = self.dropout if call.training else 0.0
+        call.keep = self._keep_masks(keep_masks, [(B, T, c) for c in self.channels[1:]], dev, call.p)  # one per convolution
         return call
 
-    def _masks(self, given, B, T, dev, p):
-        shapes = [(B, T, c) for c in self.channels[1:]]
-        if given is not None:
-            if p == 0.0:
-                raise ValueError("keep_masks given although no dropout applies (eval() or dropout == 0)")
-            given = list(given)
-            if len(given) != self.n:
-                raise ValueError(f"keep_masks must hold {self.n} masks, one per convolution, got {len(given)}")
-            ks = []
-            for k, shape in zip(given, shapes):
-                if tuple(k.shape) != shape or k.device != dev:
-                    raise ValueError(f"a keep-mask must have shape {shape} on {dev}, got {tuple(k.shape)} on {k.device}")
-                ks.append(aligned((k != 0).contiguous().view(torch.uint8)))
-            return tuple(ks)
-        if p > 0.0:
-            with guard(dev):
-                return tuple(torch.bernoulli(torch.full(shape, 1.0 - p, dtype=torch.float32, device=dev)).to(torch.uint8) for shape in shapes)
-        return None
-
     def _keep_ptrs(self, call):
-        if call.keep is None:
+        if call.keep[0] is None:
             return None
         return (C.c_void_p * self.n)(*[k.data_ptr() for k in call.keep])
 
@@ -134,7 +114,7 @@ class PostNet(HipTrainModule):
         with guard(dev):
             ws, saved = self._workspace(call, save)
             y = torch.empty((s.B, s.T, s.n_mel), dtype=torch.float32, device=dev)
-            self._done(self._lib.ns_pn_forward(C.byref(s), C.byref(call.weights), int(call.mask), _lib.ptr(call.x), self._keep_ptrs(call), call.p,
+            self._done(self._lib.ns_pn_forward(C.byref(s), C.byref(call.weights), int(call.training), _lib.ptr(call.x), self._keep_ptrs(call), call.p,
                                                _lib.ptr(y), _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "forward")
         return y, saved
 
@@ -147,6 +127,6 @@ class PostNet(HipTrainModule):
         with guard(dev):
             outs, d = self._grad_block(call, need)
             ws, _ = self._workspace(call, save=False)
-            self._done(self._lib.ns_pn_backward(C.byref(s), C.byref(call.weights), int(call.mask), _lib.ptr(call.x), self._keep_ptrs(call), call.p,
+            self._done(self._lib.ns_pn_backward(C.byref(s), C.byref(call.weights), int(call.training), _lib.ptr(call.x), self._keep_ptrs(call), call.p,
                                                 _lib.ptr(saved), _lib.ptr(g), C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward")
         return outs

@@ -75,7 +75,7 @@ class VariancePredictor(HipTrainModule):
                 raise ValueError(f"mask must be a bool [B, S] = {(B, S)} tensor on {dev}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
             call.mask = (mask != 0).contiguous().view(torch.uint8)
         call.p = self.dropout if self.training else 0.0
-        call.keep = self._keep_masks(keep_masks, 2, (B, S, self.filter_size), dev, call.p)
+        call.keep = self._keep_masks(keep_masks, [(B, S, self.filter_size)] * 2, dev, call.p, stacked=True)
         return call
 
     def forward(self, encoder_output, mask=None, keep_masks=None):

@@ -29,7 +29,54 @@ PARAM_NAMES = ("w_qs.weight", "w_qs.bias", "w_ks.weight", "w_ks.bias", "w_vs.wei
                "layer_norm.weight", "layer_norm.bias")  # order of ns_ag_weights
 
 
-class MultiHeadAttention(HipTrainModule):
+class _Attention(HipTrainModule):
+    """What the two uses of the reference's ``MultiHeadAttention`` share: the constructor (a subclass names the head widths its kernels
+    are built for in ``D_K``) and the key lengths of a call."""
+
+    PARAM_NAMES, FIELDS = PARAM_NAMES, _lib.AG_NAMES
+
+    def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
+        super().__init__()
+        who, widths = type(self).__name__, [str(w) for w in self.D_K]
+        if d_k != d_v:
+            raise ValueError(f"{who}: d_k must equal d_v, got {d_k} and {d_v}")
+        if n_head * d_k != d_model:
+            raise ValueError(f"{who}: n_head * d_k must equal d_model, got {n_head} * {d_k} and {d_model}")
+        if d_model not in (256, 512) or d_k not in self.D_K:
+            raise ValueError(f"{who}: d_model must be 256 or 512 and d_k {', '.join(widths[:-1])} or {widths[-1]}, got {d_model} and {d_k}")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"{who}: dropout must lie in [0, 1), got {dropout}")
+        self.n_head, self.d_k, self.d_v, self.d_model = n_head, d_k, d_v, d_model
+        self.p_drop = float(dropout)
+        self.w_qs = torch.nn.Linear(d_model, n_head * d_k)
+        self.w_ks = torch.nn.Linear(d_model, n_head * d_k)
+        self.w_vs = torch.nn.Linear(d_model, n_head * d_v)
+        self.layer_norm = torch.nn.LayerNorm(d_model)
+        self.fc = torch.nn.Linear(n_head * d_v, d_model)
+        self.validate_mask = True
+
+    def _key_lengths(self, call, mask, lens, T, L, dims, q, k):
+        """``call.lens`` (int64 [B]) from ``lens``, else from the key-padding ``mask`` (bool [B, T, L]), else left None.  The messages
+        call the mask's shape ``dims`` ("[B, S, S]") and a query and a key index ``q`` and ``k`` ("i", "j")."""
+        dev, B = call.device, call.shape.B
+        if lens is not None:
+            if not isinstance(lens, torch.Tensor) or tuple(lens.shape) != (B,) or lens.device != dev or lens.dtype not in (torch.int64, torch.int32):
+                raise ValueError(f"lens must be an int64 [B] = {(B,)} tensor on {dev}")
+            call.lens = lens.to(torch.int64).contiguous()
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, T, L) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != dev:
+                raise ValueError(f"mask must be a bool {dims} = {(B, T, L)} tensor on {dev}")
+            if call.lens is None:
+                with guard(dev):
+                    m = mask != 0
+                    call.lens = (L - m[:, 0, :].sum(-1)).to(torch.int64)
+                    if self.validate_mask:
+                        want = torch.arange(L, device=dev)[None, None, :] >= call.lens[:, None, None]
+                        if not bool((m == want).all()):
+                            raise ValueError(f"mask is not a key-padding mask: mask[b, {q}, {k}] must equal {k} >= lens[b] for every {q}")
+
+
+class MultiHeadAttention(_Attention):
     """Drop-in for ``MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=0.1)`` as a self-attention sublayer: the same parameter
     names (``w_qs``, ``w_ks``, ``w_vs``, ``fc``, ``layer_norm``), ``forward(q, k, v, mask=None, lens=None, keep_mask=None) ->
     (output, None)`` with ``output = layer_norm(dropout(fc(attention)) + q)``, NOT masked (FFTBlock does that outside).
@@ -49,53 +96,19 @@ class MultiHeadAttention(HipTrainModule):
     Raises on what it cannot do: cross-attention (``q``, ``k``, ``v`` not one tensor), ``d_k != d_v``, ``n_head * d_k != d_model``,
     d_model not 256 or 512, d_k not 32, 64 or 128, a mask that is not a key-padding mask."""
 
-    ABI, INPUT, PARAM_NAMES = "ns_ag", "the input", PARAM_NAMES
-    FIELDS, WEIGHTS, GRADS = _lib.AG_NAMES, _lib.NsAgWeights, _lib.NsAgGrads
+    ABI, INPUT, D_K = "ns_ag", "the input", (32, 64, 128)
+    WEIGHTS, GRADS = _lib.NsAgWeights, _lib.NsAgGrads
     WORKSPACES = WorkspaceCache("ns_ag_ws_bytes", ("B", "S", "d", "H"))
-
-    def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
-        super().__init__()
-        if d_k != d_v:
-            raise ValueError(f"MultiHeadAttention: d_k must equal d_v, got {d_k} and {d_v}")
-        if n_head * d_k != d_model:
-            raise ValueError(f"MultiHeadAttention: n_head * d_k must equal d_model, got {n_head} * {d_k} and {d_model}")
-        if d_model not in (256, 512) or d_k not in (32, 64, 128):
-            raise ValueError(f"MultiHeadAttention: d_model must be 256 or 512 and d_k 32, 64 or 128, got {d_model} and {d_k}")
-        if not 0.0 <= float(dropout) < 1.0:
-            raise ValueError(f"MultiHeadAttention: dropout must lie in [0, 1), got {dropout}")
-        self.n_head, self.d_k, self.d_v, self.d_model = n_head, d_k, d_v, d_model
-        self.p_drop = float(dropout)
-        self.w_qs = torch.nn.Linear(d_model, n_head * d_k)
-        self.w_ks = torch.nn.Linear(d_model, n_head * d_k)
-        self.w_vs = torch.nn.Linear(d_model, n_head * d_v)
-        self.layer_norm = torch.nn.LayerNorm(d_model)
-        self.fc = torch.nn.Linear(n_head * d_v, d_model)
-        self.validate_mask = True
 
     def _marshal(self, x, mask, lens, keep_mask):
         call = self._begin(x, self.d_model)
         B, S, d = x.shape
-        dev = call.device
         s = _lib.NsAgShape()
         s.B, s.S, s.d, s.H = B, S, d, self.n_head
         call.shape = s
-        if lens is not None:
-            if not isinstance(lens, torch.Tensor) or tuple(lens.shape) != (B,) or lens.device != dev or lens.dtype not in (torch.int64, torch.int32):
-                raise ValueError(f"lens must be an int64 [B] = {(B,)} tensor on {dev}")
-            call.lens = lens.to(torch.int64).contiguous()
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, S, S) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != dev:
-                raise ValueError(f"mask must be a bool [B, S, S] = {(B, S, S)} tensor on {dev}")
-            if call.lens is None:
-                with guard(dev):
-                    m = mask != 0
-                    call.lens = (S - m[:, 0, :].sum(-1)).to(torch.int64)
-                    if self.validate_mask:
-                        want = torch.arange(S, device=dev)[None, None, :] >= call.lens[:, None, None]
-                        if not bool((m == want).all()):
-                            raise ValueError("mask is not a key-padding mask: mask[b, i, j] must equal j >= lens[b] for every i")
+        self._key_lengths(call, mask, lens, S, S, "[B, S, S]", "i", "j")  # (neither given: a null pointer, every key valid)
         call.p = self.p_drop if self.training else 0.0
-        call.keep = self._keep_masks(None if keep_mask is None else (keep_mask,), 1, (B, S, d), dev, call.p)[0]
+        call.keep = self._keep_masks(None if keep_mask is None else (keep_mask,), [(B, S, d)], call.device, call.p)[0]
         return call
 
     def forward(self, q, k, v, mask=None, lens=None, keep_mask=None):
@@ -127,7 +140,7 @@ class MultiHeadAttention(HipTrainModule):
         return outs
 
 
-class MultiHeadCrossAttention(HipTrainModule):
+class MultiHeadCrossAttention(_Attention):
     """Drop-in for ``MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=0.1)`` used as ``FFTBlock2.crs_attn``
     (transformer/Layers.py:61-64): mel-frame queries against phoneme keys, forward AND backward in HIP (csrc/xattngrad.hip, ``ns_xg_*``).
     The same parameter names, so ``mel_encoder.layer_stack.N.crs_attn.*`` loads strictly.
@@ -152,28 +165,9 @@ class MultiHeadCrossAttention(HipTrainModule):
     Raises on what it cannot do: ``k is not v``, ``d_k != d_v``, ``n_head * d_k != d_model``, d_model not 256 or 512, d_k not 64 or
     128, a mask that is not a key-padding mask."""
 
-    ABI, INPUT, PARAM_NAMES = "ns_xg", "q", PARAM_NAMES
-    FIELDS, WEIGHTS, GRADS = _lib.AG_NAMES, _lib.NsXgWeights, _lib.NsXgGrads
+    ABI, INPUT, D_K, INPUT_GRADS = "ns_xg", "q", (64, 128), ("dtgt", "dsrc")
+    WEIGHTS, GRADS = _lib.NsXgWeights, _lib.NsXgGrads
     WORKSPACES = WorkspaceCache("ns_xg_ws_bytes", ("B", "T", "L", "d", "H"))
-
-    def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
-        super().__init__()
-        if d_k != d_v:
-            raise ValueError(f"MultiHeadCrossAttention: d_k must equal d_v, got {d_k} and {d_v}")
-        if n_head * d_k != d_model:
-            raise ValueError(f"MultiHeadCrossAttention: n_head * d_k must equal d_model, got {n_head} * {d_k} and {d_model}")
-        if d_model not in (256, 512) or d_k not in (64, 128):
-            raise ValueError(f"MultiHeadCrossAttention: d_model must be 256 or 512 and d_k 64 or 128, got {d_model} and {d_k}")
-        if not 0.0 <= float(dropout) < 1.0:
-            raise ValueError(f"MultiHeadCrossAttention: dropout must lie in [0, 1), got {dropout}")
-        self.n_head, self.d_k, self.d_v, self.d_model = n_head, d_k, d_v, d_model
-        self.p_drop = float(dropout)
-        self.w_qs = torch.nn.Linear(d_model, n_head * d_k)
-        self.w_ks = torch.nn.Linear(d_model, n_head * d_k)
-        self.w_vs = torch.nn.Linear(d_model, n_head * d_v)
-        self.layer_norm = torch.nn.LayerNorm(d_model)
-        self.fc = torch.nn.Linear(n_head * d_v, d_model)
-        self.validate_mask = True
 
     def _marshal(self, q, k, mask, lens, keep_mask):
         call = self._begin(q, self.d_model)
@@ -184,29 +178,16 @@ class MultiHeadCrossAttention(HipTrainModule):
             raise ValueError(f"k must be a float32 [B, L, {d}] tensor on {dev} with B = {B} and L > 0")
         L = k.shape[1]
         call.src = aligned(k.detach())
+        call.inputs.append(call.src)
         s = _lib.NsXgShape()
         s.B, s.T, s.L, s.d, s.H = B, T, L, d, self.n_head
         call.shape = s
-        if lens is not None:
-            if not isinstance(lens, torch.Tensor) or tuple(lens.shape) != (B,) or lens.device != dev or lens.dtype not in (torch.int64, torch.int32):
-                raise ValueError(f"lens must be an int64 [B] = {(B,)} tensor on {dev}")
-            call.lens = lens.to(torch.int64).contiguous()
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, T, L) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != dev:
-                raise ValueError(f"mask must be a bool [B, T, L] = {(B, T, L)} tensor on {dev}")
-            if call.lens is None:
-                with guard(dev):
-                    m = mask != 0
-                    call.lens = (L - m[:, 0, :].sum(-1)).to(torch.int64)
-                    if self.validate_mask:
-                        want = torch.arange(L, device=dev)[None, None, :] >= call.lens[:, None, None]
-                        if not bool((m == want).all()):
-                            raise ValueError("mask is not a key-padding mask: mask[b, t, l] must equal l >= lens[b] for every t")
-        if call.lens is None:
+        self._key_lengths(call, mask, lens, T, L, "[B, T, L]", "t", "l")
+        if call.lens is None:  # (ns_xg_* takes no null pointer: full lengths)
             with guard(dev):
                 call.lens = torch.full((B,), L, dtype=torch.int64, device=dev)
         call.p = self.p_drop if self.training else 0.0
-        call.keep = self._keep_masks(None if keep_mask is None else (keep_mask,), 1, (B, T, d), dev, call.p)[0]
+        call.keep = self._keep_masks(None if keep_mask is None else (keep_mask,), [(B, T, d)], dev, call.p)[0]
         return call
 
     def forward(self, q, k, v, mask=None, lens=None, keep_mask=None):
@@ -243,11 +224,7 @@ class MultiHeadCrossAttention(HipTrainModule):
                 raise ValueError(f"the map's gradient must be a float32 {(s.B, s.H, s.T, s.L)} tensor on {dev}")
             g, attn = aligned(g), aligned(attn.detach())
             d_attn = None if d_attn is None else aligned(d_attn)
-            outs = [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None
-                    for t, n in zip([call.x, call.src] + call.params, need)]
-            d = self.GRADS()
-            for f, o in zip(("dtgt", "dsrc") + tuple(self.FIELDS), outs):
-                setattr(d, f, o.data_ptr() if o is not None else None)
+            outs, d = self._grad_block(call, need)
             ws, _ = self._workspace(call, save=False)
             self._done(self._lib.ns_xg_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.src), _lib.ptr(call.lens),
                                                 _lib.ptr(call.keep), call.p, _lib.ptr(saved), _lib.ptr(attn), _lib.ptr(g), _lib.ptr(d_attn),

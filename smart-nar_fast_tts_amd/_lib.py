@@ -153,16 +153,26 @@ class NsGlConfig(C.Structure):
 
 _P, _I, _F, _Z, _S = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
 
+
+def _handle_family(prefix: str, config_ptr) -> dict:
+    """The life cycle every native handle has (csrc/host_core.h; driven by _handle.NativeHandle); ``config_ptr`` is what
+    ``{prefix}_create`` takes for its config struct."""
+    return {
+        f"{prefix}_abi_version": (_I, []),
+        f"{prefix}_create": (_I, [config_ptr, C.POINTER(_P)]),
+        f"{prefix}_destroy": (None, [_P]),
+        f"{prefix}_arena_bytes": (_Z, [_P]),
+        f"{prefix}_bind_arena": (_I, [_P, _P, _Z]),
+        f"{prefix}_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
+        f"{prefix}_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
+        f"{prefix}_finalize_weights": (_I, [_P, _P]),
+    }
+
+
 # name -> (restype, argtypes); must list every symbol include/nar_fs2.h declares
 SIGNATURES = {
     "ns_last_error": (C.c_char_p, []),
-    "ns_create": (_I, [C.POINTER(NsConfig), C.POINTER(_P)]),
-    "ns_destroy": (None, [_P]),
-    "ns_arena_bytes": (_Z, [_P]),
-    "ns_bind_arena": (_I, [_P, _P, _Z]),
-    "ns_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
-    "ns_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
-    "ns_finalize_weights": (_I, [_P, _P]),
+    **_handle_family("ns", C.POINTER(NsConfig)),
     "ns_adopt_arena": (_I, [_P]),
     "ns_encoder_ws_bytes": (_Z, [_P, _I, _I]),
     "ns_decoder_ws_bytes": (_Z, [_P, _I, _I, _I]),
@@ -180,7 +190,6 @@ SIGNATURES = {
     "ns_plan_row_tile": (_I, [_I, _I]),
     "ns_plan_row_tile_k": (_I, [_I, _I, _I]),
     "ns_acc_chunk": (_I, []),
-    "ns_abi_version": (_I, []),
     "ns_plan_attention_split": (_I, [_I, _I, _I, _I]),
     "ns_op_ws_bytes": (_Z, [_P, _I, _I]),
     "ns_op_mask_from_lengths": (_I, [_P, _I, _I, _P, _P]),
@@ -230,15 +239,8 @@ SIGNATURES = {
     "ns_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "ns_profile_read_slot": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     # HiFi-GAN vocoder (vocoder.py; the config pointer is a vocoder.NsVocConfig)
-    "ns_voc_abi_version": (_I, []),
-    "ns_voc_create": (_I, [_P, C.POINTER(_P)]),
-    "ns_voc_destroy": (None, [_P]),
+    **_handle_family("ns_voc", _P),
     "ns_voc_set_matmul": (_I, [_P, _I]),
-    "ns_voc_arena_bytes": (_Z, [_P]),
-    "ns_voc_bind_arena": (_I, [_P, _P, _Z]),
-    "ns_voc_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
-    "ns_voc_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
-    "ns_voc_finalize_weights": (_I, [_P, _P]),
     "ns_voc_ws_bytes": (_Z, [_P, _I, _I]),
     "ns_voc_forward": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "ns_voc_op_conv": (_I, [_P, _S, _P, _I, _I, _P, _P]),
@@ -247,14 +249,7 @@ SIGNATURES = {
     "ns_voc_op_stage_ws_bytes": (_Z, [_P, _I, _I, _I]),
     "ns_voc_op_stage": (_I, [_P, _I, _P, _I, _I, _P, _P, _Z, _P]),
     # reference-mel aligner (model.FastSpeech2Align.align; the config pointer is the model's NsConfig)
-    "ns_aln_abi_version": (_I, []),
-    "ns_aln_create": (_I, [C.POINTER(NsConfig), C.POINTER(_P)]),
-    "ns_aln_destroy": (None, [_P]),
-    "ns_aln_arena_bytes": (_Z, [_P]),
-    "ns_aln_bind_arena": (_I, [_P, _P, _Z]),
-    "ns_aln_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
-    "ns_aln_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
-    "ns_aln_finalize_weights": (_I, [_P, _P]),
+    **_handle_family("ns_aln", C.POINTER(NsConfig)),
     "ns_aln_ws_bytes": (_Z, [_P, _I, _I, _I]),
     "ns_aln_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ns_aln_op_cross_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
@@ -264,14 +259,7 @@ SIGNATURES = {
     "ns_loss_ws_bytes": (_Z, [_I, _I, _I]),
     "ns_loss_forward": (_I, [C.POINTER(NsLossArgs), _P, _Z, _P, _P]),
     # wave-to-mel front end (audio.TacotronSTFT)
-    "ns_mel_abi_version": (_I, []),
-    "ns_mel_create": (_I, [C.POINTER(NsMelConfig), C.POINTER(_P)]),
-    "ns_mel_destroy": (None, [_P]),
-    "ns_mel_arena_bytes": (_Z, [_P]),
-    "ns_mel_bind_arena": (_I, [_P, _P, _Z]),
-    "ns_mel_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
-    "ns_mel_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
-    "ns_mel_finalize_weights": (_I, [_P, _P]),
+    **_handle_family("ns_mel", C.POINTER(NsMelConfig)),
     "ns_mel_frames": (C.c_int64, [C.c_int64, C.c_int32]),
     "ns_mel_ws_bytes": (_Z, [_P, _I, C.c_int64]),
     "ns_mel_forward": (_I, [_P, _P, C.c_int64, _P, _I, C.c_int64, _I, _P, _P, _P, _P, _Z, _P]),
@@ -279,14 +267,7 @@ SIGNATURES = {
     "ns_mel_op_stft": (_I, [_P, _P, _I, _I, _P, _P]),
     "ns_mel_op_project": (_I, [_P, _P, _P, _I, _I, C.c_int64, _I, _P, _P, _P]),
     # Griffin-Lim mel-to-wave (audio.STFT, audio.griffin_lim, audio.mel_to_wave)
-    "ns_gl_abi_version": (_I, []),
-    "ns_gl_create": (_I, [C.POINTER(NsGlConfig), C.POINTER(_P)]),
-    "ns_gl_destroy": (None, [_P]),
-    "ns_gl_arena_bytes": (_Z, [_P]),
-    "ns_gl_bind_arena": (_I, [_P, _P, _Z]),
-    "ns_gl_set_weight": (_I, [_P, _S, _P, C.POINTER(C.c_int64), _I]),
-    "ns_gl_check_weight": (_I, [_P, _S, C.POINTER(C.c_int64), _I]),
-    "ns_gl_finalize_weights": (_I, [_P, _P]),
+    **_handle_family("ns_gl", C.POINTER(NsGlConfig)),
     "ns_gl_ws_bytes": (_Z, [_P, _I, _I]),
     "ns_gl_forward": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, C.c_int64, _P, _P, _Z, _P]),
     "ns_gl_forward_mag": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, C.c_int64, _P, _P, _Z, _P]),

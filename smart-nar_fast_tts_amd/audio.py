@@ -16,12 +16,12 @@ DEVIATIONS from the reference, both documented in DESIGN.md §15:
 from __future__ import annotations
 
 import ctypes as C
-from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._handle import DeviceModule, host_f32
 
 CLIP_VAL = 1e-5  # dynamic_range_compression's default, the only value the reference uses (audio_processing.py:85)
 
@@ -136,53 +136,37 @@ def gl_config_struct(filter_length, hop_length, win_length, n_mel, scaling=SPEC_
     return c
 
 
-class _DeviceModule:
-    """The nn.Module-shaped part both front-end classes share: eval / train / to / cuda and one workspace per HIP stream.  A subclass
-    provides ``_upload()`` and sets ``_device``, ``_arena``, ``_ws``, ``training``."""
-
-    MAX_WORKSPACE_STREAMS = 4
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("the front end has no trainable state")
-        return self.eval()
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("this front end runs on an MI355X only (device must be 'cuda[:N]'); there is no CPU path")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._device != device:
-            self._device = device
-            self._ws = OrderedDict()
-            self._arena = None
-            self._upload()
-        return self
-
-    def cuda(self, device=None):
-        return self.to("cuda" if device is None else device)
-
-    def _workspace(self, nbytes: int, stream_handle: int) -> torch.Tensor:
-        w = self._ws.get(stream_handle)
-        if w is None or w.numel() < nbytes:
-            self._ws.pop(stream_handle, None)
-            w = torch.empty(int(nbytes), dtype=torch.uint8, device=self._device)
-            self._ws[stream_handle] = w
-        self._ws.move_to_end(stream_handle)
-        while len(self._ws) > self.MAX_WORKSPACE_STREAMS:
-            self._ws.popitem(last=False)
-        return w
-
-    def release_workspaces(self):
-        self._ws = OrderedDict()
+def _device_lens(lens, B, dev, what, refuse, data="the data", one_message=False):
+    """Per-utterance lengths as a device int64 [B].  A device tensor is checked for dtype, shape and device only: its values cannot
+    be validated without a read and are clamped by the kernels.  Host values (a sequence, an array, a CPU tensor) are validated one
+    by one: ``refuse(v)`` returns what follows ``"{what}[b] = v"`` in the ValueError, or None.  ``data`` names the tensor the lengths
+    belong to; ``one_message``: ``STFT.transform``'s wording, one ValueError for dtype, shape and device together."""
+    if torch.is_tensor(lens) and lens.is_cuda:
+        shaped = lens.dtype == torch.long and tuple(lens.shape) == (B,)
+        if one_message:
+            if not shaped or lens.device != dev:
+                raise ValueError(f"device {what} must be int64 [{B}] on {dev}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+        elif lens.device != dev:
+            raise RuntimeError(f"{what} is on {lens.device}, {data} on {dev}")
+        elif not shaped:
+            raise ValueError(f"device {what} must be int64 [{B}], got {lens.dtype} {tuple(lens.shape)}")
+        return lens.contiguous()
+    host = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
+    if one_message:
+        if host.dtype.kind not in "iu" or host.shape != (B,):
+            raise ValueError(f"{what} must be {B} integers, got {host.dtype} {host.shape}")
+    elif host.dtype.kind not in "iu":
+        raise ValueError(f"{what} must hold integers, got {host.dtype}")
+    elif host.shape != (B,):
+        raise ValueError(f"{what} must have shape ({B},), got {host.shape}")
+    for b, v in enumerate(host.tolist()):
+        why = refuse(v)
+        if why:
+            raise ValueError(f"{what}[{b}] = {v}{why}")
+    return torch.as_tensor(host.astype(np.int64)).to(dev)
 
 
-class TacotronSTFT(_DeviceModule):
+class TacotronSTFT(DeviceModule):
     """Drop-in for the reference's ``TacotronSTFT(filter_length, hop_length, win_length, n_mel_channels, sampling_rate, mel_fmin,
     mel_fmax)`` on the MI355X.  ``mel_basis=`` hands in a filter bank (e.g. librosa's, from a saved ``state_dict()``) in place of the
     Slaney restatement.
@@ -201,19 +185,11 @@ class TacotronSTFT(_DeviceModule):
         self.filter_length, self.hop_length, self.win_length = int(filter_length), int(hop_length), int(win_length)
         self.n_mel_channels, self.sampling_rate = int(n_mel_channels), sampling_rate
         self.mel_fmin, self.mel_fmax = mel_fmin, mel_fmax
-        self._lib = _lib.load()
-        hd = C.c_void_p()
-        _lib.check(self._lib.ns_mel_create(C.byref(config_struct(filter_length, hop_length, win_length, n_mel_channels)), C.byref(hd)), "TacotronSTFT")
-        self._h = hd
+        self._open("ns_mel", config_struct(filter_length, hop_length, win_length, n_mel_channels), "TacotronSTFT")
         if mel_basis is None:
             mel_basis = slaney_mel_basis(sampling_rate, self.filter_length, self.n_mel_channels, mel_fmin, mel_fmax)
-        self._device = None
-        self._arena = None
-        self._ws = OrderedDict()
-        self._sd = None
         self._stft_fn = None
         self.mel_lens = None
-        self.training = False
         self.load_state_dict({"stft_fn.forward_basis": stft_forward_basis(self.filter_length, self.win_length), "mel_basis": mel_basis})
 
     @classmethod
@@ -223,15 +199,7 @@ class TacotronSTFT(_DeviceModule):
         return cls(p["stft"]["filter_length"], p["stft"]["hop_length"], p["stft"]["win_length"], p["mel"]["n_mel_channels"],
                    p["audio"]["sampling_rate"], p["mel"]["mel_fmin"], p["mel"]["mel_fmax"], mel_basis=mel_basis)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ns_mel_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    # ---- nn.Module-shaped surface (eval / train / to / cuda: _DeviceModule) ----------------------
+    # ---- nn.Module-shaped surface (eval / train / to / cuda / state_dict: _handle.DeviceModule) ------
     @property
     def stft_fn(self) -> "STFT":
         """The reference's ``TacotronSTFT.stft_fn`` (stft.py:144), with this module's forward basis and mel basis."""
@@ -251,39 +219,21 @@ class TacotronSTFT(_DeviceModule):
     def forward_basis(self) -> torch.Tensor:
         return torch.from_numpy(self._sd["stft_fn.forward_basis"].copy())
 
-    def state_dict(self):
-        return OrderedDict((k, torch.from_numpy(v.copy())) for k, v in self._sd.items())
-
     def load_state_dict(self, state_dict, strict: bool = True):
         """Keys of the reference module: ``stft_fn.forward_basis``, ``mel_basis`` (either may be absent: the current one stays) and
         ``stft_fn.inverse_basis`` (accepted, ignored).  Unknown keys and shape mismatches raise before anything is replaced."""
         new, errors = dict(self._sd or {}), []
         for k, t in dict(state_dict).items():
-            a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            shape = (C.c_int64 * a.ndim)(*a.shape)
-            if self._lib.ns_mel_check_weight(self._h, k.encode(), shape, a.ndim) != 0:
-                errors.append(self._lib.ns_last_error().decode())
+            a = host_f32(t)
+            err = self._h.check_weight(k, a)
+            if err:
+                errors.append(err)
             elif k != "stft_fn.inverse_basis":
                 new[k] = a
         if errors:
             raise RuntimeError("load_state_dict: " + "; ".join(errors))
-        self._sd = new
         self._stft_fn = None  # rebuilt from the new bases on next use
-        if self._device is not None:
-            self._upload()
-        return [], []
-
-    def _upload(self):
-        nbytes = self._lib.ns_mel_arena_bytes(self._h)
-        with torch.cuda.device(self._device):
-            arena = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
-            _lib.check(self._lib.ns_mel_bind_arena(self._h, _lib.ptr(arena), nbytes), "ns_mel_bind_arena")
-            for k, a in self._sd.items():
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                _lib.check(self._lib.ns_mel_set_weight(self._h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim), "load_state_dict")
-            _lib.check(self._lib.ns_mel_finalize_weights(self._h, _lib.stream_ptr(self._device)), "load_state_dict")
-            self._arena = arena
+        return self._loaded(new)
 
     # ---- forward -------------------------------------------------------------------------------
     def frames(self, n: int) -> int:
@@ -310,26 +260,13 @@ class TacotronSTFT(_DeviceModule):
             raise ValueError(f"max_mel_len must be >= 1, got {max_mel_len}")
         dev = y.device
         half = self.filter_length // 2
-        if wav_lens is None:
-            wav_lens = [n] * B
-        if torch.is_tensor(wav_lens) and wav_lens.is_cuda:
-            if wav_lens.device != dev:
-                raise RuntimeError(f"wav_lens is on {wav_lens.device}, y on {dev}")
-            if wav_lens.dtype != torch.long or tuple(wav_lens.shape) != (B,):
-                raise ValueError(f"device wav_lens must be int64 [{B}], got {wav_lens.dtype} {tuple(wav_lens.shape)}")
-            lens = wav_lens.contiguous()
-        else:
-            host = np.asarray(wav_lens.cpu() if torch.is_tensor(wav_lens) else wav_lens)
-            if host.dtype.kind not in "iu":
-                raise ValueError(f"wav_lens must hold integers, got {host.dtype}")
-            if host.shape != (B,):
-                raise ValueError(f"wav_lens must have shape ({B},), got {host.shape}")
-            for b, v in enumerate(host.tolist()):
-                if v <= half:
-                    raise ValueError(f"wav_lens[{b}] = {v}: a wave must be longer than filter_length / 2 = {half} samples (the reflect pad, stft.py:60-64)")
-                if v > n:
-                    raise ValueError(f"wav_lens[{b}] = {v} exceeds the {n} samples of y")
-            lens = torch.as_tensor(host.astype(np.int64)).to(dev)
+
+        def refuse(v):
+            if v <= half:
+                return f": a wave must be longer than filter_length / 2 = {half} samples (the reflect pad, stft.py:60-64)"
+            return f" exceeds the {n} samples of y" if v > n else None
+
+        lens = _device_lens([n] * B if wav_lens is None else wav_lens, B, dev, "wav_lens", refuse, data="y")
         self.to(dev)
         y = y.contiguous()
         with torch.cuda.device(dev):
@@ -339,7 +276,7 @@ class TacotronSTFT(_DeviceModule):
             if B > 0:
                 stream = torch.cuda.current_stream(dev).cuda_stream
                 nbytes = int(self._lib.ns_mel_ws_bytes(self._h, B, n))
-                ws = self._workspace(nbytes, stream)
+                ws = self._ws.take(self._device, nbytes, stream)
                 _lib.check(self._lib.ns_mel_forward(self._h, _lib.ptr(y), n, _lib.ptr(lens), B, n, T, _lib.ptr(mel), _lib.ptr(energy),
                                                     _lib.ptr(mel_lens), _lib.ptr(ws), ws.numel(), C.c_void_p(stream)), "ns_mel_forward")
         self.mel_lens = mel_lens
@@ -361,29 +298,16 @@ def get_mel_from_wav(audio, _stft: TacotronSTFT):
 
 # ---- Griffin-Lim: mel -> wave without trained weights (ns_gl_*) ------------------------------------------------------
 def _as_long_lens(lens, B, T, dev, fl, hop, drop, what):
-    """Per-utterance frame counts as a device int64 [B].  Host values are validated (too short for the reflect pad of the loop's
-    transform, stft.py:60-64, or beyond the T frames given: ValueError); device values cannot be without a read and are clamped by the
-    kernels (a too-short utterance then gives a zero wave of length 0)."""
-    if lens is None:
-        lens = [T] * B
-    if torch.is_tensor(lens) and lens.is_cuda:
-        if lens.device != dev:
-            raise RuntimeError(f"{what} is on {lens.device}, the data on {dev}")
-        if lens.dtype != torch.long or tuple(lens.shape) != (B,):
-            raise ValueError(f"device {what} must be int64 [{B}], got {lens.dtype} {tuple(lens.shape)}")
-        return lens.contiguous()
-    host = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
-    if host.dtype.kind not in "iu":
-        raise ValueError(f"{what} must hold integers, got {host.dtype}")
-    if host.shape != (B,):
-        raise ValueError(f"{what} must have shape ({B},), got {host.shape}")
-    for b, v in enumerate(host.tolist()):
+    """Per-utterance frame counts for Griffin-Lim.  Host values too short for the reflect pad of the loop's transform (stft.py:60-64)
+    or beyond the T frames given are refused; on the device a too-short utterance gives a zero wave of length 0."""
+    def refuse(v):
         if v > T:
-            raise ValueError(f"{what}[{b}] = {v} exceeds the {T} frames given")
+            return f" exceeds the {T} frames given"
         if hop * (v - drop - 1) <= fl // 2:
-            raise ValueError(f"{what}[{b}] = {v}: too short — Griffin-Lim's signal of hop_length * (frames - 1) samples must be longer than "
-                             f"filter_length / 2 = {fl // 2} (the reflect pad, stft.py:60-64)")
-    return torch.as_tensor(host.astype(np.int64)).to(dev)
+            return (f": too short — Griffin-Lim's signal of hop_length * (frames - 1) samples must be longer than "
+                    f"filter_length / 2 = {fl // 2} (the reflect pad, stft.py:60-64)")
+
+    return _device_lens([T] * B if lens is None else lens, B, dev, what, refuse)
 
 
 def _check_device_f32(t, what, ndim):
@@ -397,7 +321,7 @@ def _check_device_f32(t, what, ndim):
         raise RuntimeError(f"{what} must live on the MI355X (cuda) device; there is no CPU path")
 
 
-class STFT(_DeviceModule):
+class STFT(DeviceModule):
     """The reference's ``STFT(filter_length, hop_length, win_length, window="hann")`` (audio/stft.py:15-127) on the MI355X.
     ``transform`` and ``inverse`` take and return the reference's layouts, for batches of variable-length utterances (``lens``).
     ``n_mel_channels`` / ``mel_basis`` (not reference arguments) give the handle the mel basis ``mel_to_wave`` needs;
@@ -413,35 +337,16 @@ class STFT(_DeviceModule):
         self.sampling_rate = sampling_rate
         if (n_mel_channels is None) != (mel_basis is None):
             raise ValueError("n_mel_channels and mel_basis come together")
-        self._lib = _lib.load()
-        hd = C.c_void_p()
         # a bare STFT has no mel stage: the smallest legal n_mel, and no mel_basis is ever loaded
-        cfg = gl_config_struct(filter_length, hop_length, win_length, 4 if n_mel_channels is None else n_mel_channels)
-        _lib.check(self._lib.ns_gl_create(C.byref(cfg), C.byref(hd)), "STFT")
-        self._h = hd
+        self._open("ns_gl", gl_config_struct(filter_length, hop_length, win_length, 4 if n_mel_channels is None else n_mel_channels), "STFT")
         self.n_mel_channels = None if n_mel_channels is None else int(n_mel_channels)
         self._mel_basis = None if mel_basis is None else np.ascontiguousarray(mel_basis, dtype=np.float32)
-        if self._mel_basis is not None:
-            shape = (C.c_int64 * 2)(*self._mel_basis.shape) if self._mel_basis.ndim == 2 else None
-            if shape is None or self._lib.ns_gl_check_weight(self._h, b"mel_basis", shape, 2) != 0:
-                raise RuntimeError(f"STFT: mel_basis must be [{self.n_mel_channels}, {self.cutoff}], got {self._mel_basis.shape}")
-        self._device = None
-        self._arena = None
-        self._ws = OrderedDict()
-        self._sd = None
+        if self._mel_basis is not None and (self._mel_basis.ndim != 2 or self._h.check_weight("mel_basis", self._mel_basis)):
+            raise RuntimeError(f"STFT: mel_basis must be [{self.n_mel_channels}, {self.cutoff}], got {self._mel_basis.shape}")
         self.wave_lens = None
         self.frame_lens = None
-        self.training = False
         self.load_state_dict({"forward_basis": stft_forward_basis(self.filter_length, self.win_length),
                               "inverse_basis": stft_inverse_basis(self.filter_length, self.hop_length, self.win_length)})
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ns_gl_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     @property
     def forward_basis(self) -> torch.Tensor:
@@ -451,47 +356,31 @@ class STFT(_DeviceModule):
     def inverse_basis(self) -> torch.Tensor:
         return torch.from_numpy(self._sd["inverse_basis"].copy())
 
-    def state_dict(self):
-        return OrderedDict((k, torch.from_numpy(v.copy())) for k, v in self._sd.items())
-
     def load_state_dict(self, state_dict, strict: bool = True):
         """Keys of the reference module: ``forward_basis``, ``inverse_basis`` (either may be absent: the current one stays)."""
         new, errors = dict(self._sd or {}), []
         for k, t in dict(state_dict).items():
-            a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            shape = (C.c_int64 * a.ndim)(*a.shape)
-            if k not in ("forward_basis", "inverse_basis"):
-                errors.append(f"unexpected key '{k}'")
-            elif self._lib.ns_gl_check_weight(self._h, ("stft_fn." + k).encode(), shape, a.ndim) != 0:
-                errors.append(self._lib.ns_last_error().decode())
+            a = host_f32(t)
+            err = self._h.check_weight("stft_fn." + k, a) if k in ("forward_basis", "inverse_basis") else f"unexpected key '{k}'"
+            if err:
+                errors.append(err)
             else:
                 new[k] = a
         if errors:
             raise RuntimeError("load_state_dict: " + "; ".join(errors))
-        self._sd = new
-        if self._device is not None:
-            self._upload()
-        return [], []
+        return self._loaded(new)
 
-    def _upload(self):
-        nbytes = self._lib.ns_gl_arena_bytes(self._h)
+    def _weights(self):
+        """The library's names: the two bases under ``stft_fn.``, and ``mel_basis`` when this STFT was given one."""
         weights = {"stft_fn." + k: a for k, a in self._sd.items()}
         if self._mel_basis is not None:
             weights["mel_basis"] = self._mel_basis
-        with torch.cuda.device(self._device):
-            arena = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
-            _lib.check(self._lib.ns_gl_bind_arena(self._h, _lib.ptr(arena), nbytes), "ns_gl_bind_arena")
-            for k, a in weights.items():
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                _lib.check(self._lib.ns_gl_set_weight(self._h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim), "load_state_dict")
-            _lib.check(self._lib.ns_gl_finalize_weights(self._h, _lib.stream_ptr(self._device)), "load_state_dict")
-            self._arena = arena
+        return weights
 
     def _ws_for(self, B, T, dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         nbytes = int(self._lib.ns_gl_ws_bytes(self._h, B, T))
-        return self._workspace(nbytes, stream), stream
+        return self._ws.take(self._device, nbytes, stream), stream
 
     # ---- the reference's three methods -------------------------------------------------------------
     def transform(self, input_data, lens=None):
@@ -502,21 +391,13 @@ class STFT(_DeviceModule):
         B, n = int(input_data.shape[0]), int(input_data.shape[1])
         dev, half = input_data.device, self.filter_length // 2
         T = n // self.hop_length + 1
-        if lens is None:
-            lens = [n] * B
-        if torch.is_tensor(lens) and lens.is_cuda:
-            if lens.dtype != torch.long or tuple(lens.shape) != (B,) or lens.device != dev:
-                raise ValueError(f"device lens must be int64 [{B}] on {dev}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
-            wl = lens.contiguous()
-        else:
-            host = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
-            if host.dtype.kind not in "iu" or host.shape != (B,):
-                raise ValueError(f"lens must be {B} integers, got {host.dtype} {host.shape}")
-            for b, v in enumerate(host.tolist()):
-                if v <= half or v > n:
-                    raise ValueError(f"lens[{b}] = {v}: a signal must be longer than filter_length / 2 = {half} samples (the reflect pad, "
-                                     f"stft.py:60-64) and within the {n} given")
-            wl = torch.as_tensor(host.astype(np.int64)).to(dev)
+
+        def refuse(v):
+            if v <= half or v > n:
+                return (f": a signal must be longer than filter_length / 2 = {half} samples (the reflect pad, "
+                        f"stft.py:60-64) and within the {n} given")
+
+        wl = _device_lens([n] * B if lens is None else lens, B, dev, "lens", refuse, one_message=True)
         self.to(dev)
         x = input_data.contiguous()
         with torch.cuda.device(dev):

@@ -11,12 +11,12 @@ that torch's backward of the model produces from these."""
 from __future__ import annotations
 
 import ctypes as C
-from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._handle import StreamWorkspaces
 from ._train import guard
 
 _TRAINING = "training is out of scope for this path (SURVEY.md §2); only eval() is supported"
@@ -49,7 +49,7 @@ class FastSpeech2Loss:
             if level not in ("phoneme_level", "frame_level"):
                 raise ValueError(f"preprocessing.{what}.feature must be 'phoneme_level' or 'frame_level' (model/loss.py:199-211), got {level!r}")
         self._lib = _lib.load()
-        self._ws = OrderedDict()  # (device index, stream handle) -> partial-slot workspace, least recently used first
+        self._ws = StreamWorkspaces(self.MAX_WORKSPACE_STREAMS, per_device=True, slack=True)
         self.training = False
 
     # ---- nn.Module-shaped surface ------------------------------------------------------------
@@ -70,15 +70,7 @@ class FastSpeech2Loss:
 
     def workspace(self, device, nbytes: int) -> torch.Tensor:
         """The partial-slot workspace of the current stream of ``device`` (one per stream: calls on different streams may overlap)."""
-        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-        w = self._ws.get(key)
-        if w is None or w.numel() < nbytes:
-            w = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
-            self._ws[key] = w
-        self._ws.move_to_end(key)
-        while len(self._ws) > self.MAX_WORKSPACE_STREAMS:
-            self._ws.popitem(last=False)
-        return w
+        return self._ws.take(device, nbytes)
 
     # ---- forward -------------------------------------------------------------------------------
     def forward(self, inputs, predictions):

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from . import workload as wl
+from ._handle import NativeHandle, cuda_device, host_f32
 
 
 def config_struct(preprocess_config: dict, model_config: dict) -> _lib.NsConfig:
@@ -144,9 +145,7 @@ class FastSpeech2Align:
         self.preprocess_config = preprocess_config
         self._lib = _lib.load()
         self._cfg = config_struct(preprocess_config, model_config)
-        h = C.c_void_p()
-        _lib.check(self._lib.ns_create(C.byref(self._cfg), C.byref(h)), "ns_create")
-        self._h = h
+        self._h = NativeHandle("ns", self._cfg, "ns_create")
         self._device = None
         self._arena = None
         self._ws = OrderedDict()  # (kind, stream handle) -> scratch tensor, least recently used first
@@ -183,15 +182,9 @@ class FastSpeech2Align:
                 self._stats = json.load(f)
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ns_destroy(self._h)
-                self._h = None
-            if getattr(self, "_aln_h", None):
-                self._lib.ns_aln_destroy(self._aln_h)
-                self._aln_h = None
-        except Exception:
-            pass
+        for h in (getattr(self, "_h", None), getattr(self, "_aln_h", None)):
+            if h is not None:
+                h.close()
 
     # ---- nn.Module-shaped surface ------------------------------------------------------------
     def eval(self):
@@ -207,11 +200,7 @@ class FastSpeech2Align:
         return self
 
     def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("this implementation runs on an MI355X only (device must be 'cuda[:N]'); there is no CPU path")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = cuda_device(device, "implementation")
         if self._device != device:
             old_arena = self._arena
             self._device = device
@@ -320,16 +309,11 @@ class FastSpeech2Align:
 
     def _stage(self, key: str, a: np.ndarray):
         """Hand one (already validated) entry to the native staging area."""
-        shape = (C.c_int64 * a.ndim)(*a.shape)
-        _lib.check(self._lib.ns_set_weight(self._h, key.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim),
-                   "load_state_dict")
+        self._h.set_weight(key, a, "load_state_dict")
 
     def _check(self, key: str, a: np.ndarray) -> str:
         """'' when the native side accepts this key name and shape, else its error text.  No side effect on the model."""
-        shape = (C.c_int64 * a.ndim)(*a.shape)
-        if self._lib.ns_check_weight(self._h, key.encode(), shape, a.ndim) == 0:
-            return ""
-        return self._lib.ns_last_error().decode()
+        return self._h.check_weight(key, a)
 
     def load_state_dict(self, state_dict, strict: bool = True, *, _internal: bool = False):
         """Accepts the reference's checkpoint["model"] (utils/model.py:21-22).  ``mel_encoder.*`` entries (the reference-mel
@@ -354,8 +338,7 @@ class FastSpeech2Align:
                 continue
             if k.endswith("num_batches_tracked"):
                 continue
-            a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
+            a = host_f32(v)
             err = self._check(k, a)
             if err and "unexpected key" in err:
                 unexpected.append(k)
@@ -401,10 +384,7 @@ class FastSpeech2Align:
         return missing, unexpected
 
     def _bind_arena(self):
-        nbytes = self._lib.ns_arena_bytes(self._h)
-        with torch.cuda.device(self._device):
-            self._arena = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
-            _lib.check(self._lib.ns_bind_arena(self._h, _lib.ptr(self._arena), nbytes), "ns_bind_arena")
+        self._arena = self._h.bind_arena(self._device)
 
     def _upload(self, staged: bool = False):
         if self._arena is None:
@@ -413,7 +393,7 @@ class FastSpeech2Align:
             if not staged:
                 for k, a in self._sd.items():
                     self._stage(k, a)
-            _lib.check(self._lib.ns_finalize_weights(self._h, _lib.stream_ptr(self._device)), "load_state_dict")
+            self._h.finalize(self._device, "load_state_dict")
 
     def _ensure_weights(self):
         """The reference constructor leaves a runnable random-init module (model/fastspeech2_align.py:16-28); here the
@@ -469,30 +449,24 @@ class FastSpeech2Align:
             raise RuntimeError("align(): no aligner weights: load_state_dict() a checkpoint that holds the mel_encoder.* tensors "
                                "(the reference's MelEncoder, transformer/Models.py:103-138)")
         if self._aln_h is None:
-            h = C.c_void_p()
-            _lib.check(self._lib.ns_aln_create(C.byref(self._cfg), C.byref(h)), "ns_aln_create")
-            self._aln_h = h
+            self._aln_h = NativeHandle("ns_aln", self._cfg, "ns_aln_create")
         if self._aln_ready:
             return
         for k, a in self._aln_sd.items():
-            shape = (C.c_int64 * a.ndim)(*a.shape)
-            if self._lib.ns_aln_check_weight(self._aln_h, k.encode(), shape, a.ndim) != 0:
-                raise RuntimeError("align(): " + self._lib.ns_last_error().decode())
+            err = self._aln_h.check_weight(k, a)
+            if err:
+                raise RuntimeError("align(): " + err)
 
     def _ensure_aligner(self):
         """The aligner's arena: built and uploaded on the first align() after a load (or a move to another device)."""
         if self._aln_ready:
             return
-        lib = self._lib
         with torch.cuda.device(self._device):
             if self._aln_arena is None:
-                nbytes = lib.ns_aln_arena_bytes(self._aln_h)
-                self._aln_arena = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
-                _lib.check(lib.ns_aln_bind_arena(self._aln_h, _lib.ptr(self._aln_arena), nbytes), "ns_aln_bind_arena")
+                self._aln_arena = self._aln_h.bind_arena(self._device)
             for k, a in self._aln_sd.items():
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                _lib.check(lib.ns_aln_set_weight(self._aln_h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim), "align()")
-            _lib.check(lib.ns_aln_finalize_weights(self._aln_h, _lib.stream_ptr(self._device)), "align()")
+                self._aln_h.set_weight(k, a, "align()")
+            self._aln_h.finalize(self._device, "align()")
         self._aln_ready = True
 
     def align(self, texts, src_lens, max_src_len, mels, mel_lens, max_mel_len=None):

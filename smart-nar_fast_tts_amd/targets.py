@@ -7,11 +7,11 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
-from collections import OrderedDict
 
 import torch
 
 from . import _lib
+from ._handle import StreamWorkspaces
 from ._train import guard
 
 SORT_CAPACITY = 8192  # NS_VT_SORT_CAPACITY of include/nar_fs2.h (tests/test_variance_targets_host.py holds the two together)
@@ -40,20 +40,12 @@ class VarianceTargets:
         self.pitch_normalization = bool(pre["pitch"]["normalization"])
         self.energy_normalization = bool(pre["energy"]["normalization"])
         self._lib = _lib.load()
-        self._ws = OrderedDict()  # (device index, stream handle) -> workspace, least recently used first
+        self._ws = StreamWorkspaces(self.MAX_WORKSPACE_STREAMS, per_device=True, slack=True)
         self._state = None        # device [10] float64 = ns_vt_state, created on the first batch's device
 
     # ---- plumbing ------------------------------------------------------------------------------
     def workspace(self, device, nbytes: int) -> torch.Tensor:
-        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-        w = self._ws.get(key)
-        if w is None or w.numel() < nbytes:
-            w = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
-            self._ws[key] = w
-        self._ws.move_to_end(key)
-        while len(self._ws) > self.MAX_WORKSPACE_STREAMS:
-            self._ws.popitem(last=False)
-        return w
+        return self._ws.take(device, nbytes)
 
     def _state_on(self, dev) -> torch.Tensor:
         if self._state is None:

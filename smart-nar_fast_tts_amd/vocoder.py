@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import DeviceModule, host_f32
 
 DEFAULT_VOCODER = {"model": "HiFi-GAN", "speaker": "LJSpeech"}  # config/LJSpeech/model.yaml `vocoder`
 MAX_WAV_VALUE = 32768.0  # config/LJSpeech/preprocess.yaml preprocessing.audio.max_wav_value
@@ -67,7 +68,7 @@ def fold_weight_norm(weight_g, weight_v) -> torch.Tensor:
     return torch._weight_norm(v, g, 0)
 
 
-class Generator:
+class Generator(DeviceModule):
     """hifigan.Generator (resblock "1") for inference.  ``load_state_dict`` takes the checkpoint's ``generator`` entry — weight-norm
     ``weight_g`` / ``weight_v`` pairs, folded here exactly like ``remove_weight_norm`` — or plain ``weight`` tensors; unknown keys and
     shape mismatches raise before anything loaded is replaced.  ``remove_weight_norm()`` is then a no-op.
@@ -76,77 +77,27 @@ class Generator:
     inputs rounded to bf16 (round to nearest even), products summed in fp32; everything else stays fp32 (include/nar_fs2.h
     ns_voc_set_matmul).  The default "fp32" path is the one the library runs without the call.
 
-    Threading: one instance serves one host thread at a time; several HIP streams from that thread are fine (one workspace each)."""
+    eval / train / to / cuda / state_dict and the per-stream workspaces: ``_handle.DeviceModule``."""
 
-    MAX_WORKSPACE_STREAMS = 4
+    KIND = "vocoder"
+    NO_TRAINING = "the vocoder is inference-only"
+    PICKS_DEVICE_ON_LOAD = True
 
     def __init__(self, h, matmul: str = "fp32"):
         if matmul not in MATMUL_MODES:
             raise ValueError(f"matmul must be one of {sorted(MATMUL_MODES)}, got {matmul!r}")
         self.h = h if isinstance(h, AttrDict) else AttrDict(h)
-        self._lib = _lib.load()
         self._cfg = config_struct(self.h)
-        hd = C.c_void_p()
-        _lib.check(self._lib.ns_voc_create(C.byref(self._cfg), C.byref(hd)), "Generator")
-        self._h = hd
+        self._open("ns_voc", self._cfg, "Generator")
         self.matmul = matmul
         if matmul != "fp32":
             _lib.check(self._lib.ns_voc_set_matmul(self._h, MATMUL_MODES[matmul]), "Generator")
         self.hop = int(np.prod(self.h["upsample_rates"]))
         self.n_mel = int(self._cfg.n_mel)
-        self._device = None
-        self._arena = None
-        self._sd = None
-        self._ws = OrderedDict()
-        self.training = False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.ns_voc_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    # ---- nn.Module-shaped surface --------------------------------------------------------------
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("the vocoder is inference-only")
-        return self.eval()
 
     def remove_weight_norm(self):
         """Weights are folded when they are loaded (see load_state_dict): nothing left to remove."""
         return None
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("this vocoder runs on an MI355X only (device must be 'cuda[:N]'); there is no CPU path")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._device != device:
-            self._device = device
-            self._ws = OrderedDict()
-            self._arena = None
-            if self._sd is not None:
-                self._upload()
-        return self
-
-    def cuda(self, device=None):
-        return self.to("cuda" if device is None else device)
-
-    def state_dict(self):
-        return OrderedDict((k, torch.from_numpy(v.copy())) for k, v in (self._sd or {}).items())
-
-    def _check(self, key: str, a: np.ndarray) -> str:
-        shape = (C.c_int64 * a.ndim)(*a.shape)
-        if self._lib.ns_voc_check_weight(self._h, key.encode(), shape, a.ndim) == 0:
-            return ""
-        return self._lib.ns_last_error().decode()
 
     def load_state_dict(self, state_dict, strict: bool = True):
         folded, errors = OrderedDict(), []
@@ -170,9 +121,8 @@ class Generator:
         folded.update(sd)
         new = OrderedDict()
         for k, t in folded.items():
-            a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            err = self._check(k, a)
+            a = host_f32(t)
+            err = self._h.check_weight(k, a)
             if err:
                 errors.append(err)
                 continue
@@ -183,12 +133,7 @@ class Generator:
             errors.append("missing key(s): " + ", ".join(missing))
         if errors:
             raise RuntimeError("load_state_dict: " + "; ".join(errors))
-        self._sd = new
-        if self._device is None and torch.cuda.is_available():
-            self._device = torch.device("cuda", torch.cuda.current_device())
-        if self._device is not None:
-            self._upload()
-        return [], []
+        return self._loaded(new)
 
     def expected_keys(self):
         """Plain-weight key names of the native model, in load order."""
@@ -202,34 +147,9 @@ class Generator:
                         keys += [f"resblocks.{i * nk + j}.{w}.{n}.weight", f"resblocks.{i * nk + j}.{w}.{n}.bias"]
         return keys + ["conv_post.weight", "conv_post.bias"]
 
-    def _upload(self):
-        nbytes = self._lib.ns_voc_arena_bytes(self._h)
-        with torch.cuda.device(self._device):
-            self._arena = torch.empty(nbytes, dtype=torch.uint8, device=self._device)
-            _lib.check(self._lib.ns_voc_bind_arena(self._h, _lib.ptr(self._arena), nbytes), "ns_voc_bind_arena")
-            for k, a in self._sd.items():
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                _lib.check(self._lib.ns_voc_set_weight(self._h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim), "load_state_dict")
-            _lib.check(self._lib.ns_voc_finalize_weights(self._h, _lib.stream_ptr(self._device)), "load_state_dict")
-
     # ---- forward ---------------------------------------------------------------------------------
     def ws_bytes(self, B: int, T: int) -> int:
         return int(self._lib.ns_voc_ws_bytes(self._h, int(B), int(T)))
-
-    def _workspace(self, nbytes: int, stream_handle: int) -> torch.Tensor:
-        # one scratch buffer per stream (forwards on different streams may overlap on the GPU), LRU-bounded
-        w = self._ws.get(stream_handle)
-        if w is None or w.numel() < nbytes:
-            self._ws.pop(stream_handle, None)
-            w = torch.empty(int(nbytes), dtype=torch.uint8, device=self._device)
-            self._ws[stream_handle] = w
-        self._ws.move_to_end(stream_handle)
-        while len(self._ws) > self.MAX_WORKSPACE_STREAMS:
-            self._ws.popitem(last=False)
-        return w
-
-    def release_workspaces(self):
-        self._ws = OrderedDict()
 
     def _ready(self, mels):
         if self._sd is None:
@@ -259,7 +179,7 @@ class Generator:
             layout, src = 0, mels.contiguous()
         stream = torch.cuda.current_stream(mels.device).cuda_stream
         nbytes = self.ws_bytes(B, T)
-        ws = self._workspace(nbytes, stream)
+        ws = self._ws.take(self._device, nbytes, stream)
         with torch.cuda.device(mels.device):
             _lib.check(self._lib.ns_voc_forward(self._h, C.c_void_p(src.data_ptr()), layout, B, T, _lib.ptr(wav), _lib.ptr(ws),
                                                 nbytes, C.c_void_p(stream)), "ns_voc_forward")

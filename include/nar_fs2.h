@@ -379,6 +379,13 @@ int ns_op_block_packed(ns_model* m, int which, const char* prefix, const float* 
  * ns_op_unpack_outputs: mel_bias [n_mel], post_const [11, n_mel]; p_p / p_pred, e_p / e_pred and mel_mask are nullable. */
 int ns_op_length_regulate_packed(const float* x, const int32_t* cum, const int64_t* mel_lens, int B, int L, int D, int T, int Mp, int H,
                                  float* out_p, int32_t* status, int32_t* plan_dev, size_t plan_ints, void* stream);
+/* The Gaussian length regulator alone in the form ns_forward_mel / ns_forward_mel_packed launch it (T_out = T): own_len [B] int64 (frames
+ * at or past it are zeros), status [B] (nullable) = (own_len > T) | 2 (own_len < 0), zero / nzero (nullable together: words zeroed by
+ * the launch), plan_dev (nullable: null with Mp = att_wgs = 0 is the dense grid, out [B, T, D]; else out [Mp, D] on the rows of a plan
+ * built by ns_op_pack_plan with guard 20).  s: B (L + 1) floats of scratch.  w [B, L, T] is nullable on the dense grid (the forwards
+ * pass null) and refused with a plan. */
+int ns_op_gaussian_regulate(const float* x, const float* durations, const int64_t* own_len, int B, int L, int D, int T, float* out, float* s,
+                            float* w, int32_t* status, int32_t* zero, int nzero, const int32_t* plan_dev, int Mp, int att_wgs, void* stream);
 int ns_op_embed_pos_packed(const int64_t* texts, const float* emb, const float* pos, const int32_t* plan_dev, int B, int L, int Mp, int att_wgs, int D,
                            int n_vocab, float* out_p, void* stream);
 int ns_op_add_pos_packed(const float* x_p, const float* pos, const int32_t* plan_dev, int B, int S, int Mp, int att_wgs, int D, float* out_p,
@@ -533,7 +540,10 @@ int ns_aln_forward(ns_aligner* a, const float* src_output, const int64_t* src_le
 /* ---- per-operator entry points (tests) ----
  * cross attention alone (transformer/Modules.py:14-25 on projected heads): q [B*T, H*dk], kv [B*L, 2*H*dk] (K | V, head h at h*dk
  * inside each) -> ctx [B*T, H*dk] (merged heads), attn [B, H, T, L]; dk in {64, 128}.
- * durations: the extension above applied to one [B, H, T, L] map. */
+ * durations: the extension above applied to one [B, H, T, L] map.
+ * input: x [B, T, C] = mels with frame 0 of every utterance replaced by zeros (transformer/Models.py:145-146); C % 4 == 0, both
+ * pointers 16-byte aligned (additive: NS_ALN_ABI_VERSION is unchanged). */
+int ns_aln_op_input(const float* mels, float* x, int B, int T, int C, void* stream);
 int ns_aln_op_cross_attention(const float* q, const float* kv, const int64_t* src_lens, int B, int T, int L, int H, int dk,
                               float* ctx, float* attn, void* stream);
 int ns_aln_op_durations(const float* attn_last, const int64_t* src_lens, const int64_t* mel_lens, int B, int H, int T, int L,

@@ -229,6 +229,7 @@ SIGNATURES = {
     "ns_plan_attention_split_packed": (_I, [_I, _I, _I, _I, _I]),
     "ns_op_block_packed": (_I, [_P, _I, _S, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "ns_op_length_regulate_packed": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ns_op_gaussian_regulate": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
     "ns_op_embed_pos_packed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ns_op_add_pos_packed": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "ns_op_pack_vector": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
@@ -253,6 +254,7 @@ SIGNATURES = {
     "ns_aln_ws_bytes": (_Z, [_P, _I, _I, _I]),
     "ns_aln_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ns_aln_op_cross_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ns_aln_op_input": (_I, [_P, _P, _I, _I, _I, _P]),
     "ns_aln_op_durations": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     # validation loss (loss.FastSpeech2Loss; handle-less)
     "ns_loss_abi_version": (_I, []),

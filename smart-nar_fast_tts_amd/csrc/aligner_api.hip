@@ -254,6 +254,14 @@ extern "C" int ns_aln_op_cross_attention(const float* q, const float* kv, const 
   return 0;
 }
 
+// k_aln_input alone: x [B, T, C] = mels with frame 0 of every utterance replaced by zeros; C % 4 == 0, both pointers 16-byte aligned
+extern "C" int ns_aln_op_input(const float* mels, float* x, int B, int T, int C, void* stream) {
+  if (!mels || !x || B <= 0 || T <= 0 || C <= 0) return api_fail("ns_aln_op_input: bad argument");
+  if ((C & 3) || (((uintptr_t)mels | (uintptr_t)x) & 15)) return api_fail("ns_aln_op_input: C must be a multiple of 4 and the pointers 16-byte aligned");
+  NS_HIP(launch_aln_input(mels, x, B, T, C, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int ns_aln_op_durations(const float* attn_last, const int64_t* src_lens, const int64_t* mel_lens, int B, int H, int T, int L,
                                    int64_t* out, void* stream) {
   if (!attn_last || !src_lens || !mel_lens || !out || B <= 0 || H <= 0 || T < 0 || L <= 0) return api_fail("ns_aln_op_durations: bad argument");

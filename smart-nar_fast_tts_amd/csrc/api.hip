@@ -1498,6 +1498,28 @@ extern "C" int ns_op_length_regulate_packed(const float* x, const int32_t* cum, 
                                        (hipStream_t)stream));
   return 0;
 }
+// launch_gaussian_upsampling alone in the form the forwards launch it (ns_forward_mel / ns_forward_mel_packed): T_out = T, own_len [B]
+// (frames at or past it are zeros), status [B] (nullable), zero / nzero (nullable: words the centres kernel zeroes), plan_dev
+// (nullable: null is the dense [B, T, D] grid with Mp = att_wgs = 0; else out is [Mp, D] packed rows of a plan built by
+// ns_op_pack_plan).  s: B * (L + 1) floats.  w [B, L, T] is nullable on the dense grid (the forwards pass null) and refused with a plan.
+extern "C" int ns_op_gaussian_regulate(const float* x, const float* durations, const int64_t* own_len, int B, int L, int D, int T, float* out,
+                                       float* s, float* w, int32_t* status, int32_t* zero, int nzero, const int32_t* plan_dev, int Mp, int att_wgs,
+                                       void* stream) {
+  if (!x || !durations || !own_len || !out || !s) return fail("ns_op_gaussian_regulate: null argument");
+  if (B <= 0 || L <= 0 || D <= 0 || T <= 0 || (size_t)B * T >= ((size_t)1 << 30)) return fail("ns_op_gaussian_regulate: bad shape");
+  if (nzero < 0 || (zero == nullptr) != (nzero == 0)) return fail("ns_op_gaussian_regulate: zero and nzero go together");
+  if (!plan_dev) {
+    if (Mp != 0 || att_wgs != 0) return fail("ns_op_gaussian_regulate: Mp / att_wgs without a plan");
+    NS_HIP(launch_gaussian_upsampling(x, durations, B, L, D, T, T, out, s, w, (const long long*)own_len, status, (int*)zero, nzero, (hipStream_t)stream));
+    return 0;
+  }
+  if (w) return fail("ns_op_gaussian_regulate: the weight tensor is a [B, L, T] grid output, not available on packed rows");
+  PackedCtx pk;
+  NS_TRY(packed_ctx("ns_op_gaussian_regulate", plan_dev, B, T, Mp, att_wgs, &pk));
+  NS_HIP(launch_gaussian_upsampling(x, durations, B, L, D, T, T, out, s, nullptr, (const long long*)own_len, status, (int*)zero, nzero,
+                                    (hipStream_t)stream, &pk.rm));
+  return 0;
+}
 // launch_embed_pos_packed alone (it also writes the row maps): pos [>= L, D], emb [n_vocab, D]
 extern "C" int ns_op_embed_pos_packed(const int64_t* texts, const float* emb, const float* pos, const int32_t* plan_dev, int B, int L, int Mp, int att_wgs,
                                       int D, int n_vocab, float* out_p, void* stream) {

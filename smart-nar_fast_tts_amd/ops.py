@@ -387,6 +387,15 @@ def cross_attention(q, kv, src_lens, n_head: int):
     return ctx, attn
 
 
+def aligner_input(mels, x):
+    """The aligner's decoder input alone (transformer/Models.py:145-146): writes ``x`` = ``mels`` [B, T, C] with frame 0 of every
+    utterance replaced by zeros.  Both are the caller's tensors (any view whose memory is [B, T, C] row-major)."""
+    lib = _lib.load()
+    B, T, C = mels.shape
+    _lib.check(lib.ns_aln_op_input(_lib.ptr(mels), _lib.ptr(x), B, T, C, _st(mels)), "aligner_input")
+    return x
+
+
 def aligner_durations(attn_last, src_lens, mel_lens):
     """Frames per phoneme from one [B,H,T,L] alignment (EXTENSION beyond the reference, include/nar_fs2.h): int64 [B,L]."""
     lib = _lib.load()
@@ -529,6 +538,21 @@ def length_regulate_packed(x, cum, mel_lens, T: int, H: int, fill: int = 0):
     _lib.check(lib.ns_op_length_regulate_packed(_lib.ptr(x), _lib.ptr(cum), _lib.ptr(mel_lens), B, L, D, int(T), p.Mp, int(H), _lib.ptr(out),
                                                 _lib.ptr(status), _lib.ptr(p.plan), p.plan.numel(), _st(x)), "length_regulate_packed")
     return out, status, p
+
+
+def gaussian_regulate(x, durations, own_len, T: int, out, s, p: PackedPlan | None = None, status=None, zero=None, nzero: int | None = None, w=None):
+    """``launch_gaussian_upsampling`` alone as the forwards launch it (T_out = T): x [B, L, D], durations [B, L], own_len int64 [B];
+    writes ``out`` ([B, T, D], or [Mp, D] with a plan ``p``), ``s`` (B * (L + 1) floats: the sums, then the centres), ``status`` int32
+    [B] and the first ``nzero`` words of ``zero`` — all the caller's, pre-filled as it likes, the last two optional."""
+    lib = _lib.load()
+    B, L, D = x.shape
+    assert x.is_contiguous() and durations.is_contiguous() and durations.dtype == torch.float32 and own_len.dtype == torch.long
+    if nzero is None:
+        nzero = zero.numel() if zero is not None else 0
+    plan = (_lib.ptr(p.plan), p.Mp, p.att_wgs) if p is not None else (_lib.ptr(None), 0, 0)
+    _lib.check(lib.ns_op_gaussian_regulate(_lib.ptr(x), _lib.ptr(durations), _lib.ptr(own_len), B, L, D, int(T), _lib.ptr(out), _lib.ptr(s),
+                                           _lib.ptr(w), _lib.ptr(status), _lib.ptr(zero), int(nzero), *plan, _st(x)), "gaussian_regulate")
+    return out
 
 
 def embed_pos_packed(texts, emb, pos, p: PackedPlan):

@@ -101,6 +101,89 @@ def durations(attn_last, src_lens, mel_lens):
     return out
 
 
+# ---- crafted maps for the duration kernel alone (tests/test_gpu_aligner.py; tests/test_aligner_host.py shows what they catch) ---------
+DYADIC = np.array([0.0, 0.125, 0.25, 0.375, 0.5, 0.75, 1.0], dtype=np.float32)   # head sums of up to 4 of these are exact: ties are real
+PLANTS = np.array([8.0, np.inf, np.nan], dtype=np.float32)                       # what must never count: above every valid entry, or NaN
+GRIDS = {1: (1, 1), 5: (5, 1), 259: (7, 37)}                                     # B * T -> (B, T); 4 waves per workgroup: 1, 5 and 259 leave a partial one
+
+
+def crafted_map(H, L, B, T, seed):
+    """(attn [B, H, T, L], src_lens [B], mel_lens [B]).  Row kinds by (b T + t) % 8: 0 random dyadic draws (ties everywhere), 1 all
+    equal (key 0 wins), 2 all -inf (key 0 wins), 3 the maximum on the last valid key, 4 a tie between l and l + 64 (one lane's two
+    keys; the lower wins), 5 a tie between two lanes, 6 a tie that only the head sum creates, 7 dyadic draws with -inf among them.
+    Then 8.0, +inf and NaN are planted at every key >= src_len and in every frame >= mel_len."""
+    rng = np.random.default_rng(seed)
+    src_lens = np.array([L, 0, 1, L + 3, -2, max(1, L // 2), L][:B], dtype=np.int64)
+    mel_lens = np.array([max(T - 5, 1), T, T + 4, T, T, 0, -1][:B], dtype=np.int64)
+    a = np.empty((B, H, T, L), dtype=np.float32)
+    for b in range(B):
+        sl = int(min(max(src_lens[b], 0), L))
+        for t in range(T):
+            kind = (b * T + t) % 8
+            row = rng.choice(DYADIC, size=(H, L))
+            two = rng.choice(sl, size=2, replace=False) if sl >= 2 else None
+            if kind == 1:
+                row[:] = rng.choice(DYADIC)
+            elif kind == 2:
+                row[:] = -np.inf
+            elif kind == 3 and sl >= 1:
+                row = np.minimum(row, np.float32(0.5))
+                row[:, sl - 1] = 1.0
+            elif kind == 4 and sl > 64:
+                l0 = int(rng.integers(0, sl - 64))
+                row = np.minimum(row, np.float32(0.5))
+                row[:, l0] = row[:, l0 + 64] = 0.75
+            elif kind in (4, 5) and two is not None:
+                row = np.minimum(row, np.float32(0.5))
+                row[:, two] = 0.75
+            elif kind == 6 and two is not None and H >= 2:
+                row = np.minimum(row, np.float32(0.125))
+                row[0, two], row[1, two] = (0.75, 0.25), (0.25, 0.75)
+            elif kind == 7:
+                row[rng.random((H, L)) < 0.3] = -np.inf
+                row[:] = np.where(np.isinf(row).any(axis=0, keepdims=True), -np.inf, row)   # (a key is -inf in every head or in none)
+            a[b, :, t] = row
+        ml = int(min(max(mel_lens[b], 0), T))
+        a[b, :, :, sl:] = PLANTS[(np.arange(T)[:, None] + np.arange(L - sl)[None, :]) % 3][None]
+        a[b, :, ml:, :] = PLANTS[(np.arange(T - ml)[:, None] + np.arange(L)[None, :]) % 3][None]
+    return a, src_lens, mel_lens
+
+
+DURATION_MUTANTS = ("tie_to_highest_key", "later_key_of_a_lane_wins", "src_len_ignored", "mel_len_ignored", "last_valid_key_dropped",
+                    "first_head_only", "one_frame_too_many")
+
+
+def durations_mutant(attn_last, src_lens, mel_lens, mutate):
+    """``durations`` with one deliberate mistake of the kind a wave-level argmax can make (64 lanes, lane i walks keys i, i + 64, ...)"""
+    assert mutate in DURATION_MUTANTS, mutate
+    attn_last = np.asarray(attn_last)
+    B, _, T, L = attn_last.shape
+    with np.errstate(invalid="ignore"):
+        a = attn_last[:, 0] if mutate == "first_head_only" else head_sum(attn_last)
+    out = np.zeros((B, L), dtype=np.int64)
+    for b in range(B):
+        sl, ml = int(min(max(src_lens[b], 0), L)), int(min(max(mel_lens[b], 0), T))
+        if mutate == "mel_len_ignored":
+            ml = T
+        if mutate == "one_frame_too_many":
+            ml = min(ml + 1, T)
+        if sl == 0 or ml == 0:
+            continue
+        n = L if mutate == "src_len_ignored" else max(sl - 1, 1) if mutate == "last_valid_key_dropped" else sl
+        v = a[b, :ml, :n]
+        if mutate == "tie_to_highest_key":
+            idx = n - 1 - np.argmax(v[:, ::-1], axis=1)
+        elif mutate == "later_key_of_a_lane_wins":
+            idx = np.empty(ml, dtype=np.int64)
+            for t in range(ml):
+                best = [max(range(lane, n, 64), key=lambda l: (v[t, l], l)) for lane in range(min(64, n))]   # `>=` inside the lane
+                idx[t] = min(best, key=lambda l: (-v[t, l], l))                                             # lowest key across lanes
+        else:
+            idx = np.argmax(v, axis=1)
+        out[b] = np.bincount(idx, minlength=L)
+    return out
+
+
 # ---- the elementwise gate of the cross-attention kernel (tests/test_aligner_host.py proves it both ways) ----------------------
 GEMM_EPS = 4e-6   # the project's fp32 GEMM constant (tests/test_fp32_ops_host.py): |fp32 sum - exact| <= GEMM_EPS * sum |a||b|
 EXP_EPS = 1e-6    # exp, the division and the row sum of the softmax: a few fp32 roundings on a value <= 1

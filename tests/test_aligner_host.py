@@ -1,6 +1,7 @@
 """Reference-mel aligner, everything that needs no GPU: the torch-CPU restatement against the fixtures captured from the imported
 reference, the ns_aln_* C ABI's host side (version, size functions, refusals), the elementwise gate of the cross-attention kernel
-proven both ways (torch's fp32 passes, every mutant is rejected) and the duration rule on a hand-made case."""
+proven both ways (torch's fp32 passes, every mutant is rejected), the duration rule on a hand-made case and the crafted maps of the
+duration kernel's own GPU test against every wrong argmax they are meant to catch."""
 import ctypes as C
 import os
 import subprocess
@@ -250,3 +251,20 @@ def test_new_kernels_do_not_spill():
     assert r.returncode == 0, r.stdout + r.stderr
     for k in ("k_cross_attention<128>", "k_cross_attention<64>", "k_aln_durations", "k_aln_input"):
         assert k in r.stdout, (k, r.stdout)
+
+
+@pytest.mark.parametrize("mutant", ac.DURATION_MUTANTS)
+def test_crafted_maps_catch_duration_mutants(mutant):
+    """The maps tests/test_gpu_aligner.py hands the duration kernel alone (aligner_cpu.crafted_map): every wrong argmax of
+    aligner_cpu.DURATION_MUTANTS counts differently from aligner_cpu.durations on at least one of them."""
+    for H in (1, 2, 4):
+        for L in (1, 63, 64, 65, 130):
+            B, T = ac.GRIDS[259]
+            a, sl, ml = ac.crafted_map(H, L, B, T, seed=1000 * H + 10 * L + B)
+            with np.errstate(invalid="ignore"):
+                want = ac.durations(a, sl, ml)
+            assert np.array_equal(want.sum(axis=1), np.where(np.clip(sl, 0, L) > 0, np.clip(ml, 0, T), 0))
+            if not np.array_equal(ac.durations_mutant(a, sl, ml, mutant), want):
+                print(f"{mutant}: caught at H {H} L {L}")
+                return
+    pytest.fail(f"no crafted map catches {mutant}")

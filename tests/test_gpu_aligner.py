@@ -1,6 +1,7 @@
 """Reference-mel aligner on the GPU: the cross-attention kernel alone against float64 under the elementwise gate that
 tests/test_aligner_host.py proves both ways, ``model.align`` against the float64 evaluation of the imported reference (fixtures of
-tests/golden/make_golden_aligner.py), the duration kernel, and the forward's independence from it."""
+tests/golden/make_golden_aligner.py), the duration kernel — on the GPU's own maps and, alone, on maps crafted for its argmax, tie rule
+and length handling —, the input kernel alone, and the forward's independence from it."""
 import numpy as np
 import pytest
 import torch
@@ -175,3 +176,67 @@ def test_forward_and_align_do_not_interfere():
         m.align(dev(z["texts"]), dev(z["src_lens"]), int(meta["L"]), dev(z["mels"]), dev(z["mel_lens"]), max_mel_len=int(meta["T"]) + 1)
     with pytest.raises(NotImplementedError):
         m(dev(sp), dev(tx), dev(ln), L, mels=dev(z["mels"]), mel_lens=dev(z["mel_lens"]))
+
+
+# ---- k_aln_durations and k_aln_input alone, on inputs the test crafts ------------------------------------------------------------------
+@pytest.mark.parametrize("L", [1, 63, 64, 65, 130])
+@pytest.mark.parametrize("H", [1, 2, 4])
+def test_durations_on_crafted_maps(H, L):
+    """ns_aln_op_durations alone, bit-exact against aligner_cpu.durations on maps built to hit the wave-level argmax where it can go
+    wrong (``aligner_cpu.crafted_map``): ties between lanes, between l and l + 64 of one lane and ties only the head sum creates (lowest key wins),
+    the maximum on the last valid key, all-equal and all -inf rows (key 0 wins), larger values, +inf and NaN behind src_len and past
+    mel_len (none may count), src_len in {0, 1, L, L + 3, -2}, mel_len in {0, T, T + 4, -1}, B T = 1, 5 and 259 (a partial last
+    workgroup of 4 waves), ``out`` pre-filled with garbage.  Valid entries are finite or -inf: a NaN inside the valid region is outside
+    the kernel's contract (the aligner's softmax gives none where src_len > 0; where it is 0 nothing is counted)."""
+    from smart_nar_fast_tts_amd import _lib
+
+    lib = _lib.load()
+    for BT, (B, T) in ac.GRIDS.items():
+        a, sl, ml = ac.crafted_map(H, L, B, T, seed=1000 * H + 10 * L + B)
+        with np.errstate(invalid="ignore"):
+            want = ac.durations(a, sl, ml)
+        ad, sd, md = dev(a), dev(sl), dev(ml)
+        out = torch.full((B + 1, L), 0x5a5a5a5a5a5a5a5a, dtype=torch.long, device="cuda")
+        _lib.check(lib.ns_aln_op_durations(_lib.ptr(ad), _lib.ptr(sd), _lib.ptr(md), B, H, T, L, _lib.ptr(out), _lib.stream_ptr(ad.device)),
+                   "aligner_durations")
+        got = out.cpu().numpy()
+        assert np.array_equal(got[:B], want), (H, L, BT, np.argwhere(got[:B] != want)[:4].tolist())
+        assert (got[B] == 0x5a5a5a5a5a5a5a5a).all(), "the row after the last utterance was written"
+        frames_of = np.where(np.clip(sl, 0, L) > 0, np.clip(ml, 0, T), 0)
+        assert np.array_equal(got[:B].sum(axis=1), frames_of), (H, L, BT)
+        assert torch.equal(dev(a).view(torch.int32), ad.view(torch.int32)), "the map was written"
+    # what the crafted rows are for, on the largest grid: the tie kinds resolve to the lower key whatever lane holds it
+    B, T = ac.GRIDS[259]
+    a, sl, ml = ac.crafted_map(H, L, B, T, seed=1000 * H + 10 * L + B)
+    with np.errstate(invalid="ignore"):
+        s = ac.head_sum(a)
+    tied = sum(int((s[b, t, :n] == s[b, t, :n].max()).sum() > 1) for b in range(B) for t in range(int(min(max(ml[b], 0), T)))
+               for n in [int(min(max(sl[b], 0), L))] if n > 1)
+    assert L == 1 or tied >= 10, "the crafted maps hold tied maxima among the valid keys"
+
+
+@pytest.mark.parametrize("B,T,C", [(1, 1, 80), (3, 7, 80), (2, 257, 80), (2, 5, 4)])
+def test_aligner_input_replaces_frame_zero(B, T, C):
+    """k_aln_input alone (ns_aln_op_input): frame 0 of every utterance is exactly +0.0 even where ``mels`` holds NaN or Inf there (a
+    replacement, not a product), every other row carries the input's bits (NaN and Inf included), ``mels`` is unchanged and the floats
+    after the last element are untouched; C % 4 != 0 and a misaligned pointer are refused."""
+    g = torch.Generator().manual_seed(B * 1000 + T)
+    mels = torch.randn(B, T, C, generator=g)
+    mels[0, 0, 0], mels[B - 1, 0, C - 1], mels[0, 0, 1] = float("nan"), float("inf"), -0.0
+    if T > 1:
+        mels[0, 1, 0], mels[B - 1, T - 1, C - 1], mels[0, T - 1, 2] = float("nan"), float("-inf"), -0.0
+    md = mels.cuda()
+    buf = torch.full((B * T * C + 4,), -1, dtype=torch.int32, device="cuda").view(torch.float32)
+    x = buf[:B * T * C].view(B, T, C)
+    ops.aligner_input(md, x)
+    torch.cuda.synchronize()
+    got, tail = x.cpu().view(torch.int32), buf[B * T * C:].cpu().view(torch.int32)
+    assert (got[:, 0] == 0).all(), "frame 0 is not exactly +0.0"
+    assert torch.equal(got[:, 1:], mels.view(torch.int32)[:, 1:]), "a later row does not carry the input's bits"
+    assert torch.equal(md.cpu().view(torch.int32), mels.view(torch.int32)), "mels was written"
+    assert (tail == -1).all(), "a float after the last element was written"
+    with pytest.raises(RuntimeError):   # C % 4 != 0
+        ops.aligner_input(md.view(-1)[:B * T * (C - 2)].view(B, T, C - 2), buf[:B * T * (C - 2)].view(B, T, C - 2))
+    with pytest.raises(RuntimeError):   # x 4 bytes off a 16-byte boundary
+        ops.aligner_input(md, buf[1:B * T * C + 1].view(B, T, C))
+    assert (buf[B * T * C:].cpu().view(torch.int32) == -1).all() and torch.equal(x.cpu().view(torch.int32), got), "a refused call wrote"

@@ -60,7 +60,9 @@ typedef struct ns_config {
                                convolutions (downstream of every discrete duration / bucket decision; only launches large
                                enough to fill the chip with 64..256-row tiles, smaller ones stay fp32) run from an exact
                                3-way bf16 split of both operands on the bf16 matrix cores, 6 products, fp32 accumulation:
-                               fp32-sized error, different bits, ~1.8x faster on those layers (csrc/gemm_bf16x3.hip);
+                               fp32-sized error, different bits, ~1.6x faster on those layers (csrc/gemm_bf16x3.hip).
+                               "fp32-sized" is held per launch form against float64, on random-sign and on same-sign
+                               operands: |y - f64| <= 4e-6 * (conv(|x|, |w|) + |bias|) (tests/test_gpu_bf16x3_ops.py);
                                2 = OPT-IN "bf16": every contraction from the decoder input through the PostNet output
                                (decoder QKV, Q K^T, P V, fc, FFN w_1 / w_2, mel_linear, all five PostNet convolutions) takes
                                both operands rounded to bf16 (nearest even) and accumulates in fp32 on the bf16 matrix cores,
@@ -334,6 +336,16 @@ int ns_plan_gemm_bf16(int M, int N, int32_t* bm, int32_t* bn);
 /* 1 when the "bf16"-mode GEMM + LayerNorm of M rows, N columns takes the 64 x 256 full-row LayerNorm tile, 0 when it runs the
  * plain GEMM followed by the row kernel (same bits either way). */
 int ns_plan_gemm_bf16_ln(int M, int N, int Cin, int KW);
+/* What a "bf16x3"-mode model does with a GEMM of M rows, N output channels, kernel size KW over Cin input channels whose weight
+ * has the three bf16 planes (csrc/gemm_bf16x3.hip; answered by the functions the launch path itself calls).  epi 0: the plain
+ * GEMM; epi 1: GEMM + LayerNorm.  Returns the number of bf16x3 launches, 1 or 0 (0: the exact-fp32 kernels take the launch — a
+ * plain GEMM with fewer than 200 tiles of 128 x 256, a LayerNorm GEMM below the full-row thresholds, a shape the kernel does not
+ * cover, or any other epi) and writes out = {BM, BN, ROWEPI, workgroups}: the 128 x 256 or 256 x 256 plain tile (256 rows once
+ * that still gives 240 workgroups), or for epi 1 at N = 256 the 64 x 256 full-row tile with the LayerNorm epilogue (ROWEPI = 1;
+ * from 200 such tiles).  epi 1 with ROWEPI = 0 is the two-launch form for widths the full-row tile does not cover (N = 512): the
+ * plain bf16x3 GEMM described, followed by the LayerNorm row kernel.  out is zeroed when 0 is returned and may be NULL.
+ * Host-side, no GPU needed. */
+int ns_plan_gemm_b3(int M, int N, int Cin, int KW, int epi, int32_t out[4]);
 /* bytes of scratch with which ns_op_attention_core[_mode] splits its keys exactly as a model's own attention of this shape
  * does (the partials its workspace reserves plus the op's ticket block); 0 = pass no scratch. */
 size_t ns_op_attention_scratch_bytes(int B, int S, int H, int dk);

@@ -219,6 +219,7 @@ SIGNATURES = {
     "ns_op_gemm": (_I, [_P, _S, _P, _I, _I, _P, _P]),
     "ns_plan_gemm_bf16": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ns_plan_gemm_bf16_ln": (_I, [_I, _I, _I, _I]),
+    "ns_plan_gemm_b3": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int32)]),
     "ns_op_attention_scratch_bytes": (_Z, [_I, _I, _I, _I]),
     # packed-row test hooks: (plan, B, S, Mp, att_wgs) after the tensors
     "ns_op_pack_plan": (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),

@@ -478,6 +478,16 @@ static int gemm(const ns_model* m, const Scratch& sc, const ConvW& w, const floa
   return 0;
 }
 
+// What gemm_ln does with a weight that has bf16x3 planes (gemm_ln below and ns_plan_gemm_b3 both ask here): its full-row tile where
+// fp32 takes one launch too, two launches (plain bf16x3, then k_layernorm) for widths its LayerNorm tile does not cover, else fp32
+enum B3LnForm : int { B3_LN_FP32 = 0, B3_LN_FULL_ROW = 1, B3_LN_TWO_LAUNCH = 2 };
+static B3LnForm gemm_ln_b3_form(int M, int N, int Cin, int KW) {
+  const bool ln_ok = conv_gemm_b3_ok(M, N, Cin, KW, EPI_LN);
+  if (!ln_ok && conv_gemm_b3_ok(M, N, Cin, KW, EPI_NONE)) return B3_LN_TWO_LAUNCH;
+  if (ln_ok && fuse_row_epilogue(M, N, Cin)) return B3_LN_FULL_ROW;
+  return B3_LN_FP32;
+}
+
 // Y = mask(LayerNorm(act(conv_w(X)) + resid)), g / b the LayerNorm's weights.  Exact fp32: the ladder of host_core.h gemm_ln_fp32
 // (full-row tile, ticketed epilogue, or GEMM -> tmp -> k_layernorm).  The opt-in modes run their own kernels where those cover the
 // launch and fall back to that ladder where they do not.
@@ -494,13 +504,13 @@ static int gemm_ln(const ns_model* m, Scratch& sc, const ConvW& w, const float* 
     return 0;
   }
   if (w.b3 != NO_PLANE) {  // bf16x3 mode: two launches for widths its LayerNorm tile does not cover, its full-row tile where fp32 takes one
-    const bool ln_ok = conv_gemm_b3_ok(M, N, w.cin, w.kw, EPI_LN);
-    if (!ln_ok && conv_gemm_b3_ok(M, N, w.cin, w.kw, EPI_NONE)) {
+    const B3LnForm form = gemm_ln_b3_form(M, N, w.cin, w.kw);
+    if (form == B3_LN_TWO_LAUNCH) {
       NS_TRY(gemm(m, sc, w, X, resid, tmp, M, S, act, st));
       NS_HIP(launch_layernorm(tmp, g, b, Y, M, N, S, lens, st, cur_rm(sc)));
       return 0;
     }
-    if (ln_ok && fuse_row_epilogue(M, N, w.cin)) return gemm(m, sc, w, X, resid, Y, M, S, act, st, GemmOpts::row(e, EPI_LN));
+    if (form == B3_LN_FULL_ROW) return gemm(m, sc, w, X, resid, Y, M, S, act, st, GemmOpts::row(e, EPI_LN));
   }
   if (sc.pk) { e.row_b = sc.pk->rm.row_b; e.row_t = sc.pk->rm.row_t; }
   return gemm_ln_fp32(prepare(m, sc, w.fp32(), X, resid, nullptr, M, S, act), e, tmp, Y, sc.tk, st, cur_rm(sc));
@@ -1350,6 +1360,20 @@ extern "C" int ns_plan_gemm_bf16(int M, int N, int32_t* bm, int32_t* bn) {
   conv_gemm_bf16_plan(M, N, &a, &b);
   *bm = a; *bn = b;
   return 0;
+}
+// what gemm() (epi 0) / gemm_ln() (epi 1) do with a weight that has bf16x3 planes, from the functions those two call
+extern "C" int ns_plan_gemm_b3(int M, int N, int Cin, int KW, int epi, int32_t out[4]) {
+  int bm = 0, rowepi = 0, n = 0;
+  if (M > 0 && N > 0 && Cin > 0 && KW > 0) {
+    const B3LnForm form = epi == 1 ? gemm_ln_b3_form(M, N, Cin, KW) : B3_LN_FP32;
+    if (form == B3_LN_FULL_ROW) { bm = 64; rowepi = 1; n = 1; }
+    else if (form == B3_LN_TWO_LAUNCH || (epi == 0 && conv_gemm_b3_ok(M, N, Cin, KW, EPI_NONE))) { bm = conv_gemm_b3_tile(M, N); n = 1; }
+  }
+  if (out) {
+    out[0] = bm; out[1] = n ? 256 : 0; out[2] = rowepi;
+    out[3] = n ? (int32_t)(((long long)M + bm - 1) / bm * (rowepi ? 1 : (N + 255) / 256)) : 0;
+  }
+  return n;
 }
 extern "C" int ns_op_ffn_conv1(ns_model* m, const char* prefix, const float* x, int B, int S, float* hidden, void* stream) {
   return named_gemm(m, std::string(prefix ? prefix : "") + ".w_1", false, x, B, S, hidden, stream);

@@ -3,11 +3,22 @@
 // three-way split of every fp32 operand,
 //     x = x_hi + x_mid + x_lo      (each piece a bf16: 8 significant bits, 3 x 8 = the 24 bits of an fp32 mantissa;
 //                                   pieces by truncation, so the identity holds bit for bit),
-// keeping six of the nine partial products (lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi — the three dropped ones are
-// below 2^-32 of the product) and accumulating in fp32 inside the MFMA.  Every kept product is exact in fp32 (8 x 8 bits),
-// so the only roundings are the accumulator's — the error against an fp64 reference is the same size as the fp32 MFMA
-// kernel's own (measured: 7e-7 vs 1.5e-6 max-abs at K = 2304 on N(0,1) x N(0,0.02) operands), but the bits differ, which
-// is why this is a separate, labelled mode and not the path the parity tests and the default bench run.
+// keeping six of the nine partial products (lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi) and accumulating in fp32.  The
+// pieces are taken by truncation, so every piece carries its operand's sign and every partial product the sign of x * w:
+// the three dropped products (mid*lo and lo*mid, each up to 2^-22 of a product, and lo*lo) do not cancel on same-sign
+// operands, where they add up to about 2^-24 of conv(|x|, |w|) — 0.015 of the fp32 bound 4e-6 * conv(|x|, |w|), harmless
+// (tests/test_bf16x3_ops_host.py computes it).  Every kept product is exact in fp32 (8 x 8 bits), so the only roundings
+// are the accumulation's — the error against an fp64 reference is the same size as the fp32 MFMA kernel's own (measured:
+// 7e-7 vs 1.5e-6 max-abs at K = 2304 on N(0,1) x N(0,0.02) operands), but the bits differ, which is why this is a
+// separate, labelled mode and not the path the parity tests and the default bench run.
+//
+// Accumulation: the terms of each 16-wide K block are summed from zero on the matrix core and the block's sum is added to
+// the running total with a VALU add (`compute`): all six terms on the 128 x 256 and the full-row tile, all but hi*hi on
+// the 256 x 256 tile.  Feeding every MFMA the running accumulator, as this kernel first did, loses the small terms late in
+// a long contraction — the matrix core aligns them away against the accumulator: SAME-SIGN operands at K = 2304 came out
+// short by 3.7e-6 of conv(|x|, |w|), 1.7 x the fp32 bound, where random-sign operands (0.06 of it) and K = 256 show
+// nothing.  Held alone to float64 (tests/test_gpu_bf16x3_ops.py, profiles/bf16x3_ops.md) the tiles now sit at 0.23 ...
+// 0.38 of the fp32 bound on same-sign operands at K = 2304; the block sum costs 12-13 % of a launch's time.
 //
 // Weights are split once at load into three bf16 planes [3][N][K] (api.hip); activations stay fp32 in HBM, are staged
 // fp32 by LDS-DMA exactly like gemm_conv.hip (same zero padding / halo rule, same XOR swizzle) and are split in
@@ -19,6 +30,8 @@
 // when the launch still has a workgroup per CU.  Measured (tools/lab/gemm_b3_lab.hip, one MI355X, random operands): the
 // k=9 decoder GEMM 645 -> 324 us, PostNet 512->512 k=5 375 -> 205 us; the bf16 matrix pipe is 72 % busy while the chip
 // clocks down to ~1.7 GHz under it (fp32 MFMA kernel: 87 % busy at ~2.1 GHz in the same run) — power, not issue, bound.
+// (Those figures are from before the per-block sums; with them ops.gemm of the k=9 decoder GEMM measures 361 -> 408 us on the
+// 256-row tile at 16 x 1010 rows and 167 -> 188 us on the 128-row tile at 19 x 331.)
 #include <cstring>
 
 #include "rowln.h"
@@ -48,6 +61,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gemm_b3(ConvGemm p, int
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BK = 32, NW = WGM * WGN;
   constexpr int WM = BM / WGM, WN = BN / WGN, TN = WN / 32;
+  constexpr bool BLK6 = BM <= 128;  // all six terms of a K block through the block sum (see compute), or all but hi*hi
   static_assert(WM == 32 && TN >= 1 && BM % 8 == 0 && BN % 16 == 0, "wave strip is 32 rows x TN 32-column tiles");
   constexpr int TOTA = BM / 8;   // DMA instructions per A chunk (8 rows of 128 B each)
   constexpr int TOTB = BN / 16;  // per weight plane (16 rows of 64 B each)
@@ -170,13 +184,28 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gemm_b3(ConvGemm p, int
         const bf16x8 Bh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bp));
         const bf16x8 Bm = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bp + BN * BK));
         const bf16x8 Bl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(bp + 2 * BN * BK));
-        // smallest terms first
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[ni], 0, 0, 0);
+        // The small terms of this 16-wide K block are summed FROM ZERO on the matrix core, smallest first, and the block's sum is
+        // then added to the running total by a nearest-even VALU add.  Fed straight into the running accumulator, a lo*hi /
+        // hi*lo / mid*mid product (2^-16 of a hi*hi one) meets an accumulator up to 2^27 times its size late in a long
+        // contraction and the matrix core aligns it away: same-sign operands at K = 2304 came out short by 3.7e-6 of
+        // conv(|x|, |w|) at every element, 1.7 x the fp32 bound (tests/test_gpu_bf16x3_ops.py, profiles/bf16x3_ops.md); K = 256
+        // shows nothing.  BLK6: all six terms go through the block sum.  The 256 x 256 tile has no registers for that schedule
+        // (118 of its 128; the loop spills and runs 4 x slower): its hi*hi products, the only ones of the accumulator's own
+        // size, still go straight into the accumulator, and the scheduler is kept from overlapping two block sums.
+        if constexpr (!BLK6) __builtin_amdgcn_sched_barrier(0);
+        f32x16 blk;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) blk[r] = 0.f;
+        blk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, blk, 0, 0, 0);
+        blk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, blk, 0, 0, 0);
+        blk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, blk, 0, 0, 0);
+        blk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, blk, 0, 0, 0);
+        blk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, blk, 0, 0, 0);
+        if constexpr (BLK6) blk = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, blk, 0, 0, 0);
+        else acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[ni], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[ni][r] += blk[r];
+        if constexpr (!BLK6) __builtin_amdgcn_sched_barrier(0);
       }
     }
   };
@@ -281,6 +310,13 @@ bool conv_gemm_b3_ok(int M, int N, int Cin, int KW, int epi) {
   return epi == EPI_NONE && (long long)((M + 127) / 128) * ((N + 255) / 256) >= 200;
 }
 
+// rows of the tile a plain launch takes (the launch below and nar_fs2.h ns_plan_gemm_b3 both ask here)
+// 256-row tiles halve the weight-plane traffic per flop (k=9 decoder GEMM: 324 vs 355 us) but need a workgroup per CU
+int conv_gemm_b3_tile(int M, int N) {
+  const int ntn = (N + 255) / 256, ntm256 = (M + 255) / 256;
+  return (long long)ntm256 * ntn >= 240 ? 256 : 128;
+}
+
 hipError_t launch_conv_gemm_b3(const ConvGemm& p, hipStream_t st) {
   if (p.M <= 0 || p.N <= 0) return hipSuccess;
   if (!p.Wb3 || !conv_gemm_b3_ok(p.M, p.N, p.Cin, p.KW, p.epi) || (p.ldx & 3)) return hipErrorInvalidValue;
@@ -291,9 +327,8 @@ hipError_t launch_conv_gemm_b3(const ConvGemm& p, hipStream_t st) {
     return hipGetLastError();
   }
   const int ntn = (p.N + 255) / 256;
-  // 256-row tiles halve the weight-plane traffic per flop (k=9 decoder GEMM: 324 vs 355 us) but need a workgroup per CU
   const int ntm256 = (p.M + 255) / 256, ntm128 = (p.M + 127) / 128;
-  if ((long long)ntm256 * ntn >= 240)
+  if (conv_gemm_b3_tile(p.M, p.N) == 256)
     hipLaunchKernelGGL((k_conv_gemm_b3<256, 256, 8, 2>), dim3(ntm256 * ntn), dim3(1024), 0, st, p, ntn);
   else
     hipLaunchKernelGGL((k_conv_gemm_b3<128, 256, 4, 4>), dim3(ntm128 * ntn), dim3(1024), 0, st, p, ntn);

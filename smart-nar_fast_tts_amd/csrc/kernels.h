@@ -85,6 +85,7 @@ int conv_gemm_acc_chunk();  // k values per accumulation chunk of the long contr
 bool launch_planner_enabled();
 // opt-in "bf16x3" precision mode (gemm_bf16x3.hip): same contraction from an exact 3-way bf16 split of both operands
 bool conv_gemm_b3_ok(int M, int N, int Cin, int KW, int epi);  // epi: EPI_NONE or EPI_LN
+int conv_gemm_b3_tile(int M, int N);                           // rows of a plain launch's tile: 256 or 128 (both 256 columns wide)
 hipError_t launch_conv_gemm_b3(const ConvGemm& p, hipStream_t st);
 void split_weights_b3(const float* w, size_t n, unsigned short* hi, unsigned short* mid, unsigned short* lo);
 // opt-in "bf16" precision mode (gemm_bf16.hip): both operands rounded to bf16, fp32 accumulation, at every launch size

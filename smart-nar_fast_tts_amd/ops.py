@@ -362,6 +362,17 @@ def plan_gemm_bf16_ln(M: int, N: int, Cin: int, KW: int = 1) -> bool:
     return bool(_lib.load().ns_plan_gemm_bf16_ln(int(M), int(N), int(Cin), int(KW)))
 
 
+def plan_gemm_b3(M: int, N: int, Cin: int, KW: int = 1, epi: int = 0):
+    """What a "bf16x3" model does with a GEMM (``epi`` 0) or GEMM + LayerNorm (``epi`` 1) on a weight that has planes
+    (``ns_plan_gemm_b3``; host-side, no GPU): ``(BM, BN, ROWEPI, workgroups)`` of its one bf16x3 launch, or ``None`` when the exact-fp32
+    kernels take it.  ``epi`` 1 with ROWEPI 0: the plain bf16x3 GEMM followed by the LayerNorm row kernel."""
+    import ctypes
+
+    o = (ctypes.c_int32 * 4)()
+    n = _lib.load().ns_plan_gemm_b3(int(M), int(N), int(Cin), int(KW), int(epi), o)
+    return tuple(o) if n else None
+
+
 def plan_gemm_launches(M: int, N: int, Cin: int, KW: int = 1, epi: int = 0):
     """The launches the fp32 Conv1D-as-GEMM dispatch makes for this shape, named by the dispatch itself (``ns_plan_gemm_launches``;
     host-side, no GPU): a tuple of 0, 1 or 2 ``(BM, BN, BK, KS, MF, ROWEPI, TICKET, rows)``.  ``epi``: 0 plain, 1 LayerNorm on the

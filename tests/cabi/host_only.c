@@ -15,6 +15,7 @@ typedef size_t (*ws_fn)(const ns_model*, int, int);
 typedef int (*plan_fn)(int, int, int, int, int32_t*);
 typedef int (*launches_fn)(int, int, int, int, int, int32_t (*)[8]);
 typedef int (*split_fn)(int, int, int, int);
+typedef int (*b3_fn)(int, int, int, int, int, int32_t*);
 typedef int (*version_fn)(void);
 
 int main(int argc, char** argv) {
@@ -59,6 +60,15 @@ int main(int argc, char** argv) {
     /* the dispatch naming its own launch: the same 128 x 256 tile, K step 32, one K group, MFMA edge 32, no row epilogue, all rows */
     if (!plan_launches || plan_launches(16160, 1024, 256, 9, 0, forms) != 1 || forms[0][0] != 128 || forms[0][1] != 256 || forms[0][2] != 32 ||
         forms[0][3] != 1 || forms[0][4] != 32 || forms[0][5] != 0 || forms[0][6] != 0 || forms[0][7] != 16160 || forms[1][0] != 0) return 11;
+    {
+      /* the bf16x3 mode naming its launches: w_1 at 200 tiles of 128 x 256, fp32 one row tile below; w_2 + LayerNorm on the full-row tile */
+      b3_fn plan_b3;
+      int32_t b3[4];
+      *(void**)(&plan_b3) = dlsym(so, "ns_plan_gemm_b3");
+      if (!plan_b3 || plan_b3(6289, 1024, 256, 9, 0, b3) != 1 || b3[0] != 128 || b3[1] != 256 || b3[2] != 0 || b3[3] != 200) return 12;
+      if (plan_b3(6272, 1024, 256, 9, 0, b3) != 0 || b3[0] != 0 || b3[3] != 0 || plan_b3(6289, 1024, 256, 9, 0, 0) != 1) return 13;
+      if (plan_b3(12765, 256, 1024, 1, 1, b3) != 1 || b3[0] != 64 || b3[1] != 256 || b3[2] != 1 || b3[3] != 200) return 14;
+    }
     destroy(m);
   }
   printf("C caller ok\n");

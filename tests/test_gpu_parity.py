@@ -1078,8 +1078,10 @@ def test_packed_rows_match_the_dense_grid_on_ragged_batches():
 
 
 def test_bf16x3_mode_vs_oracle_and_fp32_path():
-    """OPT-IN precision mode (ns_config.matmul_bf16x3, csrc/gemm_bf16x3.hip): the decoder FFN k=9 convolutions and the
-    PostNet 512->512 convolutions computed from an exact 3-way bf16 split on the bf16 matrix cores.  Config 2 at full size:
+    """OPT-IN precision mode (ns_config.matmul_bf16x3, csrc/gemm_bf16x3.hip): the decoder stack's qkv and fc projections and FFN
+    convolutions (w_1, k = 9, and w_2) and the PostNet 512->512 convolutions — every weight csrc/api.hip gives planes to —
+    computed from an exact 3-way bf16 split on the bf16 matrix cores.  (A whole-model comparison: a lost small term or exchanged
+    weight planes pass it; the kernel alone is held in tests/test_gpu_bf16x3_ops.py.)  Config 2 at full size:
     every discrete output identical to the oracle's (they are all upstream of those layers), mel / PostNet mel within the
     same 1e-3 bar with the buckets pinned, and within fp32 noise of the exact-fp32 HIP path — but NOT bit-identical to it
     (if it were, the mode would not have run)."""

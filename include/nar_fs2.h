@@ -1236,6 +1236,65 @@ int ns_va_op_lr_fwd(const float* x, const int64_t* duration, int B, int L, int D
  * utterance's total are never read.  One launch. */
 int ns_va_op_lr_bwd(const float* g, const int32_t* cum, int B, int L, int D, int T, float* d_x, void* stream);
 
+/* ==== PositionwiseFeedForward: a training forward and its backward (transformer/SubLayers.py:62-95) ================================
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  With x [B, S, d], M = B * S rows, "same"-padded
+ * convolutions along S whose taps never leave an utterance's [0, S) rows (a tap outside reads zero):
+ *   h = relu(conv_K1(x, w1) + b1)               [M, d_inner]
+ *   u = conv_K2(h, w2) + b2                     [M, d]
+ *   z = u keep / (1 - p_drop) + x;  y = LayerNorm(z) ln_g + ln_b          y is not masked (FFTBlock does that outside)
+ * The weights are LIVE device tensors in checkpoint (torch Conv1d) layout; dropout is a uint8 keep-mask [M, d] (1 = kept) and p_drop.
+ * Exact fp32 on the fp32 matrix cores; row statistics and column sums in float64, rounded once.  No atomic, no host read; equal
+ * inputs give equal bits.  The ReLU backward gates on the SAVED h (dh = h > 0 ? da : +0.0, a select), so the gradients are those of
+ * the forward that ran. */
+#define NS_FG_ABI_VERSION 1
+int ns_fg_abi_version(void);
+typedef struct ns_fg_shape { int32_t B, S, d, d_inner, K1, K2; } ns_fg_shape;
+/* Device pointers, 16-byte aligned, fp32, checkpoint layout. */
+typedef struct ns_fg_weights {
+  const float* w1;    /* [d_inner, d, K1] w_1.weight */
+  const float* b1;    /* [d_inner] */
+  const float* w2;    /* [d, d_inner, K2] w_2.weight */
+  const float* b2;    /* [d] */
+  const float* ln_g;  /* [d] layer_norm.weight */
+  const float* ln_b;  /* [d] */
+} ns_fg_weights;
+/* The outputs of ns_fg_backward: the same six, shaped alike, and dx [B, S, d].  16-byte aligned.  NULL = not wanted: neither computed
+ * nor written, and a launch none of whose outputs is wanted is not made. */
+typedef struct ns_fg_grads {
+  float *w1, *b1, *w2, *b2, *ln_g, *ln_b, *dx;
+} ns_fg_grads;
+/* Bytes of the workspace of ns_fg_forward / ns_fg_backward of this shape (0 and ns_last_error() for a refused shape), and of `saved`:
+ * h [M, d_inner] | z [M, d] floats, in this order, dense. */
+size_t ns_fg_ws_bytes(const ns_fg_shape* shape);
+size_t ns_fg_saved_bytes(const ns_fg_shape* shape);
+/* Kernel launches the calling thread's last ns_fg_* call enqueued. */
+int ns_fg_last_launches(void);
+/* Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a pointer that is not 16-byte
+ * aligned, d not 256 or 512, d_inner not a positive multiple of 256, K1 or K2 not odd and positive, B * S * d_inner >= 2^31, a shape
+ * the Conv1D-as-GEMM dispatch or the weight gradient's plan (ns_pg_plan_wgrad) refuses, p_drop outside [0, 1), a keep-mask without
+ * p_drop > 0 or p_drop > 0 without one, a workspace smaller than ns_fg_ws_bytes.
+ * y [B, S, d].  saved: ns_fg_saved_bytes, or NULL (nothing kept: the no_grad forward; the same launches, the same y).
+ * Launches: 1 (pack of w1 and w2) + G(M, d_inner, K1 d) (h, bias and ReLU in its epilogue) + G(M, d, K2 d_inner) (u) + 1 (row), where
+ * G(M, N, KW Cin) is the Conv1D-as-GEMM dispatch's own launch count for that shape (ns_plan_gemm_launches(M, N, Cin, KW, 0), 1 or 2). */
+int ns_fg_forward(const ns_fg_shape* shape, const ns_fg_weights* weights, const float* x, const uint8_t* keep, float p_drop, float* y,
+                  void* saved, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of sum g[m, :] . y[m, :] (g [B, S, d], read on every row) with respect to every non-NULL member of grads, from `saved`
+ * as ns_fg_forward wrote it for the same arguments.
+ * Launches with every output wanted: 1 (row backward: dz, du, the partials of d_ln_g, d_ln_b, d_b2) + 2 (dW2: GEMM, reduce) + 1 (pack
+ * of the transposed, tap-flipped w2 and w1) + G(M, d_inner, K2 d) (da) + 1 (ReLU gate, with the partials of d_b1) + 1 (d_b1: column
+ * finish at width d_inner) + 2 (dW1) + G(M, d, K1 d_inner) (dx, the residual branch dz added in its epilogue) + 1 (column finish at
+ * width d: d_ln_g, d_ln_b, d_b2) = 9 + G(M, d_inner, K2 d) + G(M, d, K1 d_inner).  An unwanted weight gradient drops its 2 launches, dx
+ * its GEMM, b1 its column finish, all of ln_g, ln_b and b2 theirs; with none of w1, b1 and dx wanted the pack, da and the gate are
+ * dropped too: the row backward, dW2's two and the last finish remain.  With no output wanted nothing is launched. */
+int ns_fg_backward(const ns_fg_shape* shape, const ns_fg_weights* weights, const float* x, const uint8_t* keep, float p_drop,
+                   const void* saved, const float* g, const ns_fg_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* The new kernel alone.  dh [M, d_inner] = h > 0 ? da : +0.0 (a select: what da holds where h <= 0 reaches nothing; dh may be da) and,
+ * unless d_b1 is NULL, d_b1 [d_inner] = the column sums of dh: float64 partials per 64 rows, added in ascending order, rounded once.
+ * d_inner a positive multiple of 256, M * d_inner < 2^31.  ws (needed with d_b1 only): ceil(M / 64) * 5 * d_inner doubles.
+ * One launch, two with d_b1. */
+int ns_fg_op_relu_gate(const float* da, const float* h, int M, int d_inner, float* dh, float* d_b1, void* ws, size_t ws_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,24 @@ class NsPnGrads(C.Structure):
     _fields_ = [(f"{n}{i}", C.c_void_p) for i in range(PN_MAX_LAYERS) for n in PN_PARAMS] + [("dx", C.c_void_p)]
 
 
+class NsFgShape(C.Structure):
+    """``ns_fg_shape`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "S", "d", "d_inner", "K1", "K2")]
+
+
+FG_NAMES = ("w1", "b1", "w2", "b2", "ln_g", "ln_b")
+
+
+class NsFgWeights(C.Structure):
+    """``ns_fg_weights`` (include/nar_fs2.h): the six parameters in checkpoint layout."""
+    _fields_ = [(n, C.c_void_p) for n in FG_NAMES]
+
+
+class NsFgGrads(C.Structure):
+    """``ns_fg_grads`` (include/nar_fs2.h): the six parameter gradients and ``dx``, each nullable."""
+    _fields_ = [(n, C.c_void_p) for n in FG_NAMES + ("dx",)]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -352,6 +370,14 @@ SIGNATURES = {
     "ns_va_op_embed_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "ns_va_op_lr_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "ns_va_op_lr_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    # PositionwiseFeedForward training forward and backward (sublayers.PositionwiseFeedForward; handle-less)
+    "ns_fg_abi_version": (_I, []),
+    "ns_fg_ws_bytes": (_Z, [C.POINTER(NsFgShape)]),
+    "ns_fg_saved_bytes": (_Z, [C.POINTER(NsFgShape)]),
+    "ns_fg_last_launches": (_I, []),
+    "ns_fg_forward": (_I, [C.POINTER(NsFgShape), C.POINTER(NsFgWeights), _P, _P, _F, _P, _P, _P, _Z, _P]),
+    "ns_fg_backward": (_I, [C.POINTER(NsFgShape), C.POINTER(NsFgWeights), _P, _P, _F, _P, _P, C.POINTER(NsFgGrads), _P, _Z, _P]),
+    "ns_fg_op_relu_gate": (_I, [_P, _P, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -1,6 +1,6 @@
 """What the trainable HIP layers share on the Python side (predictor.VariancePredictor over ``ns_pg_*``, the two attentions of
-sublayers.py over ``ns_ag_*`` / ``ns_xg_*``, postnet.PostNet over ``ns_pn_*``, the embedding and the length regulator of adaptor.py
-over ``ns_va_*``): the device guards, the launch bookkeeping (``CountedModule``), the workspace cache, the autograd Functions and the
+sublayers.py over ``ns_ag_*`` / ``ns_xg_*`` and its PositionwiseFeedForward over ``ns_fg_*``, postnet.PostNet over ``ns_pn_*``, the
+embedding and the length regulator of adaptor.py over ``ns_va_*``): the device guards, the launch bookkeeping (``CountedModule``), the workspace cache, the autograd Functions and the
 module base class that marshals the inputs, the parameters, the keep-masks and the gradient block.  A layer keeps its constructor
 checks, its ``PARAM_NAMES``, its shape struct, its mask handling and its two ctypes calls.  The cross-attention has two outputs, one of
 them saved for the backward, and so brings ``CrossTrainFunction`` next to ``TrainFunction``; everything else it takes from the base."""

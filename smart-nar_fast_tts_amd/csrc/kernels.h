@@ -483,6 +483,10 @@ hipError_t launch_va_duration_scan(const long long* duration, int B, int L, int3
 // d_x[b, l, :] = the sum of g[b, t, :] over t in [cum[l-1], min(cum[l], T)) in t order, float64, rounded once; +0.0 for an empty range.
 // One wave per phoneme, 16-byte lanes.
 hipError_t launch_va_lr_bwd(const float* g, const int32_t* cum, int B, int L, int D, int T, float* d_x, hipStream_t st);
+// ---- PositionwiseFeedForward training backward (ffngrad.hip; transformer/SubLayers.py:62-95) ----------------
+// dh [M, F] = h > 0 ? da : +0.0 (a select; dh may be da), F a multiple of 256; part (nullable) [pg_row_blocks(M)][PG_SLOTS][F] doubles,
+// uninitialised: slot 0 of a block = the column sums of its rows of dh, summed by launch_pg_col_final at this F.  One launch.
+hipError_t launch_fg_relu_gate(const float* da, const float* h, int M, int F, float* dh, double* part, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the handle-less training ABIs (ns_pg_*, ns_ag_*, ns_xg_*, ns_pn_*, ns_va_* in the five *grad_api.hip;
+// Host-side helpers shared by the handle-less training ABIs (ns_pg_*, ns_ag_*, ns_xg_*, ns_pn_*, ns_va_*, ns_fg_* in the six *grad_api.hip;
 // DESIGN.md section 20): the argument checks whose texts they state alike, the workspace and size-query wrappers, the counted launches
 // of the kernels they share (Conv1D-as-GEMM, weight pack, column-partial finish) and the row-backward argument blocks.  Host-only, no
 // kernels.  Each ABI keeps its own thread-local launch counter and hands it in as a Counted; what differs between the layers

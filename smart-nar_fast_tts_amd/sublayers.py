@@ -15,7 +15,10 @@ memory (128 MB per decoder layer at B 16, S 1000), and no caller in the referenc
 attention loss reads the cross-attention maps of ``FFTBlock2.crs_attn``, which ``MultiHeadAttention`` does not cover).
 
 ``MultiHeadCrossAttention`` is that other use of the same reference class (csrc/xattngrad.hip, ``ns_xg_*``): ``q`` = mel frames,
-``k is v`` = phonemes, the [B, H, T, L] map returned and its gradient accepted."""
+``k is v`` = phonemes, the [B, H, T, L] map returned and its gradient accepted.
+
+``PositionwiseFeedForward`` (transformer/SubLayers.py:62-95; csrc/ffngrad.hip, ``ns_fg_*``) is the other sublayer of an FFT block, and
+``FFTBlock`` (transformer/Layers.py:39-48) the composite of ``slf_attn`` and ``pos_ffn`` in plain Python."""
 from __future__ import annotations
 
 import ctypes as C
@@ -230,3 +233,120 @@ class MultiHeadCrossAttention(_Attention):
                                                 _lib.ptr(call.keep), call.p, _lib.ptr(saved), _lib.ptr(attn), _lib.ptr(g), _lib.ptr(d_attn),
                                                 C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward")
         return outs
+
+
+FFN_PARAM_NAMES = ("w_1.weight", "w_1.bias", "w_2.weight", "w_2.bias", "layer_norm.weight", "layer_norm.bias")  # order of ns_fg_weights
+
+
+class PositionwiseFeedForward(HipTrainModule):
+    """Drop-in for ``PositionwiseFeedForward(d_in, d_hid, kernel_size, dropout=0.1)`` (transformer/SubLayers.py:62-95) whose forward
+    AND backward are HIP (csrc/ffngrad.hip, ``ns_fg_*``): the same parameter names (``w_1``, ``w_2`` as ``nn.Conv1d``, ``layer_norm``),
+    so ``encoder.layer_stack.N.pos_ffn.*`` of a reference checkpoint loads strictly.
+
+        f = PositionwiseFeedForward(256, 1024, (9, 1), dropout=0.2).to(device)
+        y = f(x)                     # layer_norm(dropout(w_2(relu(w_1(x)))) + x), NOT masked (FFTBlock does that outside)
+        y.backward(dy)
+
+    ``forward(x, keep_mask=None)`` with ``x`` float32 [B, S, d_in].  The convolutions run along S inside each utterance: a tap never
+    reads the neighbouring utterance's rows.  ``eval()`` means no dropout; the module stays differentiable.  In ``train()`` with
+    ``dropout > 0`` the keep-mask is drawn with ``torch.bernoulli`` on the device; ``keep_mask`` (bool or uint8 [B, S, d_in], nonzero =
+    kept) supplies it instead.  Under ``torch.no_grad()``, or when neither the input nor a parameter requires grad, a call keeps
+    nothing.  Otherwise it is one ``torch.autograd.Function`` (single backward) that keeps ``h = relu(w_1(x))`` and ``z = dropout(w_2(h))
+    + x`` ((d_hid + d_in) B S floats) and whose backward honours ``needs_input_grad``.  The ReLU backward gates on the saved ``h``.
+
+    Raises on what it cannot do: d_in not 256 or 512, d_hid not a positive multiple of 256, an even kernel size."""
+
+    ABI, INPUT = "ns_fg", "the input"
+    PARAM_NAMES, FIELDS = FFN_PARAM_NAMES, _lib.FG_NAMES
+    WEIGHTS, GRADS = _lib.NsFgWeights, _lib.NsFgGrads
+    WORKSPACES = WorkspaceCache("ns_fg_ws_bytes", ("B", "S", "d", "d_inner", "K1", "K2"))
+
+    def __init__(self, d_in, d_hid, kernel_size, dropout=0.1):
+        super().__init__()
+        who = type(self).__name__
+        k1, k2 = (int(k) for k in kernel_size)
+        if d_in not in (256, 512):
+            raise ValueError(f"{who}: d_in must be 256 or 512, got {d_in}")
+        if d_hid <= 0 or d_hid % 256 != 0:
+            raise ValueError(f"{who}: d_hid must be a positive multiple of 256, got {d_hid}")
+        if k1 <= 0 or k2 <= 0 or k1 % 2 == 0 or k2 % 2 == 0:
+            raise ValueError(f"{who}: the kernel sizes must be odd and positive, got {(k1, k2)}")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"{who}: dropout must lie in [0, 1), got {dropout}")
+        self.d_in, self.d_hid, self.kernel_size = d_in, d_hid, (k1, k2)
+        self.p_drop = float(dropout)
+        self.w_1 = torch.nn.Conv1d(d_in, d_hid, kernel_size=k1, padding=(k1 - 1) // 2)
+        self.w_2 = torch.nn.Conv1d(d_hid, d_in, kernel_size=k2, padding=(k2 - 1) // 2)
+        self.layer_norm = torch.nn.LayerNorm(d_in)
+
+    def _marshal(self, x, keep_mask):
+        call = self._begin(x, self.d_in)
+        B, S, d = x.shape
+        s = _lib.NsFgShape()
+        s.B, s.S, s.d, s.d_inner, s.K1, s.K2 = B, S, d, self.d_hid, self.kernel_size[0], self.kernel_size[1]
+        call.shape = s
+        call.p = self.p_drop if self.training else 0.0
+        call.keep = self._keep_masks(None if keep_mask is None else (keep_mask,), [(B, S, d)], call.device, call.p)[0]
+        return call
+
+    def forward(self, x, keep_mask=None):
+        return self._dispatch(self._marshal(x, keep_mask), x)
+
+    def _forward(self, call, save):
+        s, dev = call.shape, call.device
+        with guard(dev):
+            ws, saved = self._workspace(call, save)
+            y = torch.empty((s.B, s.S, s.d), dtype=torch.float32, device=dev)
+            self._done(self._lib.ns_fg_forward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.keep), call.p, _lib.ptr(y),
+                                               _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "forward")
+        return y, saved
+
+    def _backward(self, call, saved, g, need):
+        """Gradients of ``(g * y).sum()``: a list (dx, then the six of FFN_PARAM_NAMES) with None where ``need`` is False."""
+        s, dev = call.shape, call.device
+        if tuple(g.shape) != (s.B, s.S, s.d) or g.dtype != torch.float32 or g.device != dev:
+            raise ValueError(f"grad_output must be a float32 {(s.B, s.S, s.d)} tensor on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+        g = aligned(g)
+        with guard(dev):
+            outs, d = self._grad_block(call, need)
+            ws, _ = self._workspace(call, save=False)
+            self._done(self._lib.ns_fg_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.keep), call.p, _lib.ptr(saved),
+                                                _lib.ptr(g), C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward")
+        return outs
+
+
+class FFTBlock(torch.nn.Module):
+    """The reference's ``FFTBlock(d_model, n_head, d_k, d_v, d_inner, kernel_size, dropout=0.1)`` (transformer/Layers.py:39-48) as a
+    trainable module: ``slf_attn`` is ``MultiHeadAttention`` and ``pos_ffn`` is ``PositionwiseFeedForward``, both HIP in forward and
+    backward, composed in plain Python, so ``encoder.layer_stack.N.*`` of a reference checkpoint loads strictly.  The two
+    ``masked_fill(mask.unsqueeze(-1), 0)`` between and after the sublayers stay torch kernels for now (with torch's own backward); there
+    is no C code of the block's own.
+
+    ``forward(enc_input, mask=None, slf_attn_mask=None, lens=None, keep_masks=None) -> (enc_output, None)``: ``mask`` is the bool
+    [B, S] padding mask (True = padded; those rows of the output are exactly 0), ``slf_attn_mask`` and ``lens`` follow
+    ``MultiHeadAttention``'s rules (the reference's [B, S, S] key-padding mask, or int [B] lengths on the device at no host read, or
+    both; with neither every key is valid).  Without ``mask`` no row is zeroed, as in the reference.  ``keep_masks`` supplies the two dropout keep-masks (attention, feed-forward), each [B, S, d_model].  The second return value is
+    ``None``: the self-attention map is never written to memory."""
+
+    def __init__(self, d_model, n_head, d_k, d_v, d_inner, kernel_size, dropout=0.1):
+        super().__init__()
+        self.slf_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
+        self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, kernel_size, dropout=dropout)
+
+    def forward(self, enc_input, mask=None, slf_attn_mask=None, lens=None, keep_masks=None):
+        if keep_masks is not None and len(keep_masks) != 2:
+            raise ValueError(f"keep_masks must hold 2 masks (attention, feed-forward), got {len(keep_masks)}")
+        k_attn, k_ffn = keep_masks if keep_masks is not None else (None, None)
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(enc_input.shape[:2]) or mask.device != enc_input.device:
+                raise ValueError(f"mask must be a bool [B, S] = {tuple(enc_input.shape[:2])} tensor on {enc_input.device}")
+            pad = (mask != 0).unsqueeze(-1)
+        else:
+            pad = None
+        enc_output, _ = self.slf_attn(enc_input, enc_input, enc_input, mask=slf_attn_mask, lens=lens, keep_mask=k_attn)
+        if pad is not None:
+            enc_output = enc_output.masked_fill(pad, 0)
+        enc_output = self.pos_ffn(enc_output, keep_mask=k_ffn)
+        if pad is not None:
+            enc_output = enc_output.masked_fill(pad, 0)
+        return enc_output, None

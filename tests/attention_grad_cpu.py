@@ -16,7 +16,7 @@ Weights travel as a dict: wq, wk, wv, wfc [d, d], bq, bk, bv, bfc, ln_g, ln_b [d
 import numpy as np
 import torch
 
-from tests import lossgrad_cpu as lg
+from tests import util
 from tests import predictor_grad_cpu as pc
 
 NAMES = ("wq", "bq", "wk", "bk", "wv", "bv", "wfc", "bfc", "ln_g", "ln_b", "dx")  # order of ns_ag_grads
@@ -164,18 +164,12 @@ def closed_form(x, w, lens, H, g, saved, keep=None, p=0.0, dtype=torch.float64, 
 
 def gate(ref32, ref64, names=NAMES):
     """The absolute gates (dict by name): twice the reference's own fp32 error plus one fp32 ulp of the largest magnitude."""
-    out = {}
-    for n in names:
-        a, b = np.asarray(ref32[n], dtype=np.float64), np.asarray(ref64[n], dtype=np.float64)
-        out[n] = 2.0 * float(np.max(np.abs(a - b), initial=0.0)) + lg.ulp32(np.max(np.abs(b), initial=0.0))
-    return out
+    return util.gates(ref32, ref64, names)
 
 
 def shares(got, ref64, gates, names=NAMES):
     """{name: max |got - ref64| / gate}; inf for a NaN / Inf in got.  A missing (None) gradient is skipped."""
-    names = [n for n in names if got.get(n) is not None]
-    s, _ = lg.shares([np.asarray(got[n]).reshape(-1) for n in names], [np.asarray(ref64[n]).reshape(-1) for n in names], [gates[n] for n in names])
-    return dict(zip(names, (float(v) for v in s)))
+    return util.shares(got, ref64, gates, names)
 
 
 def seeded_weights(d, seed):

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from tests import attention_grad_cpu as ac
+from tests import util
 
 NAMES = ac.NAMES[:10] + ("dtgt", "dsrc")  # order of ns_xg_grads
 MUTANTS = ("AdA_missing_from_D", "dA_missing_from_dP", "dA_read_at_masked_keys", "c_applied_once", "dK_without_transpose",
@@ -136,11 +137,11 @@ def closed_form(tgt, src, w, lens, H, g, a, saved, keep=None, p=0.0, dtype=torch
 
 
 def gate(ref32, ref64, names=NAMES):
-    return ac.gate(ref32, ref64, names)
+    return util.gates(ref32, ref64, names)
 
 
 def shares(got, ref64, gates, names=NAMES):
-    return ac.shares(got, ref64, gates, names)
+    return util.shares(got, ref64, gates, names)
 
 
 def loss_shaped_dA(B, H, T, L, ilens, olens, seed, heads=(0,)):

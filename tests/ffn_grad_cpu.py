@@ -23,6 +23,7 @@ import torch
 
 from tests import attention_grad_cpu as ac
 from tests import predictor_grad_cpu as pc
+from tests import util
 
 NAMES = ("w1", "b1", "w2", "b2", "ln_g", "ln_b", "dx")  # order of ns_fg_grads
 MUTANTS = ("relu_gate_dropped", "gate_from_preactivation_sign_of_da", "dgrad_without_tap_flip", "wgrad_across_utterances", "residual_dropped",
@@ -99,12 +100,12 @@ def closed_form(x, w, g, saved, keep=None, p=0.0, dtype=torch.float64, mutate=No
 
 def gate(ref32, ref64, names=NAMES):
     """The absolute gates (dict by name): twice the reference's own fp32 error plus one fp32 ulp of the largest magnitude."""
-    return ac.gate(ref32, ref64, names)
+    return util.gates(ref32, ref64, names)
 
 
 def shares(got, ref64, gates, names=NAMES):
     """{name: max |got - ref64| / gate}; inf for a NaN / Inf in got.  A missing (None) gradient is skipped."""
-    return ac.shares(got, ref64, gates, names)
+    return util.shares(got, ref64, gates, names)
 
 
 def seeded_weights(d, d_inner, K1, K2, seed):

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from tests import loss_cpu as lc
+from tests.util import gate_value, share_of, ulp32  # noqa: F401  (ulp32: callers use lg.ulp32)
 
 NAMES = ("mel", "postnet", "pitch", "energy", "log_d", "attn0", "attn1", "attn2", "attn3")
 MUTANTS = ("mean_over_all_elements", "factor_2_dropped", "g0_only", "W_on_every_head", "alpha_dropped", "log_without_plus_one",
@@ -137,10 +138,6 @@ def autograd_ref(inputs, predictions, pitch_level, energy_level, g, dtype):
     return [(torch.zeros_like(x) if d is None else d).numpy() for x, d in zip(leaves, grads)]
 
 
-def ulp32(x):
-    return float(np.spacing(np.float32(abs(float(x)))))
-
-
 def n_attn_of(inputs, predictions):
     T, L = predictions[0].shape[1], predictions[4].shape[1]
     return int((lc._clamped(inputs[4], L) * lc._clamped(inputs[7], T)).sum())
@@ -150,8 +147,7 @@ def gate(ref32, ref64, g, n_attn):
     """The nine absolute gates.  An all-zero float64 gradient has a gate of one denormal: it must be matched exactly."""
     out = []
     for i, (a, w) in enumerate(zip(ref32, ref64)):
-        a, w = np.asarray(a, dtype=np.float64), np.asarray(w, dtype=np.float64)
-        v = 2.0 * float(np.max(np.abs(a - w), initial=0.0)) + ulp32(np.max(np.abs(w), initial=0.0))
+        v = gate_value(a, w)
         if i >= 5 and n_attn > 0:
             v += 4.0 * 2.0 ** -24 * lc.ALPHA * abs(float(g[0]) + float(g[6])) / n_attn
         out.append(v)
@@ -160,18 +156,8 @@ def gate(ref32, ref64, g, n_attn):
 
 def shares(got, want64, gates):
     """Per tensor (max |got - want| / gate, flat index of the worst element); a NaN or Inf anywhere in ``got`` gives inf."""
-    out, where = [], []
-    for a, w, q in zip(got, want64, gates):
-        a, w = np.asarray(a, dtype=np.float64), np.asarray(w, dtype=np.float64)
-        if a.size == 0:
-            out.append(0.0), where.append(-1)
-            continue
-        err = np.abs(a - w)
-        if not np.isfinite(a).all():
-            out.append(float("inf")), where.append(int(np.argmax(~np.isfinite(a))))
-            continue
-        out.append(float(err.max() / q)), where.append(int(err.argmax()))
-    return np.array(out), where
+    pairs = [share_of(a, w, q) for a, w, q in zip(got, want64, gates)]
+    return np.array([s for s, _ in pairs]), [i for _, i in pairs]
 
 
 _CACHE = {}

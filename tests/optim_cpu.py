@@ -15,6 +15,8 @@ multiply-add inside lerp / addcmul, a different association of step_size * m / d
 where torch's error is exactly zero (one-element tensors, the first step)."""
 import numpy as np
 
+from tests.util import gate_value
+
 CHUNK = 4096  # NS_OPT_CHUNK
 MUTANTS = ("no_bias_correction", "eps_inside_sqrt", "betas_swapped", "clip_without_1e-6", "step_off_by_one", "decoupled_weight_decay")
 QUANTITIES = ("p", "m", "v")
@@ -127,16 +129,9 @@ def torch_run(case, dtype="float32", make_optimizer=None):
 
 
 # ---- the gate ---------------------------------------------------------------------------------------------------------------------------
-def ulp32(x):
-    return float(np.spacing(np.float32(abs(float(x)))))
-
-
 def gate_of(torch32, want64):
-    """2 x max |torch fp32 - float64| + one fp32 ulp of max |float64| (an array or a scalar)."""
-    a, w = np.asarray(torch32, dtype=np.float64), np.asarray(want64, dtype=np.float64)
-    if w.size == 0:
-        return 1.0
-    return 2.0 * float(np.max(np.abs(a - w))) + ulp32(np.max(np.abs(w)))
+    """2 x max |torch fp32 - float64| + one fp32 ulp of max |float64| (an array or a scalar); 1 for an empty array."""
+    return 1.0 if np.size(want64) == 0 else gate_value(torch32, want64)
 
 
 def shares(got, torch32, want64):

@@ -22,7 +22,7 @@ Weights travel as a dict: per layer i  w{i} [C_out, C_in, K], b{i}, g{i}, be{i},
 import numpy as np
 import torch
 
-from tests import lossgrad_cpu as lg
+from tests import util
 from tests.predictor_grad_cpu import dgrad, rows_conv, wgrad
 
 BN_EPS, MOMENTUM = 1e-5, 0.1
@@ -184,20 +184,8 @@ def evaluate(x, w, g, keeps=None, p=0.0, training=True, dtype=torch.float64, mut
     return out
 
 
-def gate(ref32, ref64, names=None):
-    """The absolute gates {name: value}: twice the reference's own fp32 error plus one fp32 ulp of the largest magnitude."""
-    out = {}
-    for k in (names or [k for k in ref64 if k in ref32]):
-        a, b = np.asarray(ref32[k], dtype=np.float64), np.asarray(ref64[k], dtype=np.float64)
-        out[k] = 2.0 * float(np.max(np.abs(a - b), initial=0.0)) + lg.ulp32(np.max(np.abs(b), initial=0.0))
-    return out
-
-
-def shares(got, ref64, gates, names=None):
-    """{name: max |got - ref64| / gate}; inf for a NaN / Inf in got.  A missing (None) tensor is skipped."""
-    names = [k for k in (names or gates) if got.get(k) is not None]
-    s, _ = lg.shares([got[k] for k in names], [ref64[k] for k in names], [gates[k] for k in names])
-    return dict(zip(names, (float(v) for v in s)))
+gate = util.gates  # the absolute gates {name: value}, over the tensors both evaluations hold unless names are given
+shares = util.shares  # {name: max |got - ref64| / gate}
 
 
 def classes(sh):

@@ -19,7 +19,7 @@ be2 [F], wlin [F], blin []."""
 import numpy as np
 import torch
 
-from tests import lossgrad_cpu as lg
+from tests import util
 
 NAMES = ("w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2", "wlin", "blin", "dx")  # order of ns_pg_grads
 MUTANTS = ("dgrad_without_tap_flip", "dgrad_pad_not_flipped", "wgrad_across_utterances", "mean_dy_xhat_dropped", "relu_gate_dropped",
@@ -165,18 +165,12 @@ def closed_form(x, w, mask, g, saved, keeps=None, p=0.0, dtype=torch.float64, mu
 
 def gate(ref32, ref64):
     """The eleven absolute gates (dict by NAMES): twice the reference's own fp32 error plus one fp32 ulp of the largest magnitude."""
-    out = {}
-    for n in NAMES:
-        a, b = np.asarray(ref32[n], dtype=np.float64), np.asarray(ref64[n], dtype=np.float64)
-        out[n] = 2.0 * float(np.max(np.abs(a - b), initial=0.0)) + lg.ulp32(np.max(np.abs(b), initial=0.0))
-    return out
+    return util.gates(ref32, ref64, NAMES)
 
 
 def shares(got, ref64, gates, names=NAMES):
     """{name: max |got - ref64| / gate}; inf for a NaN / Inf in got.  A missing (None) gradient is skipped."""
-    names = [n for n in names if got.get(n) is not None]
-    s, _ = lg.shares([got[n] for n in names], [ref64[n] for n in names], [gates[n] for n in names])
-    return dict(zip(names, (float(v) for v in s)))
+    return util.shares(got, ref64, gates, names)
 
 
 def seeded_weights(Cin, F, K, seed):

@@ -4,8 +4,6 @@ proven both ways (torch's fp32 passes, every mutant is rejected), the duration r
 duration kernel's own GPU test against every wrong argmax they are meant to catch."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,7 +13,7 @@ import smart_nar_fast_tts_amd.workload as wl
 from smart_nar_fast_tts_amd import _lib, ops
 from smart_nar_fast_tts_amd.model import FastSpeech2Align, config_struct
 from tests import aligner_cpu as ac
-from tests.util import load_golden
+from tests.util import assert_no_spill, load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -245,12 +243,7 @@ def test_duration_rule_by_hand():
 def test_new_kernels_do_not_spill():
     """Register hygiene of csrc/cross_attention.hip: no VGPR / SGPR spill, no scratch (tools/kernel_resources.py cross-compiles for
     gfx950 and reads the code object's metadata; no GPU needed)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "cross_attention.hip"), "--assert-no-spill"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_cross_attention<128>", "k_cross_attention<64>", "k_aln_durations", "k_aln_input"):
-        assert k in r.stdout, (k, r.stdout)
+    assert_no_spill("cross_attention.hip", kernels=("k_cross_attention<128>", "k_cross_attention<64>", "k_aln_durations", "k_aln_input"))
 
 
 @pytest.mark.parametrize("mutant", ac.DURATION_MUTANTS)

@@ -7,7 +7,6 @@ in exact arithmetic — the softmax does not see a key bias — so its fixture v
 float64; its 1e-10 and its ulp are taken relative to the other gradients' scale, not to its own maximum.)"""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,19 +14,14 @@ import torch
 
 from tests import attention_grad_cpu as ac
 from tests import lossgrad_cpu as lg
-from tests.util import load_golden
+from tests.util import built_lib, load_golden, run_c_caller
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()
 
 
 def _fixture(c):
@@ -209,16 +203,7 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
 
 
 def test_header_is_plain_c_and_validation_works_from_c(lib, tmp_path):
-    L, so = lib
-    exe = tmp_path / "ag_host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "ag_host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), L.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    run_c_caller("ag_host_only", lib[0].LIB_PATH, tmp_path)
 
 
 # ---------------------------------------------------------------------------------------------------- the Python surface

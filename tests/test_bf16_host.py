@@ -3,22 +3,17 @@ the configuration is accepted, the arena grows by exactly the rounded bf16 weigh
 register budget.  No compute calls."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import pytest
+
+from tests.util import assert_no_spill, built_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()  # hipcc cross-compiles gfx950 without a GPU; no-op when up to date
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()  # hipcc cross-compiles gfx950 without a GPU; no-op when up to date
 
 
 def _cfg(name="tiny", **over):
@@ -106,10 +101,8 @@ def test_dtype_casts_still_raise_and_name_the_mode():
 def test_bf16_kernels_do_not_spill(src):
     """The register gate of the fp32 sources (tests/test_cabi_and_host.py) over the bf16 GEMM tiles and the attention
     variants: no VGPR / SGPR spill, no scratch."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", src),
-                        "--assert-no-spill"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (src, r.stdout[-2000:], r.stderr[-2000:])
     if src == "gemm_bf16.hip":
-        assert r.stdout.count("k_conv_gemm_bf16<") >= 5, r.stdout
+        stdout = assert_no_spill(src)
+        assert stdout.count("k_conv_gemm_bf16<") >= 5, stdout
     else:
-        assert "k_attention<64, true>" in r.stdout and "k_attention_strip<64, true>" in r.stdout, r.stdout
+        assert_no_spill(src, kernels=("k_attention<64, true>", "k_attention_strip<64, true>"))

@@ -7,17 +7,14 @@ import re
 import numpy as np
 import pytest
 
+from tests.util import assert_no_spill, built_lib, run_c_caller
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()  # hipcc cross-compiles gfx950 without a GPU; no-op when up to date
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()  # hipcc cross-compiles gfx950 without a GPU; no-op when up to date
 
 
 def test_header_symbols_are_bound_and_exported(lib):
@@ -484,21 +481,10 @@ def test_launch_plan_invariants_and_settled_choices(lib):
 def test_header_is_plain_c_and_host_entry_points_work_from_c(lib, tmp_path):
     """include/nar_fs2.h is the drop-in boundary: it must compile as C99 (not only as the C++ the library is written in) and the
     host-side entry points must work from a plain C program through dlopen — no Python, no torch, no GPU."""
-    import subprocess
-
     L, _ = lib
-    exe = tmp_path / "host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), L.LIB_PATH if hasattr(L, "LIB_PATH") else os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "libnarfs2.so")],
-                       capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    stdout = run_c_caller("host_only", L.LIB_PATH if hasattr(L, "LIB_PATH") else os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "libnarfs2.so"), tmp_path)
     # the struct the C side sees is the struct the ctypes binding declares
-    assert f"sizeof(ns_config)={C.sizeof(L.NsConfig)} " in r.stdout
+    assert f"sizeof(ns_config)={C.sizeof(L.NsConfig)} " in stdout
 
 
 def test_no_kernel_spills_registers():
@@ -506,10 +492,4 @@ def test_no_kernel_spills_registers():
     scratch memory — tools/kernel_resources.py compiles the source for gfx950 (hipcc cross-compiles without a GPU) and reads the
     kernels' metadata.  Round 5 shipped 36-43 spilled SGPRs in the two-pass full-row tiles, 10-18 in two ticketed rungs and 18 in
     k_gauss_upsample; profiles/r06_kernel_resources.txt is the table for all five sources."""
-    import subprocess
-    import sys
-
-    for src in ("gemm_conv.hip", "rowops.hip"):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", src),
-                            "--assert-no-spill"], capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, (src, r.stdout[-2000:], r.stderr[-2000:])
+    assert_no_spill("gemm_conv.hip", "rowops.hip")

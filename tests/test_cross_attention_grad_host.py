@@ -8,8 +8,6 @@ fixture values are rounding noise; its 1e-10 and its ulp are taken relative to t
 tests/test_attention_grad_host.py.)"""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,7 +15,7 @@ import torch
 
 from tests import cross_attention_grad_cpu as xc
 from tests import lossgrad_cpu as lg
-from tests.util import load_golden
+from tests.util import assert_no_spill, built_lib, load_golden, run_c_caller
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the case table of tests/test_gpu_cross_attention_grad.py
@@ -28,12 +26,7 @@ _cid = lambda c: f"{c[0]}x{c[1]}x{c[2]}"  # noqa: E731
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()
 
 
 def _fixture(c):
@@ -277,24 +270,11 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
 
 
 def test_header_is_plain_c_and_validation_works_from_c(lib, tmp_path):
-    L_, so = lib
-    exe = tmp_path / "xg_host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "xg_host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), L_.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    run_c_caller("xg_host_only", lib[0].LIB_PATH, tmp_path)
 
 
 def test_the_new_kernels_do_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "xattngrad.hip"),
-                        "--assert-no-spill"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_xg_bwd_q<64>", "k_xg_bwd_q<128>", "k_xg_bwd_kv<64>", "k_xg_bwd_kv<128>", "k_xg_kv_reduce"):
-        assert k in r.stdout, r.stdout
+    assert_no_spill("xattngrad.hip", kernels=("k_xg_bwd_q<64>", "k_xg_bwd_q<128>", "k_xg_bwd_kv<64>", "k_xg_bwd_kv<128>", "k_xg_kv_reduce"))
 
 
 # ---------------------------------------------------------------------------------------------------- the Python surface

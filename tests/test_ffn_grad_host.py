@@ -7,8 +7,6 @@ not see a key bias — so its bounds are taken relative to the other gradients' 
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,7 +14,7 @@ import torch
 
 from tests import attention_grad_cpu as ac
 from tests import ffn_grad_cpu as fc
-from tests.util import load_golden
+from tests.util import assert_no_spill, built_lib, expect_refusals, load_golden, run_c_caller
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ((2, 1), (3, 5), (2, 33), (1, 65), (3, 130))  # the (B, S) table of tests/test_gpu_ffn_grad.py
@@ -24,12 +22,7 @@ CASES = ((2, 1), (3, 5), (2, 33), (1, 65), (3, 130))  # the (B, S) table of test
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()
 
 
 def _fixture(c):
@@ -208,7 +201,7 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
         return so.ns_fg_backward(C.byref(s), C.byref(w or weights()), P(x), P(keep), p, P(saved), P(g), C.byref(d), P(ws), nbytes, None)
 
     for call in (fwd, bwd):
-        for kw, msg in ((dict(x=0), "null argument"), (dict(ws=0), "null argument"), (dict(x=0x9000004), "x must be 16-byte aligned"),
+        expect_refusals(err, call, ((dict(x=0), "null argument"), (dict(ws=0), "null argument"), (dict(x=0x9000004), "x must be 16-byte aligned"),
                         (dict(ws=0xC000008), "the workspace must be 16-byte aligned"), (dict(saved=0xB000004), "saved must be 16-byte aligned"),
                         (dict(shape=dict(d=128)), "d must be 256 or 512"), (dict(shape=dict(d=384)), "d must be 256 or 512"),
                         (dict(shape=dict(d_inner=0)), "d_inner must be a positive multiple of 256"),
@@ -223,8 +216,7 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
                         (dict(p=float("nan")), "p_drop must lie in [0, 1)"), (dict(p=0.5), "needs a keep-mask"),
                         (dict(keep=0xE000000), "although p_drop == 0"), (dict(p=0.5, keep=0xE000004), "16-byte aligned"),
                         (dict(w=weights(w2=0)), "null weights->w2"), (dict(w=weights(b1=0)), "null weights->b1"),
-                        (dict(w=weights(ln_g=0x100004)), "weights->ln_g must be 16-byte aligned"), (dict(nbytes=1024), "workspace too small")):
-            assert call(**kw) != 0 and msg in err(), (call.__name__, kw, err())
+                        (dict(w=weights(ln_g=0x100004)), "weights->ln_g must be 16-byte aligned"), (dict(nbytes=1024), "workspace too small")))
     assert fwd(saved=0, nbytes=64) != 0 and "workspace too small" in err()  # saved is nullable in the forward
     assert fwd(y=0) != 0 and "null argument" in err()
     assert fwd(y=0xA000004) != 0 and "y must be 16-byte aligned" in err()
@@ -249,23 +241,11 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
 
 
 def test_header_is_plain_c_and_validation_works_from_c(lib, tmp_path):
-    L, so = lib
-    exe = tmp_path / "fg_host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "fg_host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), L.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    run_c_caller("fg_host_only", lib[0].LIB_PATH, tmp_path)
 
 
 def test_the_new_kernel_does_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "ffngrad.hip"),
-                        "--assert-no-spill"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "k_fg_relu_gate" in r.stdout, r.stdout
+    assert_no_spill("ffngrad.hip", kernels=("k_fg_relu_gate",))
 
 
 # ---------------------------------------------------------------------------------------------------- the Python surface

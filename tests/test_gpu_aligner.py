@@ -10,7 +10,7 @@ import smart_nar_fast_tts_amd.workload as wl
 from smart_nar_fast_tts_amd import ops
 from smart_nar_fast_tts_amd.model import FastSpeech2Align
 from tests import aligner_cpu as ac
-from tests.util import load_golden
+from tests.util import dev, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +19,6 @@ KEY_STRIP = 32     # keys per strip
 FIXTURES = ("aligner_tiny", "aligner_T_above_1000")
 
 _CACHE = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def aligned(name):

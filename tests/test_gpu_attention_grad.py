@@ -25,7 +25,7 @@ from tests import attention_grad_cpu as ac
 from tests import bf16_emu as E
 from tests import lossgrad_cpu as lg
 from tests import optim_cpu as oc
-from tests.test_gpu_fp32_ops import _report
+from tests.util import dev, native_lib, report
 
 pytestmark = pytest.mark.gpu
 REL = E.FP32_REL
@@ -35,15 +35,9 @@ _cid = lambda c: f"{c[0]}x{c[1]}"  # noqa: E731
 _fid = lambda c: f"d{c[0]}h{c[1]}"  # noqa: E731
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 @pytest.fixture(scope="module")
 def so():
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return native_lib()
 
 
 def _ws(nbytes, fill=0xFF):
@@ -139,7 +133,7 @@ def test_lse_alone_elementwise(so, cfg, case):
     B, S, lens = case
     qkv = np.random.RandomState(B * S + H).standard_normal((B, S, 3 * d)).astype(np.float32)
     share, _ = _lse_check(so, qkv, lens, B, S, d, H)
-    _report(test="ag_lse", cfg=_fid(cfg), case=_cid(case), share=share)
+    report(test="ag_lse", cfg=_fid(cfg), case=_cid(case), share=share)
     assert share <= 1.0, share
 
 
@@ -155,7 +149,7 @@ def test_lse_at_scores_around_90(so, cfg):
     share, ref = _lse_check(so, qkv, lens, B, S, d, H)
     assert 80 < float(ref.min()) and float(ref.max()) < 120
     assert not bool(torch.isfinite(ac.lse_of(qkv, lens, H, torch.float32, with_max=False)).all())
-    _report(test="ag_lse_shifted", cfg=_fid(cfg), share=share)
+    report(test="ag_lse_shifted", cfg=_fid(cfg), share=share)
     assert share <= 1.0, share
 
 
@@ -186,7 +180,7 @@ def test_attention_backward_alone(so, cfg, case):
         a, w64, w32 = (t[..., i * d:(i + 1) * d].double() for t in (got, r64, r32))
         gate = 2.0 * float((w32 - w64).abs().max()) + lg.ulp32(float(w64.abs().max()))
         sh[n] = float((a - w64).abs().max() / gate) if bool(torch.isfinite(a).all()) else float("inf")
-    _report(test="ag_attention_backward", cfg=_fid(cfg), case=_cid(case), shares=sh)
+    report(test="ag_attention_backward", cfg=_fid(cfg), case=_cid(case), shares=sh)
     # dK and dV at keys >= lens[b]: exactly +0.0
     pad = torch.from_numpy(np.arange(S)[None, :] >= np.asarray(lens)[:, None])
     assert not got[..., d:][pad].view(torch.int32).any()
@@ -228,7 +222,7 @@ def test_row_backward_alone(so, p, d):
     sh = ac.shares({n: outs[n].cpu().numpy() for n in r64}, r64, gates, names=list(r64))
     if keep is not None:
         assert not outs["du"][dev(~keep)].any()
-    _report(test="ag_row_backward", p=p, d=d, shares=sh)
+    report(test="ag_row_backward", p=p, d=d, shares=sh)
     assert max(sh.values()) <= 1.0, sh
 
 
@@ -262,7 +256,7 @@ def test_module_forward_and_backward(so, cfg, case):
     sh = _grad_shares(cfg, case, x, g, parts, grads)
     fwd = 1 + _gemm_launches(lib, M, 3 * d, d) + 1 + 1 + _gemm_launches(lib, M, d, d) + 1
     bwd = 14 + _gemm_launches(lib, M, d, d) + _gemm_launches(lib, M, d, 3 * d)
-    _report(test="ag_module", cfg=_fid(cfg), case=_cid(case), mode="eval", launches=launches, qkv=c1.worst, y=c2.worst, shares=sh)
+    report(test="ag_module", cfg=_fid(cfg), case=_cid(case), mode="eval", launches=launches, qkv=c1.worst, y=c2.worst, shares=sh)
     assert launches == dict(forward=fwd, backward=bwd), (launches, fwd, bwd)  # the counts include/nar_fs2.h states
     assert max(sh.values()) <= 1.0, sh
     # ---- train() at p = 0.5 with a given keep-mask
@@ -278,7 +272,7 @@ def test_module_forward_and_backward(so, cfg, case):
     y64 = E.layernorm_emu(z, wt["ln_g"], wt["ln_b"])
     assert bool(((y.double() - y64).abs() <= REL * (y64.abs() + wt["ln_b"].double().abs())).all())
     sh = _grad_shares(cfg, case, x, g, parts, grads, keep, m.p_drop)
-    _report(test="ag_module", cfg=_fid(cfg), case=_cid(case), mode="train_p0.5", launches=launches, shares=sh)
+    report(test="ag_module", cfg=_fid(cfg), case=_cid(case), mode="train_p0.5", launches=launches, shares=sh)
     assert max(sh.values()) <= 1.0, sh
 
 
@@ -335,7 +329,7 @@ def test_needs_input_grad_run_to_run_bits_and_replicas(so):
         bad[0, 1, 2] = True
         with pytest.raises(ValueError, match="not a key-padding mask"):
             m(xd, xd, xd, mask=bad)
-        _report(test="ag_launches", forward=a[3]["forward"], backward=a[3]["backward"], backward_no_dx=nx[3]["backward"], backward_frozen_wq=fz[3]["backward"],
+        report(test="ag_launches", forward=a[3]["forward"], backward=a[3]["backward"], backward_no_dx=nx[3]["backward"], backward_frozen_wq=fz[3]["backward"],
                 backward_tail_only=tail[3]["backward"])
     finally:
         for p in params:
@@ -381,5 +375,5 @@ def test_one_native_training_step():
     for k, a, t32, w64 in zip(ac.NAMES[:10], got, chain["f32"], chain["f64"]):
         err = np.abs(a.astype(np.float64) - w64).max()
         sh[k] = float(err / oc.gate_of(t32, w64)) if np.isfinite(err) else float("inf")
-    _report(test="ag_native_step", shares=sh)
+    report(test="ag_native_step", shares=sh)
     assert max(sh.values()) <= 1.0, sh

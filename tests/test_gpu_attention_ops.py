@@ -16,7 +16,6 @@ that the gates below reject the wrong versions that matter.  Here, for every row
 
 Every test reports the form, the key ranges, the worst error on the GPU and torch's fp32 CPU evaluation of the same input (reported,
 not gated); NS_ATTENTION_OPS_REPORT=<path> appends the rows to a JSON-lines file (profiles/attention_ops.md was written from one)."""
-import json
 import os
 import subprocess
 import sys
@@ -27,6 +26,7 @@ import torch
 import tests.test_attention_ops_host as H
 from tests import attention_cpu as AC
 from tests import bf16_emu as E
+from tests.util import reporter
 
 pytestmark = pytest.mark.gpu
 
@@ -34,12 +34,7 @@ PAD = 1024  # floats on either side of `out` inside the larger tensor (a multipl
 _FP32 = {}
 
 
-def _report(**row):
-    print(json.dumps(row))
-    path = os.environ.get("NS_ATTENTION_OPS_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(row) + "\n")
+_report = reporter("NS_ATTENTION_OPS_REPORT")
 
 
 def _cpu_fp32_err(c, spiked=False):

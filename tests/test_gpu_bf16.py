@@ -16,7 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import load_golden, weights_for
+from tests.util import dev, load_golden, weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +33,6 @@ EMU_FRAC = 0.75
 NOISE_REL = 2e-7
 LJ = dict(config="ljspeech", weight_seed=0, frames_per_phoneme=8.0, dur_weight_scale=0.25)
 TINY = dict(config="tiny", weight_seed=0, frames_per_phoneme=4.0, dur_weight_scale=0.25)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 _MODELS = {}

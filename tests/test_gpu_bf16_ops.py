@@ -12,15 +12,12 @@ worst 0.020 of theirs, attention worst element 1.87 flips of the 3 allowed and a
 fp32 tier (cap 5 %).
 
 NS_BF16_OPS_REPORT=<path> appends every measured figure to a JSON-lines file (profiles/bf16_ops_r09.md was written from one)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from tests import bf16_emu as E
-from tests.util import weights_for
+from tests.util import reporter, weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -46,12 +43,7 @@ LARGE = [
 ]
 
 
-def _report(**row):
-    print(json.dumps(row))
-    path = os.environ.get("NS_BF16_OPS_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(row) + "\n")
+_report = reporter("NS_BF16_OPS_REPORT")
 
 
 def _build(meta, sd_override=None, modes=("fp32", "bf16")):

@@ -32,9 +32,6 @@ same-sign cases fail (2.1 ... 2.6 x, signed mean -7.3e-6 or worse) while the who
 Every case reports torch's fp32 CPU figure beside the GPU's (reported, not gated).  NS_FP32_OPS_REPORT=<path> appends every figure
 to a JSON-lines file (profiles/bf16x3_ops.md was written from one).  Inf / NaN operands are out of scope (the split makes an Inf a
 NaN through Inf - Inf)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -42,6 +39,7 @@ import torch
 import tests.test_gpu_bf16_ops as BO
 from tests import bf16_emu as E
 from tests import bf16x3_emu as X
+from tests.util import report as _report
 from tests.util import weights_for
 
 pytestmark = pytest.mark.gpu
@@ -50,14 +48,6 @@ REL = E.FP32_REL
 METAS = {"tiny": BO.METAS["tiny"], "tiny512": dict(config="tiny512", weight_seed=0, frames_per_phoneme=4.0, dur_weight_scale=0.25)}
 SAME_SIGN_LAYERS = [X.L0 + ".pos_ffn.w_1", X.L0 + ".slf_attn.qkv"]
 _MODELS = {}
-
-
-def _report(**row):
-    print(json.dumps(row))
-    path = os.environ.get("NS_FP32_OPS_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(row) + "\n")
 
 
 def models(config, same=False, fp32=False):

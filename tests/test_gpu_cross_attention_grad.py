@@ -30,7 +30,7 @@ from tests import bf16_emu as E
 from tests import cross_attention_grad_cpu as xc
 from tests import lossgrad_cpu as lg
 from tests import optim_cpu as oc
-from tests.test_gpu_fp32_ops import _report
+from tests.util import dev, native_lib, report
 
 pytestmark = pytest.mark.gpu
 REL = E.FP32_REL
@@ -40,19 +40,13 @@ _cid = lambda c: f"{c[0]}x{c[1]}x{c[2]}"  # noqa: E731
 _fid = lambda c: f"d{c[0]}h{c[1]}"  # noqa: E731
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def lens_d(lens):
     return dev(np.asarray(lens, dtype=np.int64))
 
 
 @pytest.fixture(scope="module")
 def so():
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return native_lib()
 
 
 def _gemm_launches(lib, M, N, K):
@@ -170,7 +164,7 @@ def test_attention_backward_alone(so, cfg, case):
                 x = got[n].double()
                 sh[n] = float((x - w64).abs().max() / gate) if bool(torch.isfinite(x).all()) else float("inf")
             print(f"{_fid(cfg)} {_cid(case)} dA {name} kv_splits {ks}: {sh}")
-            _report(test="xg_attention_backward", cfg=_fid(cfg), case=_cid(case), dA=name, kv_splits=ks, shares=sh)
+            report(test="xg_attention_backward", cfg=_fid(cfg), case=_cid(case), dA=name, kv_splits=ks, shares=sh)
             for n, v in sh.items():
                 worst[n] = max(worst.get(n, 0.0), v)
             # dK and dV at keys >= src_lens[b]: exactly +0.0
@@ -206,7 +200,7 @@ def test_forward(so, cfg, case):
     c3 = E.gemm_ln_check(y, ctx, wt["wfc"], wt["bfc"], tt, wt["ln_g"], wt["ln_b"], rel=REL, round_fn=E.exact)
     rp, rc = al.attention_gate(q, kv, torch.as_tensor(lens), H, ctx, attn)
     print(f"{_fid(cfg)} {_cid(case)}: q {c1.worst:.3g} kv {c2.worst:.3g} y {c3.worst:.3g} attn {rp:.3g} ctx {rc:.3g}")
-    _report(test="xg_forward", cfg=_fid(cfg), case=_cid(case), q=c1.worst, kv=c2.worst, y=c3.worst, attn=rp, ctx=rc)
+    report(test="xg_forward", cfg=_fid(cfg), case=_cid(case), q=c1.worst, kv=c2.worst, y=c3.worst, attn=rp, ctx=rc)
     masked = torch.from_numpy(np.broadcast_to(xc.key_mask(lens, L).numpy()[:, None], tuple(attn.shape)).copy())
     assert not attn[masked].view(torch.int32).any(), "masked keys hold exactly +0.0"
     fwd = 1 + _gemm_launches(lib, B * T, d, d) + _gemm_launches(lib, B * L, 2 * d, d) + 1 + _gemm_launches(lib, B * T, d, d) + 1
@@ -239,7 +233,7 @@ def test_module_forward_and_backward(so, cfg, case):
     parts = _saved_parts(saved, attn, B, T, L, d, H)
     sh = _grad_shares(cfg, case, tgt, src, g, a, parts, grads)
     print(f"{_fid(cfg)} {_cid(case)} eval: {sh}")
-    _report(test="xg_module", cfg=_fid(cfg), case=_cid(case), mode="eval", launches=launches, shares=sh)
+    report(test="xg_module", cfg=_fid(cfg), case=_cid(case), mode="eval", launches=launches, shares=sh)
     assert launches["backward"] == bwd, (launches, bwd)  # the count include/nar_fs2.h states
     worst = dict(sh)
     # ---- train() at p = 0.5 with a given keep-mask
@@ -257,7 +251,7 @@ def test_module_forward_and_backward(so, cfg, case):
     assert bool(((y.double() - y64).abs() <= REL * (y64.abs() + wt["ln_b"].double().abs())).all())
     sh = _grad_shares(cfg, case, tgt, src, g, a, parts, grads, keep, m.p_drop)
     print(f"{_fid(cfg)} {_cid(case)} train p=0.5: {sh}")
-    _report(test="xg_module", cfg=_fid(cfg), case=_cid(case), mode="train_p0.5", launches=launches, shares=sh)
+    report(test="xg_module", cfg=_fid(cfg), case=_cid(case), mode="train_p0.5", launches=launches, shares=sh)
     assert launches["backward"] == bwd, (launches, bwd)
     for n, v in sh.items():
         worst[n] = max(worst[n], v)
@@ -345,7 +339,7 @@ def test_needs_input_grad_run_to_run_bits_replicas_and_no_host_read(so):
         sa = sublayers.MultiHeadAttention(H, d, d // H, d // H).cuda()
         with pytest.raises(NotImplementedError, match="self-attention only"):
             sa(td, sd, sd)
-        _report(test="xg_launches", forward=x[3]["forward"], backward=x[3]["backward"], backward_no_dsrc=ns[3]["backward"],
+        report(test="xg_launches", forward=x[3]["forward"], backward=x[3]["backward"], backward_no_dsrc=ns[3]["backward"],
                 backward_frozen_wq=fz[3]["backward"], backward_tail_only=tail[3]["backward"])
     finally:
         for p in params:
@@ -393,5 +387,5 @@ def test_one_chain_from_a_loss_shaped_map_gradient_into_the_optimiser():
         err = np.abs(x.astype(np.float64) - w64).max()
         sh[k] = float(err / oc.gate_of(t32, w64)) if np.isfinite(err) else float("inf")
     print(sh)
-    _report(test="xg_chain", shares=sh)
+    report(test="xg_chain", shares=sh)
     assert max(sh.values()) <= 1.0, sh

@@ -26,7 +26,7 @@ from tests import attention_grad_cpu as ac
 from tests import bf16_emu as E
 from tests import ffn_grad_cpu as fc
 from tests import optim_cpu as oc
-from tests.test_gpu_fp32_ops import _report
+from tests.util import dev, native_lib, report
 
 pytestmark = pytest.mark.gpu
 REL = E.FP32_REL
@@ -36,15 +36,9 @@ _cid = lambda c: f"{c[0]}x{c[1]}"  # noqa: E731
 _fid = lambda c: f"d{c[0]}i{c[1]}k{c[2]}{c[3]}"  # noqa: E731
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 @pytest.fixture(scope="module")
 def so():
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return native_lib()
 
 
 def _G(lib, M, N, Cin, KW):
@@ -131,7 +125,7 @@ def test_relu_gate_alone(so, shape, in_place):
         if with_bias:
             err = np.abs(b1_d.cpu().numpy().astype(np.float64) - col)
             bound = 2.0 ** -24 * np.abs(col) + 1e-30
-            _report(test="fg_relu_gate", shape=_cid(shape), in_place=in_place, d_b1=float((err / bound).max()))
+            report(test="fg_relu_gate", shape=_cid(shape), in_place=in_place, d_b1=float((err / bound).max()))
             assert (err <= bound).all(), float((err / bound).max())
 
 
@@ -163,7 +157,7 @@ def test_module_forward_and_backward(so, cfg, case):
     z_share = float(((z.double() - z64).abs() / (REL * unit + REL * z64.abs())).max())
     sh = _grad_shares(cfg, x, g, (h, z), grads)
     fwd, bwd = _counts(lib, cfg, B * S)
-    _report(test="fg_module", cfg=_fid(cfg), case=_cid(case), mode="eval", launches=launches, h=c1.worst, z=z_share, y=c2.worst, shares=sh)
+    report(test="fg_module", cfg=_fid(cfg), case=_cid(case), mode="eval", launches=launches, h=c1.worst, z=z_share, y=c2.worst, shares=sh)
     assert c1.ok and c2.ok and z_share <= 1.0, (str(c1), str(c2), z_share)
     assert launches == dict(forward=fwd, backward=bwd), (launches, fwd, bwd)  # the counts include/nar_fs2.h states
     assert max(sh.values()) <= 1.0, sh
@@ -178,7 +172,7 @@ def test_module_forward_and_backward(so, cfg, case):
     y64 = E.layernorm_emu(z, wt["ln_g"], wt["ln_b"])
     assert bool(((y.double() - y64).abs() <= REL * (y64.abs() + wt["ln_b"].double().abs())).all())
     sh = _grad_shares(cfg, x, g, (h2, z), grads, keep, m.p_drop)
-    _report(test="fg_module", cfg=_fid(cfg), case=_cid(case), mode="train_p0.5", launches=launches, shares=sh)
+    report(test="fg_module", cfg=_fid(cfg), case=_cid(case), mode="train_p0.5", launches=launches, shares=sh)
     assert launches == dict(forward=fwd, backward=bwd), (launches, fwd, bwd)
     assert max(sh.values()) <= 1.0, sh
 
@@ -230,7 +224,7 @@ def test_needs_input_grad_run_to_run_bits_and_replicas(so):
             quiet = m(dev(x))
         assert quiet.cpu().numpy().tobytes() == a[0].tobytes() and not quiet.requires_grad, "a forward that saves nothing gives the same y bits"
         assert m.last_launches["forward"] == a[3]["forward"]
-        _report(test="fg_launches", forward=a[3]["forward"], backward=a[3]["backward"], backward_no_dx=nx[3]["backward"],
+        report(test="fg_launches", forward=a[3]["forward"], backward=a[3]["backward"], backward_no_dx=nx[3]["backward"],
                 backward_tail_only=tail[3]["backward"], backward_ln_g_only=only_g[3]["backward"])
     finally:
         for p in params:
@@ -327,5 +321,5 @@ def test_one_native_training_step():
     for k, a, t32, w64 in zip(fc.NAMES[:6], got, chain["f32"], chain["f64"]):
         err = np.abs(a.astype(np.float64) - w64).max()
         sh[k] = float(err / oc.gate_of(t32, w64)) if np.isfinite(err) else float("inf")
-    _report(test="fg_native_step", shares=sh)
+    report(test="fg_native_step", shares=sh)
     assert max(sh.values()) <= 1.0, sh

@@ -10,29 +10,19 @@ ops.multi_head_attention on the GPU's own hidden / attention input, so only the 
 Every case also reports the same figure for torch's fp32 CPU evaluation of the same inputs (reported, not gated): what "as close to
 float64 as the reference's own fp32" means per kernel form.  NS_FP32_OPS_REPORT=<path> appends every figure (form, shape, GPU and
 CPU-fp32 worst ratios) to a JSON-lines file, from which a per-form table under profiles/ is written."""
-import json
-import os
-
 import pytest
 import torch
 
 import tests.test_fp32_ops_host as T
 import tests.test_gpu_bf16_ops as BO
 from tests import bf16_emu as E
+from tests.util import report as _report
 
 pytestmark = pytest.mark.gpu
 
 REL = E.FP32_REL
 METAS = dict(BO.METAS, tiny512=dict(config="tiny512", weight_seed=0, frames_per_phoneme=4.0, dur_weight_scale=0.25))
 _MODELS = {}
-
-
-def _report(**row):
-    print(json.dumps(row))
-    path = os.environ.get("NS_FP32_OPS_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(row) + "\n")
 
 
 def models(config):

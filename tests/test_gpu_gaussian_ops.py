@@ -22,7 +22,7 @@ import torch
 
 from smart_nar_fast_tts_amd import _lib, ops
 from tests import gaussian_cpu as gc
-from tests.test_gpu_fp32_ops import _report
+from tests.util import report as _report
 
 pytestmark = pytest.mark.gpu
 

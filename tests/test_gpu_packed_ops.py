@@ -17,9 +17,6 @@ rejects the wrong versions that matter; here the kernels are held to the same re
 
 Every figure is also reported next to torch's fp32 CPU evaluation of the same inputs (reported, not gated);
 NS_PACKED_OPS_REPORT=<path> appends them to a JSON-lines file (profiles/packed_ops.md was written from one)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -29,7 +26,7 @@ import tests.test_packed_ops_host as H
 from tests import bf16_emu as E
 from tests import packed_cpu as PC
 from tests.test_gpu_rowops import duration_case
-from tests.util import weights_for
+from tests.util import reporter, weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -39,12 +36,7 @@ METAS = dict(BO.METAS, tiny512=dict(config="tiny512", weight_seed=0, frames_per_
 _MODELS, _SD = {}, {}
 
 
-def _report(**row):
-    print(json.dumps(row))
-    path = os.environ.get("NS_PACKED_OPS_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(row) + "\n")
+_report = reporter("NS_PACKED_OPS_REPORT")
 
 
 def model(config, mode="fp32", row_epilogue="fused"):

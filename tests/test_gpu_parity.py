@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import load_golden, weights_for
+from tests.util import dev, load_golden, weights_for
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +32,6 @@ def gpu_model(meta):
         m.load_state_dict(sd)
         _MODEL[key] = (cfg, sd, m)
     return _MODEL[key]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def run_gpu(m, z, meta, texts_key="texts", p_targets=None, e_targets=None):

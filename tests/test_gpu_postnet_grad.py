@@ -23,7 +23,7 @@ from tests import bf16_emu as E
 from tests import optim_cpu as oc
 from tests import postnet_grad_cpu as pc
 from tests.predictor_grad_cpu import wgrad
-from tests.test_gpu_fp32_ops import _report
+from tests.util import dev, native_lib, report
 
 pytestmark = pytest.mark.gpu
 REL = E.FP32_REL
@@ -35,15 +35,9 @@ CONFIGS = [(c, BASE) for c in CASES] + [((5, 130), (80, 512, 5, 5)), ((5, 130), 
 _id = lambda cc: f"{cc[0][0]}x{cc[0][1]}_mel{cc[1][0]}_emb{cc[1][1]}_n{cc[1][3]}"  # noqa: E731
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 @pytest.fixture(scope="module")
 def so():
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return native_lib()
 
 
 def _ws(nbytes=64 << 20, fill=0xFF):
@@ -101,7 +95,7 @@ def test_stats_alone(so, M, Cw):
     want_rv = 0.9 * rv0.astype(np.float64) + 0.1 * var * M / (M - 1)
     s_rm = (np.abs(rm - want_rm) / _ulp(want_rm)).max()
     s_rv = (np.abs(rv - want_rv) / _ulp(want_rv)).max()
-    _report(test="pn_stats", M=M, C=Cw, mu=e_mu, rstd=e_rs, running_mean_ulp=s_rm, running_var_ulp=s_rv)
+    report(test="pn_stats", M=M, C=Cw, mu=e_mu, rstd=e_rs, running_mean_ulp=s_rm, running_var_ulp=s_rv)
     # (rstd: the one-pass variance E[u^2] - mu^2 in float64 is off by about 1e-15 E[u^2] absolute, which 1 / (2 (var + 1e-5)) magnifies
     #  to at most 5e-11 E[u^2] relative where a column's variance is far below eps — possible at M = 2; E[u^2] is below 20 here)
     assert e_mu <= 1e-13 and e_rs <= 1e-9 and s_rm <= 1.0 and s_rv <= 1.0
@@ -146,7 +140,7 @@ def test_apply_alone(so, M, Cw, p, last):
     got = h.cpu().numpy()
     assert np.isnan(got[M]).all() and np.isfinite(got[:M]).all()
     share = (np.abs(got[:M] - want) / _ulp(want)).max()
-    _report(test="pn_apply", M=M, C=Cw, p=p, last=last, ulps=share)
+    report(test="pn_apply", M=M, C=Cw, p=p, last=last, ulps=share)
     assert share <= 1.0
     if keep is not None:
         assert not got[:M][keep == 0].any()
@@ -212,7 +206,7 @@ def test_backward_kernels_alone(so, M, Cw, p, last):
             assert sh <= 1.0 and sb <= 1.0, (mode, ldz, sh, sb)
             if mode == "train" and M > 2:
                 assert (np.abs(gb[:Cw]) <= 1e-12 * abs_b + 1e-30).all(), "train-mode d_bias is float64 rounding noise"
-    _report(test="pn_backward_kernels", M=M, C=Cw, p=p, last=last, d_beta=sh_b, d_gamma=sh_g, dz=worst)
+    report(test="pn_backward_kernels", M=M, C=Cw, p=p, last=last, d_beta=sh_b, d_gamma=sh_g, dz=worst)
 
 
 @pytest.mark.parametrize("B,S,N,Cin", [(3, 5, 80, 512), (5, 130, 80, 512), (5, 130, 16, 256), (2, 1, 80, 512)])
@@ -233,7 +227,7 @@ def test_wgrad_narrow_alone(so, B, S, N, Cin):
     dz64, x64 = torch.from_numpy(dz[..., :N]).double(), torch.from_numpy(x).double()
     ref, unit = wgrad(dz64, x64, K, 2), wgrad(dz64.abs(), x64.abs(), K, 2)
     share = float(((got[:N] - ref).abs() / (REL * unit).clamp_min(1e-300)).max())
-    _report(test="pn_wgrad_narrow", case=f"{B}x{S}", N=N, Cin=Cin, share=share)
+    report(test="pn_wgrad_narrow", case=f"{B}x{S}", N=N, Cin=Cin, share=share)
     assert share <= 1.0
     if B > 1 and S > 1:
         cross = wgrad(dz64, x64, K, 2, cross=True)
@@ -341,7 +335,7 @@ def test_module_forward_and_backward(so, cc, mode, p):
     sh = pc.shares(got, r64, gates)
     cl = pc.classes(sh)
     print(_id(cc), mode, p, "worst share per class", {k: f"{v:.3g}" for k, v in cl.items()}, launches)
-    _report(test="pn_module", case=_id(cc), mode=mode, p=p, launches=launches, classes=cl)
+    report(test="pn_module", case=_id(cc), mode=mode, p=p, launches=launches, classes=cl)
     chans = [n_mel] + [emb] * (n - 1) + [n_mel]
     fwd = (n + 1) // 2 + sum(_gemm_launches(so, M, chans[i + 1], chans[i]) + (3 if mode == "train" else 2) for i in range(n))
     bwd = (n + 1) // 2 + 1 + sum(3 + 2 + _gemm_launches(so, M, chans[i], chans[i + 1]) for i in range(n)) + 1
@@ -384,7 +378,7 @@ def test_buffers_after_one_and_two_forwards_also_under_no_grad(so):
         w2 = {k: (r64[k] if k[:2] in ("rm", "rv") else v) for k, v in w.items()}
         q64, _ = pc.autograd_ref(x, w2, g, None, 0.0, True, torch.float64)
         sh2 = pc.shares(two, q64, pc.gate(q32, q64), pc.buffer_names(n))
-        _report(test="pn_buffers", one=pc.classes(sh1), two=pc.classes(sh2))
+        report(test="pn_buffers", one=pc.classes(sh1), two=pc.classes(sh2))
         assert max(sh2.values()) <= 1.0 and all(two[f"nbt{i}"] == int(w[f"nbt{i}"]) + 2 for i in range(n)), sh2
         assert y2.detach().cpu().numpy().tobytes() == y.cpu().numpy().tobytes(), "train-mode output does not depend on the running statistics"
     finally:
@@ -435,7 +429,7 @@ def test_needs_input_grad_launch_counts_and_run_to_run_bits(so):
             m.train()
             quiet = m(dev(x))
         assert quiet.cpu().numpy().tobytes() == a[0] and not quiet.requires_grad
-        _report(test="pn_launches", forward=a[3]["forward"], backward=full, only_dx=dx[3]["backward"], only_last=last[3]["backward"], no_layer0=no0[3]["backward"])
+        report(test="pn_launches", forward=a[3]["forward"], backward=full, only_dx=dx[3]["backward"], only_last=last[3]["backward"], no_layer0=no0[3]["backward"])
     finally:
         m.dropout = 0.5
         _reset(cfg)
@@ -503,7 +497,7 @@ def test_eval_forward_equals_the_folded_inference_postnet_and_a_trained_state_di
     model.load_state_dict(sd2)
     with torch.no_grad():
         e2 = float((pn(x) - ops.postnet(model, x)).abs().max())
-    _report(test="pn_eval_vs_folded", before=e1, after_training_forward=e2)
+    report(test="pn_eval_vs_folded", before=e1, after_training_forward=e2)
     assert e1 <= OP_TOL and e2 <= OP_TOL, (e1, e2)
 
 
@@ -598,5 +592,5 @@ def test_one_native_training_step_through_the_residual_and_an_l1_loss(so):
         err = np.abs(a.astype(np.float64) - w64)
         sh[k] = float((err / bound).max()) if np.isfinite(err).all() else float("inf")
     sh["mel.grad"] = pc.shares({"dx": mel.grad.cpu().numpy()}, {"dx": dmel["f64"]}, pc.gate({"dx": dmel["f32"]}, {"dx": dmel["f64"]}))["dx"]
-    _report(test="pn_native_step", shares=pc.classes(sh))
+    report(test="pn_native_step", shares=pc.classes(sh))
     assert max(sh.values()) <= 1.0, sh

@@ -25,8 +25,7 @@ from tests import bf16_emu as E
 from tests import lossgrad_cpu as lg
 from tests import optim_cpu as oc
 from tests import predictor_grad_cpu as pc
-from tests.test_gpu_fp32_ops import _report
-from tests.util import load_golden
+from tests.util import dev, load_golden, native_lib, report
 
 pytestmark = pytest.mark.gpu
 REL = E.FP32_REL
@@ -36,15 +35,9 @@ CONFIGS = {"tiny": 256, "tiny512": 512}
 _id = lambda c: f"{c[0]}x{c[1]}"  # noqa: E731
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 @pytest.fixture(scope="module")
 def so():
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return native_lib()
 
 
 def _plan(so, M, N, Cin, K):
@@ -99,7 +92,7 @@ def test_wgrad_alone_elementwise(so, case, K):
     if B > 1 and S > 1:
         cross = pc.wgrad(dz64, x64, K, (K - 1) // 2, cross=True)
         assert not bool(((cross - ref).abs() <= REL * unit).all())
-    _report(test="pg_wgrad", case=_id(case), K=K, Cin=Cin, ranges=_plan(so, M, F, Cin, K)[3], share=share, share_db=share_b)
+    report(test="pg_wgrad", case=_id(case), K=K, Cin=Cin, ranges=_plan(so, M, F, Cin, K)[3], share=share, share_db=share_b)
 
 
 @pytest.mark.parametrize("K", [3, 5])
@@ -123,7 +116,7 @@ def test_dgrad_alone_elementwise(so, case, K):
     if K > 1 and S > 1:
         noflip = pc.dgrad(dz64, w64, (K - 1) // 2, mutate="dgrad_without_tap_flip")
         assert not bool(((noflip - ref).abs() <= REL * unit).all())
-    _report(test="pg_dgrad", case=_id(case), K=K, Cin=Cin, share=share)
+    report(test="pg_dgrad", case=_id(case), K=K, Cin=Cin, share=share)
 
 
 def _row_ref(tail, up, g, mask, v, w, keep, p, dtype):
@@ -179,7 +172,7 @@ def test_row_backward_alone(so, tail, p, Fw):
     else:
         assert not outs["dz"][dev(mask)].any()  # +0 behind the mask, NaN in g or not
     assert (outs["dz"][dev(v) <= 0] == 0).all()
-    _report(test="pg_row_backward", tail=tail, p=p, F=Fw, shares=worst)
+    report(test="pg_row_backward", tail=tail, p=p, F=Fw, shares=worst)
     assert max(worst.values()) <= 1.0, worst
 
 
@@ -248,7 +241,7 @@ def test_module_forward_and_backward(config, case):
     r32 = _flat(pc.closed_form(x, w, mask, g, (v1, h1, v2), dtype=torch.float32))
     gates = pc.gate(r32, r64)
     sh = pc.shares(grads, r64, gates)
-    _report(test="pg_module", config=config, case=_id(case), mode="eval", launches=launches, v1=c1.worst, h1=c2.worst, v2=c3.worst, pred=c4.worst, shares=sh)
+    report(test="pg_module", config=config, case=_id(case), mode="eval", launches=launches, v1=c1.worst, h1=c2.worst, v2=c3.worst, pred=c4.worst, shares=sh)
     assert max(sh.values()) <= 1.0, sh
     # ---- train with keep-masks at p = dropout, NaN in g behind the mask
     rs = np.random.RandomState(B * S + 3)
@@ -259,7 +252,7 @@ def test_module_forward_and_backward(config, case):
     r64 = _flat(pc.closed_form(x, w, mask, g0, (v1, h1, v2), keeps, m.dropout, torch.float64))
     r32 = _flat(pc.closed_form(x, w, mask, g0, (v1, h1, v2), keeps, m.dropout, torch.float32))
     sh = pc.shares(grads, r64, pc.gate(r32, r64))
-    _report(test="pg_module", config=config, case=_id(case), mode="train_nan_behind_mask", launches=launches, shares=sh)
+    report(test="pg_module", config=config, case=_id(case), mode="train_nan_behind_mask", launches=launches, shares=sh)
     assert max(sh.values()) <= 1.0, sh
     # the dropped h1 is the kept fp32 LayerNorm rows times 1 / (1 - p): zero exactly where the mask drops
     assert not h1[torch.from_numpy(~keeps[0])].any()
@@ -295,7 +288,7 @@ def test_needs_input_grad_and_run_to_run_bits():
         with torch.no_grad():
             quiet = m(dev(x.numpy()), dev(mask))
         assert quiet.cpu().numpy().tobytes() == a[0] and not quiet.requires_grad
-        _report(test="pg_launches", forward=a[3]["forward"], backward=a[3]["backward"], backward_no_dx=nx[3]["backward"], backward_frozen_w1=fz[3]["backward"])
+        report(test="pg_launches", forward=a[3]["forward"], backward=a[3]["backward"], backward_no_dx=nx[3]["backward"], backward_frozen_w1=fz[3]["backward"])
     finally:
         for p in params:
             p.requires_grad_(True)
@@ -337,5 +330,5 @@ def test_one_native_training_step():
     for k, a, t32, w64 in zip(pc.NAMES[:10], got, chain["f32"], chain["f64"]):
         err = np.abs(a.astype(np.float64) - w64).max()
         sh[k] = float(err / oc.gate_of(t32, w64)) if np.isfinite(err) else float("inf")
-    _report(test="pg_native_step", shares=sh)
+    report(test="pg_native_step", shares=sh)
     assert max(sh.values()) <= 1.0, sh

@@ -18,7 +18,8 @@ import torch
 import tests.test_fp32_ops_host as T
 import tests.test_predictor_ops_host as P
 from tests import bf16_emu as E
-from tests.test_gpu_fp32_ops import _form_str, _report
+from tests.test_gpu_fp32_ops import _form_str
+from tests.util import report as _report
 from tests.util import weights_for
 
 pytestmark = pytest.mark.gpu

@@ -13,19 +13,14 @@
 """
 import types
 
-import numpy as np
 import pytest
 import torch
 
-from tests.util import load_golden, weights_for
+from tests.util import dev, load_golden, weights_for
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ["mel", "postnet_mel", "p_pred", "e_pred", "log_d", "d_rounded", "src_masks", "mel_masks", "src_lens", "mel_lens"]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def build(cfg, sd, **extra):

@@ -12,7 +12,7 @@ from smart_nar_fast_tts_amd import _lib, ops
 from smart_nar_fast_tts_amd.model import FastSpeech2Align
 from tests import aligner_cpu as ac
 from tests import teacher_cpu as tc
-from tests.util import load_golden
+from tests.util import dev, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +23,6 @@ FLOOR = {"log_d": 4e-7, "pitch_rel": 2e-6, "energy_rel": 2e-6, "mel": 1e-6, "pos
 _BASE = {}
 _MODELS = {}
 _OUT = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def weights(meta):

@@ -18,21 +18,14 @@ import smart_nar_fast_tts_amd.workload as wl
 from tests import lossgrad_cpu as lg
 from tests import optim_cpu as oc
 from tests import variance_adaptor_grad_cpu as vc
-from tests.test_gpu_fp32_ops import _report
-from tests.util import load_golden
+from tests.util import dev, load_golden, native_lib, report
 
 pytestmark = pytest.mark.gpu
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 @pytest.fixture(scope="module")
 def so():
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return native_lib()
 
 
 def _poison(shape, dtype):
@@ -141,7 +134,7 @@ def test_embedding_alone(so, M, D, n_bins, kind):
     empty = np.setdiff1d(np.arange(n_bins), k)
     assert (kind, len(empty)) != ("one_bin", 0) and (M >= n_bins or len(empty) > 0)
     assert not got[empty].any() and not np.signbit(got[empty]).any()  # a bin no row hits: +0.0
-    _report(test="va_embedding_alone", M=M, D=D, n_bins=n_bins, kind=kind, y=s_y, d_table=s_t)
+    report(test="va_embedding_alone", M=M, D=D, n_bins=n_bins, kind=kind, y=s_y, d_table=s_t)
     assert s_y <= 1.0 and s_t <= 1.0, (s_y, s_t)
     assert _bits(_embed_bwd(lib, dev(g), idx, n_bins)) == _bits(dt)  # run to run, bit for bit
 
@@ -231,7 +224,7 @@ def test_length_regulator_alone(so, name):
     s = _share(got_dx, want_dx, absum)
     zero = np.maximum(d, 0) == 0
     assert not got_dx[zero].any() and not np.signbit(got_dx[zero]).any()  # duration 0: exactly +0.0
-    _report(test="va_length_regulator_alone", case=name, d_x=s)
+    report(test="va_length_regulator_alone", case=name, d_x=s)
     assert s <= 1.0, s
     assert _bits(_lr_bwd(lib, dev(g), cum, L)) == _bits(dx)
     # NaN at every frame at or past an utterance's total never reaches d_x
@@ -329,7 +322,7 @@ def test_module_forward_and_backward(so, name, mix):
     assert np.array_equal(d_r.cpu().numpy(), inp["duration"]) and mm.dtype == torch.bool  # duration_target itself; mel_mask passed through
     sh = vc.shares(got, r64, gates)
     assert set(sh) == set(vc.NAMES)
-    _report(test="va_module", case=name, mix=mix, launches=list(launches), shares=vc.classes(sh))
+    report(test="va_module", case=name, mix=mix, launches=list(launches), shares=vc.classes(sh))
     assert max(sh.values()) <= 1.0, sh
     if name == "tiny":  # the reference's own recorded results, under the gate built from them
         ref64 = {k: z[f"{mix}_{k}_f64"] for k in vc.FIXTURE_NAMES}
@@ -381,7 +374,7 @@ def test_needs_input_grad_drops_launches_and_returns_none(so):
     got, _, (f3, b3), _ = _run(m, inp, x_grad=False)
     assert got["dx"] is None and b3 < b_all
     assert all(got[k].tobytes() == full[k].tobytes() for k in vc.NAMES if k != "dx")
-    _report(test="va_launches", mix="pf", forward=f_all, backward=b_all, frozen_table_backward=b1, frozen_predictor_backward=b2, no_dx_backward=b3)
+    report(test="va_launches", mix="pf", forward=f_all, backward=b_all, frozen_table_backward=b1, frozen_predictor_backward=b2, no_dx_backward=b3)
 
 
 def test_one_native_training_step_from_the_loss_through_the_adaptor(so):
@@ -449,5 +442,5 @@ def test_one_native_training_step_from_the_loss_through_the_adaptor(so):
         sh[k] = float((err / bound).max()) if np.isfinite(err).all() else float("inf")
     sh["x_grad"] =vc.shares({"dx": x.grad.cpu().numpy()}, gr["f64"], g_gate, ["dx"])["dx"]
     assert all(np.abs(a - before[vc.grad_key(k)]).max() > 0 for k, a in zip(names, got))  # every parameter moved
-    _report(test="va_native_step", mix=mix, shares=vc.classes(sh))
+    report(test="va_native_step", mix=mix, shares=vc.classes(sh))
     assert max(sh.values()) <= 1.0, sh

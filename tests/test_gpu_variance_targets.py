@@ -9,16 +9,12 @@ import pytest
 import torch
 
 from tests import variance_targets_cpu as vc
-from tests.util import load_golden
+from tests.util import dev, load_golden
 
 pytestmark = pytest.mark.gpu
 
 FIXTURES = ("variance_targets_tiny", "variance_targets_edges")
 _CPU = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def fixture(name):

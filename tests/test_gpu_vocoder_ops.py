@@ -9,13 +9,11 @@ Asserted in every case: the gate at every element; the copy of utterance 0 in th
 tile-position-dependent error shows there below any tolerance); everything finite.  Reported in every case: the worst ratio to the
 bound, and the same figure for torch's fp32 evaluation on the CPU (not gated here).  NS_VOC_OPS_REPORT=<path> appends every figure
 to a JSON-lines file, from which profiles/vocoder_ops_r12.md is written."""
-import json
-import os
-
 import pytest
 import torch
 
 from tests import vocoder_ops as V
+from tests.util import reporter
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore::FutureWarning")]
 
@@ -33,12 +31,7 @@ def gen(mode):
     return _GENS[mode]
 
 
-def _report(**row):
-    print(json.dumps(row))
-    path = os.environ.get("NS_VOC_OPS_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(row) + "\n")
+_report = reporter("NS_VOC_OPS_REPORT")
 
 
 def _judge(c, got, x, resid, acc):

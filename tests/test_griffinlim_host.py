@@ -16,6 +16,7 @@ if HERE not in sys.path:
 import griffinlim_cpu as gc  # noqa: E402
 import melfront_cpu as mc  # noqa: E402
 from smart_nar_fast_tts_amd import audio as A  # noqa: E402
+from tests.util import built_lib  # noqa: E402
 
 CONFIGS = {"tiny": gc.TINY, "ljspeech": gc.LJSPEECH}
 
@@ -43,12 +44,7 @@ def refs(golden):
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))

@@ -4,8 +4,6 @@ C ABI's host side (versions, size function, every refusal) and the kernels' regi
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,7 +11,7 @@ import torch
 
 from smart_nar_fast_tts_amd import _lib
 from tests import loss_cpu as lc
-from tests.util import load_golden
+from tests.util import assert_no_spill, load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = (("loss_tiny", "teacher_tiny"), ("loss_tiny_phoneme_level", "teacher_tiny_phoneme_level"))
@@ -196,8 +194,4 @@ def test_python_surface_without_a_gpu():
 def test_loss_kernels_do_not_spill():
     """Register hygiene of csrc/loss.hip: no VGPR / SGPR spill, no scratch (tools/kernel_resources.py cross-compiles for gfx950 and
     reads the code object's metadata; no GPU needed)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "loss.hip"), "--assert-no-spill"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_loss_partial", "k_loss_final"):
-        assert k in r.stdout, (k, r.stdout)
+    assert_no_spill("loss.hip", kernels=("k_loss_partial", "k_loss_final"))

@@ -5,8 +5,6 @@ the gate proven both ways (the fp32 reference uses at most half of it, every mut
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,7 +14,7 @@ from smart_nar_fast_tts_amd import _lib
 from smart_nar_fast_tts_amd.loss import GRAD_NAMES, FastSpeech2TrainingLoss
 from tests import loss_cpu as lc
 from tests import lossgrad_cpu as lg
-from tests.util import load_golden
+from tests.util import assert_no_spill, load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = (("lossgrad_tiny", "teacher_tiny"), ("lossgrad_tiny_phoneme_level", "teacher_tiny_phoneme_level"))
@@ -261,10 +259,8 @@ def test_python_surface_without_a_gpu():
 def test_lossgrad_kernel_does_not_spill():
     """Register hygiene of csrc/lossgrad.hip: no VGPR / SGPR spill, no scratch, no LDS (tools/kernel_resources.py cross-compiles for
     gfx950 and reads the code object's metadata; no GPU needed)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "lossgrad.hip"), "--assert-no-spill"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    row = [ln for ln in r.stdout.splitlines() if "k_lossg_backward" in ln]
-    assert len(row) == 1, r.stdout
-    cols = dict(zip(r.stdout.splitlines()[0].split(), row[0].split()))
+    stdout = assert_no_spill("lossgrad.hip")
+    row = [ln for ln in stdout.splitlines() if "k_lossg_backward" in ln]
+    assert len(row) == 1, stdout
+    cols = dict(zip(stdout.splitlines()[0].split(), row[0].split()))
     assert cols["lds"] == "0" and cols["scratch"] == "0", row

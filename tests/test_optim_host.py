@@ -5,8 +5,6 @@ register hygiene."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,7 +12,7 @@ import torch
 
 from smart_nar_fast_tts_amd import _lib
 from tests import optim_cpu as oc
-from tests.util import load_golden
+from tests.util import assert_no_spill, load_golden, run_c_caller
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "nar_fs2.h")
@@ -328,15 +326,7 @@ def test_every_refusal_is_reached_without_a_gpu():
 
 
 def test_header_is_plain_c_and_validation_works_from_c(tmp_path):
-    exe = tmp_path / "opt_host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "opt_host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), _lib.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    run_c_caller("opt_host_only", _lib.LIB_PATH, tmp_path)
 
 
 # ---- the Python surface ---------------------------------------------------------------------------------------------------------------
@@ -379,8 +369,4 @@ def test_python_refusals_without_a_gpu():
 
 
 def test_optim_kernels_do_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "optim.hip"), "--assert-no-spill"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_opt_sumsq", "k_opt_norm_final", "k_opt_scale", "k_opt_adam", "k_opt_zero"):
-        assert k in r.stdout, (k, r.stdout)
+    assert_no_spill("optim.hip", kernels=("k_opt_sumsq", "k_opt_norm_final", "k_opt_scale", "k_opt_adam", "k_opt_zero"))

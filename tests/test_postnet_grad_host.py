@@ -7,27 +7,20 @@ is inside the gate; the written-out forward and backward agree with the float64 
 1e-10 is taken relative to the other gradients' scale, as tests/test_cross_attention_grad_host.py does for d_bk.)"""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from tests import postnet_grad_cpu as pc
-from tests.util import load_golden
+from tests.util import assert_no_spill, built_lib, load_golden, run_c_caller
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()
 
 
 _FIX = {}
@@ -263,24 +256,11 @@ def test_the_single_kernel_entries_refuse_before_any_hip_call(lib):
 
 
 def test_header_is_plain_c_and_validation_works_from_c(lib, tmp_path):
-    L_, so = lib
-    exe = tmp_path / "pn_host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "pn_host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), L_.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    run_c_caller("pn_host_only", lib[0].LIB_PATH, tmp_path)
 
 
 def test_the_new_kernels_do_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "postnetgrad.hip"),
-                        "--assert-no-spill"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_pn_stats", "k_pn_finish", "k_pn_apply", "k_pn_bwd_reduce", "k_pn_bwd_apply", "k_pn_bias_finish", "k_pn_copy"):
-        assert k in r.stdout, r.stdout
+    assert_no_spill("postnetgrad.hip", kernels=("k_pn_stats", "k_pn_finish", "k_pn_apply", "k_pn_bwd_reduce", "k_pn_bwd_apply", "k_pn_bias_finish", "k_pn_copy"))
 
 
 # ---------------------------------------------------------------------------------------------------- the Python surface

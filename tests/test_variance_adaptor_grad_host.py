@@ -7,27 +7,20 @@ and its fp32 run is inside the gate; the written-out forward and backward agree 
 outside the gate of some tensor of some mix."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from tests import variance_adaptor_grad_cpu as vc
-from tests.util import load_golden
+from tests.util import assert_no_spill, built_lib, load_golden, run_c_caller
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-
-    ge.build()
-    import smart_nar_fast_tts_amd._lib as L
-
-    return L, L.load()
+    return built_lib()
 
 
 _FIX = {}
@@ -195,24 +188,11 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
 
 
 def test_header_is_plain_c_and_validation_works_from_c(lib, tmp_path):
-    L_, so = lib
-    exe = tmp_path / "va_host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "va_host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), L_.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    run_c_caller("va_host_only", lib[0].LIB_PATH, tmp_path)
 
 
 def test_the_new_kernels_do_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "adaptorgrad.hip"),
-                        "--assert-no-spill"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_va_embed_fwd", "k_va_embed_bwd", "k_va_embed_finish", "k_va_duration_scan", "k_va_lr_bwd"):
-        assert k in r.stdout, r.stdout
+    assert_no_spill("adaptorgrad.hip", kernels=("k_va_embed_fwd", "k_va_embed_bwd", "k_va_embed_finish", "k_va_duration_scan", "k_va_lr_bwd"))
 
 
 # ---------------------------------------------------------------------------------------------------- the Python surface

@@ -6,8 +6,6 @@ import ctypes as C
 import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,7 +13,7 @@ import torch
 
 from smart_nar_fast_tts_amd import _lib
 from tests import variance_targets_cpu as vc
-from tests.util import load_golden
+from tests.util import assert_no_spill, load_golden, run_c_caller
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = ("variance_targets_tiny", "variance_targets_edges")
@@ -254,15 +252,7 @@ def test_every_refusal_is_reached_without_a_gpu():
 
 
 def test_header_is_plain_c_and_validation_works_from_c(tmp_path):
-    exe = tmp_path / "vt_host_only"
-    src = os.path.join(ROOT, "tests", "cabi", "vt_host_only.c")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", str(exe), "-ldl"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = "/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    r = subprocess.run([str(exe), _lib.LIB_PATH], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "C caller ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    run_c_caller("vt_host_only", _lib.LIB_PATH, tmp_path)
 
 
 def test_python_surface_without_a_gpu(tmp_path):
@@ -313,8 +303,4 @@ def test_python_surface_without_a_gpu(tmp_path):
 
 
 def test_vartargets_kernels_do_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "vartargets.hip"), "--assert-no-spill"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    for k in ("k_vt_targets", "k_vt_fit_partial", "k_vt_fit_merge", "k_vt_normalize", "k_vt_minmax_merge", "k_vt_state_init"):
-        assert k in r.stdout, (k, r.stdout)
+    assert_no_spill("vartargets.hip", kernels=("k_vt_targets", "k_vt_fit_partial", "k_vt_fit_merge", "k_vt_normalize", "k_vt_minmax_merge", "k_vt_state_init"))

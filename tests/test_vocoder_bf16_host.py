@@ -2,7 +2,6 @@
 construction without a device, mode validation, the arena growth by the documented bf16-plane formula, the unchanged workspace,
 and the register gate of csrc/vocoder_bf16.hip.  The GPU side is tests/test_gpu_vocoder_bf16.py."""
 import os
-import subprocess
 import sys
 
 import pytest
@@ -12,6 +11,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import smart_nar_fast_tts_amd.workload as wl  # noqa: E402
+from tests.util import assert_no_spill  # noqa: E402
 
 pytestmark = pytest.mark.filterwarnings("ignore::FutureWarning")
 
@@ -78,8 +78,5 @@ def test_arena_grows_by_the_bf16_planes_and_ws_is_unchanged(V, h, name):
 
 
 def test_vocoder_bf16_kernels_do_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "vocoder_bf16.hip"), "--assert-no-spill"],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    assert r.stdout.count("k_voc_gemm_bf16<") == 4, r.stdout
+    stdout = assert_no_spill("vocoder_bf16.hip")
+    assert stdout.count("k_voc_gemm_bf16<") == 4, stdout

@@ -4,7 +4,6 @@ register gate of csrc/vocoder.hip.  The GPU side is tests/test_gpu_vocoder.py.""
 import copy
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -17,6 +16,7 @@ if ROOT not in sys.path:
 
 import smart_nar_fast_tts_amd.workload as wl  # noqa: E402
 from tests import hifigan_cpu  # noqa: E402
+from tests.util import assert_no_spill  # noqa: E402
 
 pytestmark = pytest.mark.filterwarnings("ignore::FutureWarning")
 
@@ -162,8 +162,5 @@ def test_get_vocoder_rejects_melgan(V):
 
 
 def test_vocoder_kernels_do_not_spill():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
-                        os.path.join(ROOT, "smart-nar_fast_tts_amd", "csrc", "vocoder.hip"), "--assert-no-spill"],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    assert r.stdout.count("k_voc_gemm<") == 3 and "k_voc_post" in r.stdout and "k_voc_transpose" in r.stdout, r.stdout
+    stdout = assert_no_spill("vocoder.hip", kernels=("k_voc_post", "k_voc_transpose"))
+    assert stdout.count("k_voc_gemm<") == 3, stdout

@@ -18,7 +18,7 @@ g_out [B, T, d], g_pitch / g_energy (at the mix's level), g_log_d [B, L]."""
 import numpy as np
 import torch
 
-from tests import lossgrad_cpu as lg
+from tests import util
 from tests import predictor_grad_cpu as pg
 
 PRED = ("dur", "pitch", "energy")
@@ -197,18 +197,10 @@ def evaluate(inp, w, mix, dtype=torch.float64, mutate=None):
 
 def gate(ref32, ref64, names=None):
     """The absolute gates {name: value}: twice the reference's own fp32 error plus one fp32 ulp of the largest magnitude."""
-    out = {}
-    for k in (names or [k for k in ref64 if k in ref32 and k != "mel_len"]):
-        a, b = np.asarray(ref32[k], dtype=np.float64), np.asarray(ref64[k], dtype=np.float64)
-        out[k] = 2.0 * float(np.max(np.abs(a - b), initial=0.0)) + lg.ulp32(np.max(np.abs(b), initial=0.0))
-    return out
+    return util.gates(ref32, ref64, names or [k for k in ref64 if k in ref32 and k != "mel_len"])
 
 
-def shares(got, ref64, gates, names=None):
-    """{name: max |got - ref64| / gate}; inf for a NaN / Inf in got.  A missing (None) tensor is skipped."""
-    names = [k for k in (names or gates) if got.get(k) is not None]
-    s, _ = lg.shares([np.asarray(got[k]).reshape(np.asarray(ref64[k]).shape) for k in names], [ref64[k] for k in names], [gates[k] for k in names])
-    return dict(zip(names, (float(v) for v in s)))
+shares = util.shares  # {name: max |got - ref64| / gate}
 
 
 def classes(sh):

@@ -350,7 +350,7 @@ def poison(batch, frame_lens):
 
 # ---- gates (all derived) ----------------------------------------------------------------------------------------------------------------
 def ulp32(y64):
-    """The spacing of fp32 at |y64| (2^-149 at 0)."""
+    """The spacing of fp32 at |y64| (2^-149 at 0), per element of an array: not tests/util.py's ulp32, which takes one scalar."""
     a = np.abs(np.asarray(y64, dtype=np.float64)).astype(np.float32)
     return (np.nextafter(a, np.float32(np.inf)).astype(np.float64) - a.astype(np.float64))
 

@@ -18,16 +18,11 @@ reports none).  --report adds the accuracy shares tests/test_gpu_ffn_grad.py app
 """
 import argparse
 import json
-import os
-import sys
-import time
-import warnings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from _bench import Candidate, alternate, candidate_table, common_args, emit, host_reads
 
 PEAK = 157.3e12  # fp32 MFMA flop/s (MI355X_MICROARCH.md)
 SHAPES = {"cfg2_encoder": dict(B=16, S=128), "cfg2_decoder": dict(B=16, S=1000)}  # BASELINE config 2: phoneme level, frame level
@@ -47,31 +42,6 @@ class TorchFFN(torch.nn.Module):
     def forward(self, x):
         out = self.w_2(torch.nn.functional.relu(self.w_1(x.transpose(1, 2)))).transpose(1, 2)
         return self.layer_norm(out + x)
-
-
-def stats(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts))}
-
-
-class Candidate:
-    def __init__(self, name, step, leaves=()):
-        self.name, self.step, self.leaves = name, step, leaves
-        self.events, self.wall = [], []
-
-    def timed(self, record):
-        for x in self.leaves:
-            x.grad = None
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        a.record()
-        self.step()
-        b.record()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        if record:
-            self.events.append(a.elapsed_time(b))
-            self.wall.append((t1 - t0) * 1e3)
 
 
 def against_float64(ours, x, g, grads, h):
@@ -111,14 +81,9 @@ def bench(shape, steps, warmup):
 
     step_a()
     torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("warn")
-    with warnings.catch_warnings(record=True) as seen:
-        warnings.simplefilter("always")
-        step_a()
-    torch.cuda.set_sync_debug_mode("default")
+    n_reads, messages = host_reads(step_a)
     launches = dict(ours.last_launches)
-    host_reads = len([w for w in seen if "synchroniz" in str(w.message).lower()])
-    assert host_reads == 0, [str(w.message) for w in seen]
+    assert n_reads == 0, messages
 
     lib = L.load()
     call = ours._marshal(xa.detach(), None)
@@ -153,9 +118,7 @@ def bench(shape, steps, warmup):
              Candidate("(c) the backward without dx", backward(("dx",))),
              Candidate("(d) da = conv(du, w2^T) alone (pack + GEMM)", step_da),
              Candidate("(d) the ReLU gate alone, with d_b1 (two launches)", step_gate)]
-    for i in range(warmup + steps):
-        for c in cands:
-            c.timed(i >= warmup)
+    alternate(cands, steps, warmup)
     diff = float((xa.grad - xb.grad).abs().max())
     med = [float(np.median(c.events)) for c in cands]
     flop = {"dW1": 2.0 * M * D_INNER * KS[0] * D, "dW2": 2.0 * M * D * KS[1] * D_INNER, "da": 2.0 * M * D_INNER * KS[1] * D, "dx": 2.0 * M * D * KS[0] * D_INNER}
@@ -163,9 +126,9 @@ def bench(shape, steps, warmup):
     gemms = {k: {"flop": flop[k], "ms": ms[k], "floor_us": flop[k] / PEAK * 1e6, "share_of_peak": (flop[k] / (ms[k] * 1e-3) / PEAK) if ms[k] > 0 else None}
              for k in ("dW1", "dW2", "da", "dx")}
     gate_bytes = 3.0 * M * D_INNER * 4
-    res = {"shape": shape, "B": B, "S": S, "M": M, "d": D, "d_inner": D_INNER, "kernel": list(KS), "launches": launches, "host_reads": host_reads,
+    res = {"shape": shape, "B": B, "S": S, "M": M, "d": D, "d_inner": D_INNER, "kernel": list(KS), "launches": launches, "host_reads": n_reads,
            "max_abs_dx_diff_a_vs_b": diff, "rel_err_vs_float64_same_gate": rel64, "gemms": gemms, "gate_ms": med[7], "gate_bytes": gate_bytes, "gate_GBps": gate_bytes / (med[7] * 1e-3) / 1e9,
-           "candidates": [{"name": c.name, "events": stats(c.events), "wall": stats(c.wall)} for c in cands]}
+           "candidates": [c.result() for c in cands]}
     res["a_over_b_events"] = med[0] / med[1]
     return res
 
@@ -196,10 +159,7 @@ def accuracy_lines(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES))
-    ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--md")
-    ap.add_argument("--json")
+    common_args(ap, steps=30, warmup=5)
     ap.add_argument("--report", help="an NS_FP32_OPS_REPORT file of tests/test_gpu_ffn_grad.py to summarise")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
@@ -210,11 +170,8 @@ def main():
              "ms; candidates alternate step by step in one process.  Nothing here is asserted.", ""]
     for r in results:
         print(json.dumps(r), flush=True)
-        lines += [f"## {r['shape']}: B = {r['B']}, S = {r['S']}, d = {r['d']}, d_inner = {r['d_inner']}, kernel sizes {tuple(r['kernel'])}", "",
-                  "| candidate | device events | wall clock |", "|---|---|---|"]
-        for c in r["candidates"]:
-            f = lambda k: f"{c[k]['median_ms']:.3f} ({c[k]['min_ms']:.3f} - {c[k]['max_ms']:.3f})"  # noqa: E731
-            lines.append(f"| {c['name']} | {f('events')} | {f('wall')} |")
+        lines += [f"## {r['shape']}: B = {r['B']}, S = {r['S']}, d = {r['d']}, d_inner = {r['d_inner']}, kernel sizes {tuple(r['kernel'])}", ""]
+        lines += candidate_table(r["candidates"])
         verdict = "faster than" if r["a_over_b_events"] < 1 else "SLOWER than"
         lines += ["", f"(a) is {verdict} (b): (a) / (b) = {r['a_over_b_events']:.3f} by device events.  (a) enqueued {r['launches'].get('forward')} launches forward and "
                   f"{r['launches'].get('backward')} backward and made {r['host_reads']} host reads (asserted).  max |dx (a) - dx (b)|: "
@@ -233,17 +190,7 @@ def main():
                   f"= {r['gate_GBps']:.0f} GB/s for the whole call (two launches, the host side inside).", ""]
     if args.report:
         lines += accuracy_lines(args.report)
-    text = "\n".join(lines) + "\n"
-    if args.md:
-        os.makedirs(os.path.dirname(os.path.abspath(args.md)), exist_ok=True)
-        with open(args.md, "w") as f:
-            f.write(text)
-    else:
-        print(text)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        with open(args.json, "w") as f:
-            json.dump(results, f, indent=1)
+    emit(args, lines, results)
 
 
 if __name__ == "__main__":

@@ -1295,6 +1295,38 @@ int ns_fg_backward(const ns_fg_shape* shape, const ns_fg_weights* weights, const
 int ns_fg_op_relu_gate(const float* da, const float* h, int M, int d_inner, float* dh, float* d_b1, void* ws, size_t ws_bytes,
                        void* stream);
 
+/* ==== TxtEncoder / MelDecoder: what the training stacks add to their FFT blocks (transformer/Models.py:33-100, 176-244) =============
+ * Handle-less, no workspace; nothing above changes (every other ABI version stays as it is).  Four single-launch ops: the two forward
+ * entries of the stacks (kernels the inference path already runs), the gradient of the word-embedding table, and the row mask of an
+ * FFT block (transformer/Layers.py:43,46).  No atomic, no host read; equal inputs give equal bits.
+ * Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a misaligned pointer (16 bytes
+ * for the float tensors, 8 for int64; the uint8 mask needs none), D not 256 or 512, n_vocab < 2, B * S * D (M * D) >= 2^31, a
+ * non-positive size, and, for the row mask, mask and lens both NULL or y == x.
+ * The stacks of stacks.py (python) launch, over L FFT blocks, each A(forward) = ns_ag_forward's and F(forward) = ns_fg_forward's count:
+ *   forward    1 (ns_st_op_embed_pos, or ns_st_op_add_pos) + sum over layers (A + 1 (row mask) + F + 1 (row mask)), + 1 when the
+ *              position table is regenerated (eval() past max_seq_len: ns_op_sinusoid_table)
+ *   backward   the mirror, sum over layers (1 + F(backward) + 1 + A(backward)), + 1 for the table gradient (ns_st_op_embed_grad),
+ *              which a frozen embedding drops; the position add has no backward launch (its gradient is grad_output itself). */
+#define NS_ST_ABI_VERSION 1 /* what ns_st_abi_version() returns */
+int ns_st_abi_version(void);
+/* Kernel launches the calling thread's last ns_st_* call enqueued. */
+int ns_st_last_launches(void);
+/* out [B, S, D] = emb[texts[b, s], :] + pos[s, :] (transformer/Models.py:83-91: src_word_emb(src_seq) + position_enc[:, :S]).  texts
+ * int64 [B, S]; emb [n_vocab, D]; pos [>= S, D].  A token outside [0, n_vocab) reads row 0 (PAD); nn.Embedding would raise, this has no
+ * host read to raise from.  One launch. */
+int ns_st_op_embed_pos(const int64_t* texts, const float* emb, const float* pos, int B, int S, int D, int n_vocab, float* out,
+                       void* stream);
+/* out [B, S, D] = x + pos[s, :] (transformer/Models.py:221-233: enc_seq + position table); pos [>= S, D].  One launch. */
+int ns_st_op_add_pos(const float* x, const float* pos, int B, int S, int D, float* out, void* stream);
+/* d_table [n_vocab, D] = the sum of g [M, D]'s rows per token id (the backward of nn.Embedding(n_vocab, D, padding_idx=0),
+ * transformer/Models.py:56-58), texts int64 [M]: float64 accumulation in ascending m, rounded once.  Row 0 (PAD) is +0.0 and g at a PAD
+ * row is never read; an id no row carries is +0.0; a token outside [0, n_vocab) contributes to no row.  One launch. */
+int ns_st_op_embed_grad(const float* g, const int64_t* texts, int M, int D, int n_vocab, float* d_table, void* stream);
+/* y [B, S, D] = padded(b, s) ? +0.0 : x (masked_fill(mask.unsqueeze(-1), 0), transformer/Layers.py:43,46; its backward is the same op
+ * on the gradient).  A select: x in a padded row is not read.  padded = mask[b, s] != 0 (uint8 [B, S]) when mask is given, else
+ * s >= lens[b] (int64 [B]); at least one of the two.  Out of place.  One launch. */
+int ns_st_op_row_mask(const float* x, const uint8_t* mask, const int64_t* lens, int B, int S, int D, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -378,6 +378,13 @@ SIGNATURES = {
     "ns_fg_forward": (_I, [C.POINTER(NsFgShape), C.POINTER(NsFgWeights), _P, _P, _F, _P, _P, _P, _Z, _P]),
     "ns_fg_backward": (_I, [C.POINTER(NsFgShape), C.POINTER(NsFgWeights), _P, _P, _F, _P, _P, C.POINTER(NsFgGrads), _P, _Z, _P]),
     "ns_fg_op_relu_gate": (_I, [_P, _P, _I, _I, _P, _P, _P, _Z, _P]),
+    # what the TxtEncoder / MelDecoder training stacks add to their FFT blocks (stacks.py; handle-less, no workspace)
+    "ns_st_abi_version": (_I, []),
+    "ns_st_last_launches": (_I, []),
+    "ns_st_op_embed_pos": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "ns_st_op_add_pos": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "ns_st_op_embed_grad": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "ns_st_op_row_mask": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -487,6 +487,13 @@ hipError_t launch_va_lr_bwd(const float* g, const int32_t* cum, int B, int L, in
 // dh [M, F] = h > 0 ? da : +0.0 (a select; dh may be da), F a multiple of 256; part (nullable) [pg_row_blocks(M)][PG_SLOTS][F] doubles,
 // uninitialised: slot 0 of a block = the column sums of its rows of dh, summed by launch_pg_col_final at this F.  One launch.
 hipError_t launch_fg_relu_gate(const float* da, const float* h, int M, int F, float* dh, double* part, hipStream_t st);
+// ---- TxtEncoder / MelDecoder training stacks (stackgrad.hip; transformer/Models.py:33-100, 176-244) ---------
+// d_table [n_vocab, D] = the sum of g [M, D]'s rows per token id, float64 in ascending m, rounded once; row 0 (PAD) and an id no row
+// carries are +0.0; a token outside [0, n_vocab) contributes nothing; g at a PAD row is not read.  D a multiple of 256.  One launch.
+hipError_t launch_st_embed_grad(const float* g, const long long* texts, int M, int D, int n_vocab, float* d_table, hipStream_t st);
+// y [M, D] = padded(m) ? +0.0 : x[m, :] (a select; out of place), padded(m) = mask[m] != 0, or m % S >= lens[m / S] without a mask.
+// D a multiple of 256.  One launch.
+hipError_t launch_st_row_mask(const float* x, const uint8_t* mask, const long long* lens, int M, int S, int D, float* y, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

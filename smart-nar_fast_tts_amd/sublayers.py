@@ -18,7 +18,8 @@ attention loss reads the cross-attention maps of ``FFTBlock2.crs_attn``, which `
 ``k is v`` = phonemes, the [B, H, T, L] map returned and its gradient accepted.
 
 ``PositionwiseFeedForward`` (transformer/SubLayers.py:62-95; csrc/ffngrad.hip, ``ns_fg_*``) is the other sublayer of an FFT block, and
-``FFTBlock`` (transformer/Layers.py:39-48) the composite of ``slf_attn`` and ``pos_ffn`` in plain Python."""
+``FFTBlock`` (transformer/Layers.py:39-48) the composite of ``slf_attn``, ``pos_ffn`` and the row mask (``stacks.mask_rows``) in plain
+Python."""
 from __future__ import annotations
 
 import ctypes as C
@@ -319,8 +320,9 @@ class FFTBlock(torch.nn.Module):
     """The reference's ``FFTBlock(d_model, n_head, d_k, d_v, d_inner, kernel_size, dropout=0.1)`` (transformer/Layers.py:39-48) as a
     trainable module: ``slf_attn`` is ``MultiHeadAttention`` and ``pos_ffn`` is ``PositionwiseFeedForward``, both HIP in forward and
     backward, composed in plain Python, so ``encoder.layer_stack.N.*`` of a reference checkpoint loads strictly.  The two
-    ``masked_fill(mask.unsqueeze(-1), 0)`` between and after the sublayers stay torch kernels for now (with torch's own backward); there
-    is no C code of the block's own.
+    ``masked_fill(mask.unsqueeze(-1), 0)`` between and after the sublayers are ``stacks.mask_rows``: one HIP launch each in the forward
+    and one each in the backward (a select on the row's mask byte; ``mask_book`` counts them), so no torch kernel stands between
+    ``enc_input`` and ``enc_output``.
 
     ``forward(enc_input, mask=None, slf_attn_mask=None, lens=None, keep_masks=None) -> (enc_output, None)``: ``mask`` is the bool
     [B, S] padding mask (True = padded; those rows of the output are exactly 0), ``slf_attn_mask`` and ``lens`` follow
@@ -332,6 +334,9 @@ class FFTBlock(torch.nn.Module):
         super().__init__()
         self.slf_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
         self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, kernel_size, dropout=dropout)
+        from . import stacks  # (stacks imports this module: resolved here, at first use)
+
+        self._mask_rows, self.mask_book = stacks.mask_rows, stacks.Launches()
 
     def forward(self, enc_input, mask=None, slf_attn_mask=None, lens=None, keep_masks=None):
         if keep_masks is not None and len(keep_masks) != 2:
@@ -340,13 +345,15 @@ class FFTBlock(torch.nn.Module):
         if mask is not None:
             if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(enc_input.shape[:2]) or mask.device != enc_input.device:
                 raise ValueError(f"mask must be a bool [B, S] = {tuple(enc_input.shape[:2])} tensor on {enc_input.device}")
-            pad = (mask != 0).unsqueeze(-1)
+            pad = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+            pad = pad.contiguous().view(torch.uint8)  # (a bool's bytes are 0 and 1: no kernel)
         else:
             pad = None
+        self.mask_book.begin()
         enc_output, _ = self.slf_attn(enc_input, enc_input, enc_input, mask=slf_attn_mask, lens=lens, keep_mask=k_attn)
         if pad is not None:
-            enc_output = enc_output.masked_fill(pad, 0)
+            enc_output = self._mask_rows(enc_output, mask=pad, book=self.mask_book)
         enc_output = self.pos_ffn(enc_output, keep_mask=k_ffn)
         if pad is not None:
-            enc_output = enc_output.masked_fill(pad, 0)
+            enc_output = self._mask_rows(enc_output, mask=pad, book=self.mask_book)
         return enc_output, None

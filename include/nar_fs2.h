@@ -1327,6 +1327,70 @@ int ns_st_op_embed_grad(const float* g, const int64_t* texts, int M, int D, int 
  * s >= lens[b] (int64 [B]); at least one of the two.  Out of place.  One launch. */
 int ns_st_op_row_mask(const float* x, const uint8_t* mask, const int64_t* lens, int B, int S, int D, float* y, void* stream);
 
+/* ==== MelEncoder: the Prenet and the position add behind it, a training forward and its backward ===================================
+ * (transformer/Models.py:145-146,151,162; transformer/Layers.py:11-26).  Handle-less; nothing above changes (every other ABI version
+ * stays as it is).  With mels [B, T, n_mel], M = B * T rows:
+ *   xin = mels with frame 0 of every utterance replaced by +0.0 (Models.py:145-146)     [M, n_mel]
+ *   h1 = relu(xin w1^T + b1);  h2 = relu(h1 w2^T + b2)  (Layers.py:23)                   [M, d] each
+ *   y  = h2 keep / (1 - p_drop) + pos[t, :]             (Layers.py:24, Models.py:151,162)
+ * The weights are LIVE device tensors in checkpoint (torch nn.Linear) layout; dropout is a uint8 keep-mask [M, d] (nonzero = kept) and
+ * p_drop.  Exact fp32 on the fp32 matrix cores; y and the column sums in float64, rounded once.  No atomic, no host read; equal inputs
+ * give equal bits.  Both ReLU backwards gate on the SAVED activations (a select), so the gradients are those of the forward that ran.
+ * The stack of FFTBlock2 behind it (Layers.py:51-70) is composed in python from ns_xg_*, ns_fg_* and ns_st_op_row_mask. */
+#define NS_ME_ABI_VERSION 1 /* what ns_me_abi_version() returns */
+int ns_me_abi_version(void);
+typedef struct ns_me_shape { int32_t B, T, n_mel, d; } ns_me_shape;
+/* Device pointers, 16-byte aligned, fp32, checkpoint layout. */
+typedef struct ns_me_weights {
+  const float* w1; /* [d, n_mel] prenet.w_1.weight (Layers.py:18) */
+  const float* b1; /* [d] */
+  const float* w2; /* [d, d] prenet.w_2.weight (Layers.py:19) */
+  const float* b2; /* [d] */
+} ns_me_weights;
+/* The outputs of ns_me_backward: dmels [B, T, n_mel] and the four parameter gradients, shaped as the weights.  16-byte aligned.  NULL =
+ * not wanted: neither computed nor written, and a launch none of whose outputs is wanted is not made. */
+typedef struct ns_me_grads {
+  float *dmels, *w1, *b1, *w2, *b2;
+} ns_me_grads;
+/* Bytes of the workspace of ns_me_forward / ns_me_backward of this shape (0 and ns_last_error() for a refused shape), and of `saved`:
+ * xin [M, n_mel] | h1 [M, d] | h2 [M, d] floats, in this order, dense. */
+size_t ns_me_ws_bytes(const ns_me_shape* shape);
+size_t ns_me_saved_bytes(const ns_me_shape* shape);
+/* Kernel launches the calling thread's last ns_me_* call enqueued. */
+int ns_me_last_launches(void);
+/* Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a pointer that is not 16-byte
+ * aligned, d not 256 or 512, n_mel not a positive multiple of 4, B or T not positive, B * T * max(d, n_mel) >= 2^31, a shape the Conv1D-as-GEMM
+ * dispatch or the weight gradient's plan (ns_pg_plan_wgrad) refuses (the dispatch takes Cin only as a multiple of 16, so in effect n_mel
+ * must be one: 4, 20 or 84 are refused with its message), p_drop outside [0, 1), a keep-mask without p_drop > 0 or
+ * p_drop > 0 without one, a workspace smaller than ns_me_ws_bytes.
+ * mels is never written.  pos [>= T, d] (the position table of the call).  y [B, T, d].  saved: ns_me_saved_bytes, or NULL (nothing
+ * kept: the no_grad forward; the same launches, the same y).
+ * Launches: 1 (pack of w1 and w2) + 1 (frame-0 select) + G(M, d, n_mel) (h1, bias and ReLU in its epilogue) + G(M, d, d) (h2, the same)
+ * + 1 (dropout + position add), where G(M, N, Cin) is the Conv1D-as-GEMM dispatch's own launch count for that shape
+ * (ns_plan_gemm_launches(M, N, Cin, 1, 0), 1 or 2). */
+int ns_me_forward(const ns_me_shape* shape, const ns_me_weights* weights, const float* mels, const float* pos, const uint8_t* keep,
+                  float p_drop, float* y, void* saved, void* ws, size_t ws_bytes, void* stream);
+/* The gradient of sum g[m, :] . y[m, :] (g [B, T, d], read only, on every row) with respect to every non-NULL member of grads, from
+ * `saved` as ns_me_forward wrote it for the same arguments.  Frame 0 of dmels is +0.0 (the forward replaced that frame).
+ * Launches with every output wanted: 1 (dropout + ReLU gate, with the partials of d_b2) + 1 (d_b2: column finish) + 2 (dW2: GEMM,
+ * reduce) + 1 (pack of the transposed w2 and w1, one launch for both) + G(M, d, d) (da1) + 1 (ReLU gate, with the partials of d_b1) + 1
+ * (d_b1: column finish) + 2 (dW1) + G(M, n_mel, d) (the data gradient) + 1 (frame-0 select into dmels) = 10 + G(M, d, d) +
+ * G(M, n_mel, d).  An unwanted weight gradient drops its 2 launches, b1 and b2 their column finish, dmels its GEMM and its select;
+ * with none of w1, b1 and dmels wanted the pack, da1 and the second gate are dropped too: the first gate, d_b2's finish and dW2's two
+ * remain.  With no output wanted nothing is launched. */
+int ns_me_backward(const ns_me_shape* shape, const ns_me_weights* weights, const uint8_t* keep, float p_drop, const void* saved,
+                   const float* g, const ns_me_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* The two new kernels alone.  d 256 or 512, B * T * d (M * d) < 2^31, p_drop and keep as above.
+ * y [B, T, d] = h2 k + pos[t, :] in float64, rounded once, k = 1 / (1 - p_drop) where keep [B, T, d] is nonzero and 0 where it is zero
+ * (keep NULL at p_drop == 0: y = h2 + pos).  Out of place.  One launch. */
+int ns_me_op_drop_pos(const float* h2, const float* pos, const uint8_t* keep, float p_drop, int B, int T, int d, float* y, void* stream);
+/* dh [M, d] = (keep != 0 && h2 > 0) ? g / (1 - p_drop) : +0.0 (a select: what g holds behind a dropped or gated element reaches
+ * nothing, a NaN in h2 gates like a zero; dh is not g, which is only read) and, unless d_b2 is NULL, d_b2 [d] = the column sums of dh:
+ * float64 partials per 64 rows, added in ascending order, rounded once.  ws (needed with d_b2 only): ceil(M / 64) * 5 * d doubles.
+ * One launch, two with d_b2. */
+int ns_me_op_drop_relu_gate(const float* g, const float* h2, const uint8_t* keep, float p_drop, int M, int d, float* dh, float* d_b2,
+                            void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

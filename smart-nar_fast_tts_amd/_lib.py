@@ -159,6 +159,24 @@ class NsFgGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in FG_NAMES + ("dx",)]
 
 
+class NsMeShape(C.Structure):
+    """``ns_me_shape`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "n_mel", "d")]
+
+
+ME_NAMES = ("w1", "b1", "w2", "b2")
+
+
+class NsMeWeights(C.Structure):
+    """``ns_me_weights`` (include/nar_fs2.h): the Prenet's four parameters in checkpoint layout."""
+    _fields_ = [(n, C.c_void_p) for n in ME_NAMES]
+
+
+class NsMeGrads(C.Structure):
+    """``ns_me_grads`` (include/nar_fs2.h): ``dmels`` and the four parameter gradients, each nullable."""
+    _fields_ = [(n, C.c_void_p) for n in ("dmels",) + ME_NAMES]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -385,6 +403,15 @@ SIGNATURES = {
     "ns_st_op_add_pos": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "ns_st_op_embed_grad": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "ns_st_op_row_mask": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    # MelEncoder: the Prenet and the position add, training forward and backward (sublayers.Prenet; handle-less)
+    "ns_me_abi_version": (_I, []),
+    "ns_me_ws_bytes": (_Z, [C.POINTER(NsMeShape)]),
+    "ns_me_saved_bytes": (_Z, [C.POINTER(NsMeShape)]),
+    "ns_me_last_launches": (_I, []),
+    "ns_me_forward": (_I, [C.POINTER(NsMeShape), C.POINTER(NsMeWeights), _P, _P, _P, _F, _P, _P, _P, _Z, _P]),
+    "ns_me_backward": (_I, [C.POINTER(NsMeShape), C.POINTER(NsMeWeights), _P, _F, _P, _P, C.POINTER(NsMeGrads), _P, _Z, _P]),
+    "ns_me_op_drop_pos": (_I, [_P, _P, _P, _F, _I, _I, _I, _P, _P]),
+    "ns_me_op_drop_relu_gate": (_I, [_P, _P, _P, _F, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -1,5 +1,5 @@
 """What the trainable HIP layers share on the Python side (predictor.VariancePredictor over ``ns_pg_*``, the two attentions of
-sublayers.py over ``ns_ag_*`` / ``ns_xg_*`` and its PositionwiseFeedForward over ``ns_fg_*``, postnet.PostNet over ``ns_pn_*``, the
+sublayers.py over ``ns_ag_*`` / ``ns_xg_*``, its PositionwiseFeedForward over ``ns_fg_*`` and its Prenet over ``ns_me_*``, postnet.PostNet over ``ns_pn_*``, the
 embedding and the length regulator of adaptor.py over ``ns_va_*``): the device guards, the launch bookkeeping (``CountedModule``), the workspace cache, the autograd Functions and the
 module base class that marshals the inputs, the parameters, the keep-masks and the gradient block.  A layer keeps its constructor
 checks, its ``PARAM_NAMES``, its shape struct, its mask handling and its two ctypes calls.  The cross-attention has two outputs, one of
@@ -56,8 +56,9 @@ class WorkspaceCache:
 class Call:
     """One marshalled call: the shape, the weight block and everything that must stay alive until the launches have run.  ``inputs``
     are the differentiable inputs in the order of the layer's ``INPUT_GRADS`` (``x`` first; the cross-attention adds ``src``);
-    ``training`` and ``buffers`` are the BatchNorm mode and the live running statistics of a layer that has them."""
-    __slots__ = ("shape", "weights", "x", "src", "inputs", "mask", "lens", "keep", "p", "training", "buffers", "device", "params")
+    ``training`` and ``buffers`` are the BatchNorm mode and the live running statistics of a layer that has them; ``pos`` is the
+    position table of a Prenet call."""
+    __slots__ = ("shape", "weights", "x", "src", "inputs", "mask", "lens", "keep", "p", "training", "buffers", "device", "params", "pos")
 
 
 class TrainFunction(torch.autograd.Function):

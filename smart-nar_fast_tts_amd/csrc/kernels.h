@@ -494,6 +494,13 @@ hipError_t launch_st_embed_grad(const float* g, const long long* texts, int M, i
 // y [M, D] = padded(m) ? +0.0 : x[m, :] (a select; out of place), padded(m) = mask[m] != 0, or m % S >= lens[m / S] without a mask.
 // D a multiple of 256.  One launch.
 hipError_t launch_st_row_mask(const float* x, const uint8_t* mask, const long long* lens, int M, int S, int D, float* y, hipStream_t st);
+// ---- MelEncoder training: Prenet (melencgrad.hip; transformer/Models.py:103-173, Layers.py:11-26) ----------
+// y [M, F] = h2 k + pos[m % T, :], k = scale where keep [M, F] is nonzero and 0 where it is zero (keep nullable: k = scale); float64,
+// rounded once.  F a multiple of 256; pos [>= T, F].  Out of place.  One launch.
+hipError_t launch_me_drop_pos(const float* h2, const float* pos, const uint8_t* keep, float scale, int M, int T, int F, float* y, hipStream_t st);
+// dh [M, F] = (keep != 0 && h2 > 0) ? g scale : +0.0 (a select; dh is not g); part (nullable) as launch_fg_relu_gate's.  One launch.
+hipError_t launch_me_drop_relu_gate(const float* g, const float* h2, const uint8_t* keep, float scale, int M, int F, float* dh, double* part,
+                                    hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

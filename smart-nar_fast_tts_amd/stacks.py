@@ -1,6 +1,7 @@
 """The reference's ``TxtEncoder`` and ``MelDecoder`` (transformer/Models.py:33-100, 176-244) as trainable modules: the two stacks of
 ``sublayers.FFTBlock`` with what stands in front of them, forward AND backward in HIP (csrc/stackgrad.hip, ``ns_st_*`` in
-include/nar_fs2.h), under the reference's parameter names.
+include/nar_fs2.h), under the reference's parameter names; and its ``MelEncoder`` (transformer/Models.py:103-173), the stack of
+``sublayers.FFTBlock2`` behind ``sublayers.Prenet`` (csrc/melencgrad.hip, ``ns_me_*``).
 
     enc = TxtEncoder(model_config).to(device)
     enc.load_state_dict({k[len("txt_encoder."):]: v for k, v in ckpt["model"].items() if k.startswith("txt_encoder.")})
@@ -20,7 +21,7 @@ import torch
 from . import _lib, ops
 from . import workload as wl
 from ._train import aligned, guard, need_gpu
-from .sublayers import FFTBlock
+from .sublayers import FFTBlock, FFTBlock2, Prenet
 
 
 class Launches:
@@ -189,27 +190,29 @@ class _AddPosFunction(torch.autograd.Function):
 
 
 class _Stack(torch.nn.Module):
-    """What the two stacks share: ``position_enc``, ``layer_stack``, the position table of a call, the lengths of a call, the walk
-    through the layers and the launch bookkeeping."""
+    """What the three stacks share: ``position_enc``, ``layer_stack``, the position table of a call, the lengths of a call, the walk
+    through the layers and the launch bookkeeping.  ``front(d) -> (name, module)`` is what stands in front of the layers
+    (``src_word_emb``, ``prenet``), ``block`` the class of a layer and ``attn`` the name of its attention sublayer."""
 
-    def __init__(self, config, side, n_src_vocab=None):
+    def __init__(self, config, side, front=None, block=FFTBlock, attn="slf_attn"):
         super().__init__()
         t = config["transformer"]
         d, n_head = t[f"{side}_hidden"], t[f"{side}_head"]
         if d % n_head:
             raise ValueError(f"{type(self).__name__}: {side}_hidden must be a multiple of {side}_head, got {d} and {n_head}")
         self.max_seq_len, self.d_model = int(config["max_seq_len"]), d
-        if n_src_vocab is not None:  # (registered in the reference's order: a state dict lists it ahead of the layers)
-            self.src_word_emb = WordEmbedding(n_src_vocab, d)
+        self._attn = attn
+        if front is not None:  # (registered in the reference's order: a state dict lists it ahead of the layers)
+            self.add_module(*front(d))
         self.position_enc = torch.nn.Parameter(torch.from_numpy(wl.sinusoid_table(self.max_seq_len + 1, d).copy())[None], requires_grad=False)
         self.layer_stack = torch.nn.ModuleList([
-            FFTBlock(d, n_head, d // n_head, d // n_head, t["conv_filter_size"], t["conv_kernel_size"], dropout=t[f"{side}_dropout"])
+            block(d, n_head, d // n_head, d // n_head, t["conv_filter_size"], t["conv_kernel_size"], dropout=t[f"{side}_dropout"])
             for _ in range(t[f"{side}_layer"])])
         self.validate_mask = True
         self.book = Launches()  # the stack's own launches: the decoder's position add, a regenerated table
 
     def _hip_modules(self):
-        return [m for layer in self.layer_stack for m in (layer.slf_attn, layer.pos_ffn)]
+        return [m for layer in self.layer_stack for m in (getattr(layer, self._attn), layer.pos_ffn)]
 
     @property
     def launches(self):
@@ -226,7 +229,7 @@ class _Stack(torch.nn.Module):
     def _begin(self):
         self.book.begin()
         for layer in self.layer_stack:  # (a layer's mask_book and the embedding's book begin in their own forward)
-            layer.slf_attn.last_launches, layer.pos_ffn.last_launches = {}, {}
+            getattr(layer, self._attn).last_launches, layer.pos_ffn.last_launches = {}, {}
 
     def _table(self, S, dev):
         """The [>= S, d] position table of a call of S rows: ``position_enc``'s, or, in ``eval()`` past ``max_seq_len``, a regenerated
@@ -288,7 +291,7 @@ class TxtEncoder(_Stack):
     ``src_word_emb`` drops."""
 
     def __init__(self, config, n_src_vocab=wl.N_SYMBOLS + 1):
-        super().__init__(config, "encoder", n_src_vocab)
+        super().__init__(config, "encoder", lambda d: ("src_word_emb", WordEmbedding(n_src_vocab, d)))
 
     def _hip_modules(self):
         return [self.src_word_emb] + super()._hip_modules()
@@ -361,3 +364,87 @@ class MelDecoder(_Stack):
         else:
             x = self._add_pos(enc_seq.detach(), pos)
         return self._layers(x, mask, lens, keep_masks), mask
+
+
+class MelEncoder(_Stack):
+    """Drop-in for ``MelEncoder(config)`` (transformer/Models.py:103-173) whose forward AND backward are HIP: ``prenet.*``
+    (``sublayers.Prenet``: the zeroed first frame, the two Linears, the dropout and the position add), ``position_enc`` ([1,
+    max_seq_len + 1, d], ``requires_grad=False``, the bits of ``workload.sinusoid_table``) and ``layer_stack.N.{crs_attn,pos_ffn}.*`` of
+    ``sublayers.FFTBlock2``, so the ``mel_encoder.*`` slice of a checkpoint loads with ``strict=True`` (``workload.aligner_shapes``
+    lists the names).  Raises ``ValueError`` unless ``decoder_hidden == 256``: the Prenet's width is not configurable in the reference.
+
+    ``forward(src_seq, tgt_seq, src_mask, tgt_mask, return_attns=True, src_lens=None, mel_lens=None, keep_masks=None,
+    prenet_keep_mask=None) -> (dec_output, [attn per layer])`` with ``src_seq`` float32 [B, L, d] (the text encoder's output, the keys
+    and values of every layer), ``tgt_seq`` float32 [B, T, 80] (the reference mel; frame 0 is replaced by zeros and gets a zero
+    gradient), ``src_mask`` bool [B, L] and ``tgt_mask`` bool [B, T] (True = padded).  Padded target rows of ``dec_output`` are exactly
+    ``+0.0``; each map is [B, H, T, L], differentiable, exact 0 at padded phonemes (an empty list with ``return_attns=False``).  Both
+    length vectors are derived once per call from the masks on the device and, while ``validate_mask`` is True, checked against them
+    (one host read each), which passing ``src_lens`` / ``mel_lens`` (int [B] on the device) avoids; every layer gets the source lengths
+    and the target mask and never a [B, T, L] tensor.  ``keep_masks`` is ``n_layers`` pairs (attention, feed-forward) of dropout
+    keep-masks and ``prenet_keep_mask`` the Prenet's; otherwise each sublayer draws its own in ``train()``.
+
+    In ``train()``, or when ``T <= max_seq_len``, it takes the reference's else-branch: ``tgt_seq``, ``tgt_mask`` and ``mel_lens`` are
+    cut to ``max_mel_len = min(T, max_seq_len)`` rows (torch's slice with torch's backward, zeros past the cut, as in ``MelDecoder``)
+    and the maps are [B, H, max_mel_len, L]; given keep-masks have ``max_mel_len`` rows.  In ``eval()`` with ``T > max_seq_len`` the position table is regenerated for ``T`` rows
+    (one more launch) and nothing is cut.
+
+    ``src_seq`` feeds every layer, so its gradient is the sum of the layers' ``dsrc``: autograd's fan-in adds of those are the only
+    torch kernels on the data path (apart from the slice of a truncating call).
+
+    Launches: forward ``Prenet forward + sum over layers (cross-attention forward + 1 + FFN forward + 1)``, plus 1 for a regenerated
+    table; backward the mirror."""
+
+    def __init__(self, config):
+        d = config["transformer"]["decoder_hidden"]
+        if d != Prenet.D:
+            raise ValueError(f"MelEncoder: decoder_hidden must be {Prenet.D} (Prenet is hard-coded {Prenet.N_MEL} -> {Prenet.D} -> {Prenet.D}, "
+                             f"transformer/Layers.py:18-19), got {d}")
+        super().__init__(config, "decoder", lambda d: ("prenet", Prenet()), block=FFTBlock2, attn="crs_attn")
+
+    def _hip_modules(self):
+        return [self.prenet] + super()._hip_modules()
+
+    def _begin(self):
+        super()._begin()
+        self.prenet.last_launches = {}
+
+    def forward(self, src_seq, tgt_seq, src_mask, tgt_mask, return_attns=True, src_lens=None, mel_lens=None, keep_masks=None,
+                prenet_keep_mask=None):
+        need_gpu("MelEncoder", "tgt_seq", tgt_seq)
+        if tgt_seq.dtype != torch.float32 or tgt_seq.dim() != 3 or tgt_seq.shape[2] != Prenet.N_MEL or tgt_seq.numel() == 0:
+            raise ValueError(f"tgt_seq must be a non-empty float32 [B, T, {Prenet.N_MEL}] tensor, got {tgt_seq.dtype} {tuple(tgt_seq.shape)}")
+        B, T, _ = tgt_seq.shape
+        dev = tgt_seq.device
+        if (not isinstance(src_seq, torch.Tensor) or src_seq.device != dev or src_seq.dtype != torch.float32 or src_seq.dim() != 3
+                or src_seq.shape[0] != B or src_seq.shape[2] != self.d_model or src_seq.shape[1] == 0):
+            raise ValueError(f"src_seq must be a float32 [B, L, {self.d_model}] tensor on {dev} with B = {B} and L > 0")
+        L = src_seq.shape[1]
+        n = len(self.layer_stack)
+        if keep_masks is not None and len(keep_masks) != n:
+            raise ValueError(f"keep_masks must hold {n} pairs (one per layer), got {len(keep_masks)}")
+        self._begin()
+        if not isinstance(tgt_mask, torch.Tensor) or tuple(tgt_mask.shape) != (B, T):
+            raise ValueError(f"tgt_mask must be a bool [B, T] = {(B, T)} tensor on {dev}")
+        if self.training or T <= self.max_seq_len:
+            max_len = min(T, self.max_seq_len)
+            if max_len < T:
+                tgt_seq, tgt_mask = tgt_seq[:, :max_len, :], tgt_mask[:, :max_len]
+                if mel_lens is not None:
+                    mel_lens = mel_lens.clamp(max=max_len)
+                T = max_len
+        tgt_mask, mel_lens = self._lengths(tgt_mask, mel_lens, B, T, dev)
+        src_mask, src_lens = self._lengths(src_mask, src_lens, B, L, dev)
+        x = self.prenet(tgt_seq, self._table(T, dev), keep_mask=prenet_keep_mask)
+        attns = []
+        for i, layer in enumerate(self.layer_stack):
+            x, attn = layer(src_seq, x, mask=tgt_mask, src_lens=src_lens, keep_masks=None if keep_masks is None else keep_masks[i])
+            if return_attns:
+                attns.append(attn)
+        return x, attns
+
+    @torch.no_grad()
+    def durations(self, attn_last, src_lens, mel_lens):
+        """Frames per phoneme, int64 [B, L], from the last layer's map [B, H, T, L]: frame ``t < mel_lens[b]`` goes to the phoneme
+        ``l < src_lens[b]`` at which the head-summed map peaks (``ops.aligner_durations``).  The reference's ``_calculate_duration``
+        is undefined; this is the rule ``forward_teacher_forced()`` uses in its place."""
+        return ops.aligner_durations(attn_last.detach(), src_lens, mel_lens)

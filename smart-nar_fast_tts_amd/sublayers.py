@@ -19,7 +19,11 @@ attention loss reads the cross-attention maps of ``FFTBlock2.crs_attn``, which `
 
 ``PositionwiseFeedForward`` (transformer/SubLayers.py:62-95; csrc/ffngrad.hip, ``ns_fg_*``) is the other sublayer of an FFT block, and
 ``FFTBlock`` (transformer/Layers.py:39-48) the composite of ``slf_attn``, ``pos_ffn`` and the row mask (``stacks.mask_rows``) in plain
-Python."""
+Python.
+
+``Prenet`` (transformer/Layers.py:11-26 with the zeroed first frame and the position add of transformer/Models.py:145-162;
+csrc/melencgrad.hip, ``ns_me_*``) and ``FFTBlock2`` (transformer/Layers.py:51-70: ``crs_attn``, ``pos_ffn`` and the row mask) are what
+``stacks.MelEncoder`` is made of."""
 from __future__ import annotations
 
 import ctypes as C
@@ -357,3 +361,118 @@ class FFTBlock(torch.nn.Module):
         if pad is not None:
             enc_output = self._mask_rows(enc_output, mask=pad, book=self.mask_book)
         return enc_output, None
+
+
+PRENET_PARAM_NAMES = ("w_1.weight", "w_1.bias", "w_2.weight", "w_2.bias")  # order of ns_me_weights
+
+
+class Prenet(HipTrainModule):
+    """Drop-in for ``Prenet()`` (transformer/Layers.py:11-26; hard-coded 80 -> 256 -> 256, ``Dropout(0.2)``) together with what
+    ``MelEncoder`` does around it, forward AND backward in HIP (csrc/melencgrad.hip, ``ns_me_*``): the zeroed first frame in front
+    (transformer/Models.py:145-146) and the position add behind (Models.py:151,162).  The same parameter names (``w_1``, ``w_2`` as
+    ``nn.Linear`` with torch's initialisation), so ``mel_encoder.prenet.*`` of a reference checkpoint loads strictly.
+
+        p = Prenet().to(device)
+        y = p(mels, pos)             # dropout(relu(w_2(relu(w_1(mels with frame 0 zeroed))))) + pos[:T]
+        y.backward(dy)
+
+    ``forward(x, pos, keep_mask=None)`` with ``x`` float32 [B, T, 80], never written, and ``pos`` float32 [>= T, 256], the position
+    table of the call, which gets no gradient.  ``x`` gets one only if it requires one; its frame 0 is exactly ``+0.0`` then, and a NaN
+    in frame 0 of ``x`` reaches nothing.  The drop probability is 0.2 in ``train()`` and 0 in ``eval()``; the keep-mask is drawn with
+    ``torch.bernoulli`` on the device, or ``keep_mask`` (bool or uint8 [B, T, 256], nonzero = kept) supplies it.  Under
+    ``torch.no_grad()``, or when neither ``x`` nor a parameter requires grad, a call keeps nothing.  Otherwise it is one
+    ``torch.autograd.Function`` (single backward) that keeps the zeroed input and the two activations ((80 + 2 * 256) B T floats) and
+    whose backward honours ``needs_input_grad``.  Both ReLU backwards gate on the saved activations."""
+
+    ABI, INPUT, INPUT_GRADS = "ns_me", "x", ("dmels",)
+    PARAM_NAMES, FIELDS = PRENET_PARAM_NAMES, _lib.ME_NAMES
+    WEIGHTS, GRADS = _lib.NsMeWeights, _lib.NsMeGrads
+    WORKSPACES = WorkspaceCache("ns_me_ws_bytes", ("B", "T", "n_mel", "d"))
+    N_MEL, D, P_DROP = 80, 256, 0.2
+
+    def __init__(self):
+        super().__init__()
+        self.p_drop = self.P_DROP
+        self.w_1 = torch.nn.Linear(self.N_MEL, self.D)
+        self.w_2 = torch.nn.Linear(self.D, self.D)
+
+    def _marshal(self, x, pos, keep_mask):
+        call = self._begin(x, self.N_MEL)
+        B, T, _ = x.shape
+        dev = call.device
+        if not isinstance(pos, torch.Tensor) or pos.dim() != 2 or pos.shape[0] < T or pos.shape[1] != self.D or pos.dtype != torch.float32 or pos.device != dev:
+            raise ValueError(f"pos must be a float32 [>= {T}, {self.D}] tensor on {dev}")
+        call.pos = aligned(pos.detach())
+        s = _lib.NsMeShape()
+        s.B, s.T, s.n_mel, s.d = B, T, self.N_MEL, self.D
+        call.shape = s
+        call.p = self.p_drop if self.training else 0.0
+        call.keep = self._keep_masks(None if keep_mask is None else (keep_mask,), [(B, T, self.D)], dev, call.p)[0]
+        return call
+
+    def forward(self, x, pos, keep_mask=None):
+        return self._dispatch(self._marshal(x, pos, keep_mask), x)
+
+    def _forward(self, call, save):
+        s, dev = call.shape, call.device
+        with guard(dev):
+            ws, saved = self._workspace(call, save)
+            y = torch.empty((s.B, s.T, s.d), dtype=torch.float32, device=dev)
+            self._done(self._lib.ns_me_forward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.pos), _lib.ptr(call.keep), call.p,
+                                               _lib.ptr(y), _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "forward")
+        return y, saved
+
+    def _backward(self, call, saved, g, need):
+        """Gradients of ``(g * y).sum()``: a list (dmels, then the four of PRENET_PARAM_NAMES) with None where ``need`` is False."""
+        s, dev = call.shape, call.device
+        if tuple(g.shape) != (s.B, s.T, s.d) or g.dtype != torch.float32 or g.device != dev:
+            raise ValueError(f"grad_output must be a float32 {(s.B, s.T, s.d)} tensor on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+        g = aligned(g)
+        with guard(dev):
+            outs, d = self._grad_block(call, need)
+            ws, _ = self._workspace(call, save=False)
+            self._done(self._lib.ns_me_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.keep), call.p, _lib.ptr(saved), _lib.ptr(g),
+                                                C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward")
+        return outs
+
+
+class FFTBlock2(torch.nn.Module):
+    """The reference's ``FFTBlock2(d_model, n_head, d_k, d_v, d_inner, kernel_size, dropout=0.1)`` (transformer/Layers.py:51-70) as a
+    trainable module: ``crs_attn`` is ``MultiHeadCrossAttention`` and ``pos_ffn`` is ``PositionwiseFeedForward``, both HIP in forward
+    and backward, composed in plain Python as ``FFTBlock`` is, so ``mel_encoder.layer_stack.N.*`` of a reference checkpoint loads
+    strictly.  The two ``masked_fill(mask.unsqueeze(-1), 0)`` are ``stacks.mask_rows`` (``mask_book`` counts them).
+
+    ``forward(src_input, tgt_input, mask=None, crs_attn_mask=None, src_lens=None, keep_masks=None) -> (enc_output, attn)``:
+    ``src_input`` float32 [B, L, d_model] (the keys and values), ``tgt_input`` float32 [B, T, d_model] (the queries), ``mask`` the bool
+    [B, T] padding mask of the target rows (True = padded; those rows of the output are exactly 0; without it no row is zeroed),
+    ``crs_attn_mask`` and ``src_lens`` follow ``MultiHeadCrossAttention``'s rules (the reference's [B, T, L] key-padding mask, or int
+    [B] source lengths on the device at no host read, or both).  ``keep_masks`` supplies the two dropout keep-masks (attention,
+    feed-forward), each [B, T, d_model].  ``attn`` is the [B, H, T, L] map, differentiable."""
+
+    def __init__(self, d_model, n_head, d_k, d_v, d_inner, kernel_size, dropout=0.1):
+        super().__init__()
+        self.crs_attn = MultiHeadCrossAttention(n_head, d_model, d_k, d_v, dropout=dropout)
+        self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, kernel_size, dropout=dropout)
+        from . import stacks  # (stacks imports this module: resolved here, at first use)
+
+        self._mask_rows, self.mask_book = stacks.mask_rows, stacks.Launches()
+
+    def forward(self, src_input, tgt_input, mask=None, crs_attn_mask=None, src_lens=None, keep_masks=None):
+        if keep_masks is not None and len(keep_masks) != 2:
+            raise ValueError(f"keep_masks must hold 2 masks (attention, feed-forward), got {len(keep_masks)}")
+        k_attn, k_ffn = keep_masks if keep_masks is not None else (None, None)
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(tgt_input.shape[:2]) or mask.device != tgt_input.device:
+                raise ValueError(f"mask must be a bool [B, T] = {tuple(tgt_input.shape[:2])} tensor on {tgt_input.device}")
+            pad = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+            pad = pad.contiguous().view(torch.uint8)  # (a bool's bytes are 0 and 1: no kernel)
+        else:
+            pad = None
+        self.mask_book.begin()
+        enc_output, attn = self.crs_attn(tgt_input, src_input, src_input, mask=crs_attn_mask, lens=src_lens, keep_mask=k_attn)
+        if pad is not None:
+            enc_output = self._mask_rows(enc_output, mask=pad, book=self.mask_book)
+        enc_output = self.pos_ffn(enc_output, keep_mask=k_ffn)
+        if pad is not None:
+            enc_output = self._mask_rows(enc_output, mask=pad, book=self.mask_book)
+        return enc_output, attn

@@ -1391,6 +1391,59 @@ int ns_me_op_drop_pos(const float* h2, const float* pos, const uint8_t* keep, fl
 int ns_me_op_drop_relu_gate(const float* g, const float* h2, const uint8_t* keep, float p_drop, int M, int d, float* dh, float* d_b2,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* ==== Mel head: mel_linear and the PostNet residual, a training forward and its backward ===========================================
+ * (model/fastspeech2_align.py:24,83,85).  Handle-less; nothing above changes (every other ABI version stays as it is).  With
+ * x [B, T, d] (the decoder's output), M = B * T rows:
+ *   y = x w^T + b                      (fastspeech2_align.py:83, nn.Linear(decoder_hidden, n_mel_channels) of line 24)   [M, n_mel]
+ *   out = postnet(y) + y               (fastspeech2_align.py:85; the add is ns_mh_op_residual, the PostNet is ns_pn_*)
+ * The weight is a LIVE device tensor in checkpoint (torch nn.Linear) layout.  Exact fp32 on the fp32 matrix cores; the bias gradient
+ * in float64, rounded once.  No atomic, no host read; equal inputs give equal bits.  Nothing is saved between the two calls: the
+ * backward needs x and g alone.  No row is masked: the reference masks none here (a padded row of y equals the bias). */
+#define NS_MH_ABI_VERSION 1 /* what ns_mh_abi_version() returns */
+int ns_mh_abi_version(void);
+typedef struct ns_mh_shape { int32_t B, T, d, n_mel; } ns_mh_shape;
+/* Device pointers, 16-byte aligned, fp32, checkpoint layout. */
+typedef struct ns_mh_weights {
+  const float* w; /* [n_mel, d] mel_linear.weight (fastspeech2_align.py:24) */
+  const float* b; /* [n_mel] */
+} ns_mh_weights;
+/* The outputs of ns_mh_backward: dx [B, T, d] and the two parameter gradients, shaped as the weights.  16-byte aligned.  NULL = not
+ * wanted: neither computed nor written, and a launch none of whose outputs is wanted is not made. */
+typedef struct ns_mh_grads {
+  float *dx, *w, *b;
+} ns_mh_grads;
+/* Bytes of the workspace of ns_mh_forward / ns_mh_backward of this shape (0 and ns_last_error() for a refused shape). */
+size_t ns_mh_ws_bytes(const ns_mh_shape* shape);
+/* Kernel launches the calling thread's last ns_mh_* call enqueued. */
+int ns_mh_last_launches(void);
+/* Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null shape or weights, a null argument, a
+ * pointer that is not 16-byte aligned, d not 256 or 512, n_mel not a multiple of 16 in [16, 128], B or T not positive,
+ * B * T * d >= 2^31, a shape the Conv1D-as-GEMM dispatch or the weight gradient's plan (ns_pg_plan_wgrad) refuses, a workspace smaller
+ * than ns_mh_ws_bytes.
+ * y [B, T, n_mel] = x w^T + b (fastspeech2_align.py:83).  x is never written.  At KW = 1 the nn.Linear layout is the dispatch's
+ * packed form, so the live weight is read and there is no pack launch.
+ * Launches: G(M, n_mel, d), the Conv1D-as-GEMM dispatch's own launch count for that shape (ns_plan_gemm_launches(M, n_mel, d, 1, 0),
+ * 1 or 2). */
+int ns_mh_forward(const ns_mh_shape* shape, const ns_mh_weights* weights, const float* x, float* y, void* ws, size_t ws_bytes,
+                  void* stream);
+/* The gradient of sum g[m, :] . y[m, :] (g [B, T, n_mel], read only, on every row) with respect to every non-NULL member of grads
+ * (the backward of fastspeech2_align.py:83), from x as ns_mh_forward read it.
+ * Launches: 1 (g padded to 128 columns, with the partials of d_b; wanted by w or b) + 1 (d_b: bias finish) + 3 (dW at the padded
+ * width: GEMM, fixed-order reduce, copy of the first n_mel rows) + 1 (pack of w^T) + G(M, d, n_mel) (dx, reading g at row stride
+ * n_mel) = 6 + G(M, d, n_mel) with every output wanted.  An unwanted output drops its launches; with no output wanted the call
+ * validates and launches nothing. */
+int ns_mh_backward(const ns_mh_shape* shape, const ns_mh_weights* weights, const float* x, const float* g, const ns_mh_grads* grads,
+                   void* ws, size_t ws_bytes, void* stream);
+/* The two new kernels alone.  n_mel a multiple of 16 in [16, 128], M positive.
+ * dz [M, 128] = g [M, n_mel] with exact +0.0 in the columns [n_mel, 128), whatever dz held (the feed of the weight gradient at the
+ * padded width); dz is not g, which is only read.  Unless d_bias is NULL, d_bias [n_mel] = the column sums of g: float64 partials per
+ * 64 rows, added in ascending block order, rounded once.  ws (needed with d_bias only): ceil(M / 64) * n_mel doubles.  One launch, two
+ * with d_bias. */
+int ns_mh_op_pad_colsum(const float* g, int M, int n_mel, float* dz, float* d_bias, void* ws, size_t ws_bytes, void* stream);
+/* out [M, n_mel] = p + x (fastspeech2_align.py:85: postnet(output) + output).  Out of place.  Its backward makes no launch: the
+ * gradient of both operands is grad_output itself.  One launch. */
+int ns_mh_op_residual(const float* p, const float* x, int M, int n_mel, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

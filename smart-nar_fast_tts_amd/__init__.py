@@ -4,8 +4,8 @@
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
 when it is missing.  ``FastSpeech2Loss``, ``FastSpeech2TrainingLoss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
-``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``), the trainable ``VariancePredictor`` (``predictor``), ``MultiHeadAttention`` / ``MultiHeadCrossAttention`` / ``PositionwiseFeedForward`` / ``FFTBlock`` / ``Prenet`` / ``FFTBlock2`` (``sublayers``) the trainable ``PostNet`` (``postnet``) and the trainable ``VarianceAdaptor`` with its ``VarianceEmbedding`` and ``LengthRegulator`` (``adaptor``) and the trainable ``TxtEncoder`` / ``MelDecoder`` / ``MelEncoder`` stacks with their ``WordEmbedding`` and ``mask_rows`` (``stacks``) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim", "VariancePredictor", "MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2", "PostNet", "VarianceAdaptor", "VarianceEmbedding", "LengthRegulator", "TxtEncoder", "MelDecoder", "MelEncoder", "WordEmbedding", "mask_rows"]
+``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``), the trainable ``VariancePredictor`` (``predictor``), ``MultiHeadAttention`` / ``MultiHeadCrossAttention`` / ``PositionwiseFeedForward`` / ``FFTBlock`` / ``Prenet`` / ``FFTBlock2`` (``sublayers``) the trainable ``PostNet`` (``postnet``) and the trainable ``VarianceAdaptor`` with its ``VarianceEmbedding`` and ``LengthRegulator`` (``adaptor``) and the trainable ``TxtEncoder`` / ``MelDecoder`` / ``MelEncoder`` stacks with their ``WordEmbedding`` and ``mask_rows`` (``stacks``), the trainable ``MelLinear`` (``sublayers``) and the ``training`` module (the trainable ``FastSpeech2Align``, ``get_model``, ``train_step``, ``save_checkpoint``, ``add_residual``) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim", "VariancePredictor", "MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2", "PostNet", "VarianceAdaptor", "VarianceEmbedding", "LengthRegulator", "TxtEncoder", "MelDecoder", "MelEncoder", "WordEmbedding", "mask_rows", "MelLinear", "training"]
 
 
 def __getattr__(name):
@@ -29,7 +29,11 @@ def __getattr__(name):
         from . import predictor
 
         return predictor.VariancePredictor
-    if name in ("MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2"):
+    if name == "training":  # the trainable FastSpeech2Align, get_model, train_step, save_checkpoint, add_residual
+        import importlib
+
+        return importlib.import_module(".training", __name__)
+    if name in ("MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2", "MelLinear"):
         from . import sublayers
 
         return getattr(sublayers, name)

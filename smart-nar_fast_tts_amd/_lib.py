@@ -177,6 +177,24 @@ class NsMeGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dmels",) + ME_NAMES]
 
 
+class NsMhShape(C.Structure):
+    """``ns_mh_shape`` (include/nar_fs2.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "d", "n_mel")]
+
+
+MH_NAMES = ("w", "b")
+
+
+class NsMhWeights(C.Structure):
+    """``ns_mh_weights`` (include/nar_fs2.h): ``mel_linear``'s two parameters in checkpoint layout."""
+    _fields_ = [(n, C.c_void_p) for n in MH_NAMES]
+
+
+class NsMhGrads(C.Structure):
+    """``ns_mh_grads`` (include/nar_fs2.h): ``dx`` and the two parameter gradients, each nullable."""
+    _fields_ = [(n, C.c_void_p) for n in ("dx",) + MH_NAMES]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -412,6 +430,14 @@ SIGNATURES = {
     "ns_me_backward": (_I, [C.POINTER(NsMeShape), C.POINTER(NsMeWeights), _P, _F, _P, _P, C.POINTER(NsMeGrads), _P, _Z, _P]),
     "ns_me_op_drop_pos": (_I, [_P, _P, _P, _F, _I, _I, _I, _P, _P]),
     "ns_me_op_drop_relu_gate": (_I, [_P, _P, _P, _F, _I, _I, _P, _P, _P, _Z, _P]),
+    # mel head: mel_linear and the PostNet residual, training forward and backward (sublayers.MelLinear, training.add_residual; handle-less)
+    "ns_mh_abi_version": (_I, []),
+    "ns_mh_ws_bytes": (_Z, [C.POINTER(NsMhShape)]),
+    "ns_mh_last_launches": (_I, []),
+    "ns_mh_forward": (_I, [C.POINTER(NsMhShape), C.POINTER(NsMhWeights), _P, _P, _P, _Z, _P]),
+    "ns_mh_backward": (_I, [C.POINTER(NsMhShape), C.POINTER(NsMhWeights), _P, _P, C.POINTER(NsMhGrads), _P, _Z, _P]),
+    "ns_mh_op_pad_colsum": (_I, [_P, _I, _I, _P, _P, _P, _Z, _P]),
+    "ns_mh_op_residual": (_I, [_P, _P, _I, _I, _P, _P]),
 }
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*

@@ -501,6 +501,13 @@ hipError_t launch_me_drop_pos(const float* h2, const float* pos, const uint8_t* 
 // dh [M, F] = (keep != 0 && h2 > 0) ? g scale : +0.0 (a select; dh is not g); part (nullable) as launch_fg_relu_gate's.  One launch.
 hipError_t launch_me_drop_relu_gate(const float* g, const float* h2, const uint8_t* keep, float scale, int M, int F, float* dh, double* part,
                                     hipStream_t st);
+// ---- mel head training: mel_linear and the PostNet residual (melheadgrad.hip; model/fastspeech2_align.py:24,83,85) --
+// dz [M, PN_PAD_N] = g [M, n_mel] with +0.0 in the columns [n_mel, PN_PAD_N) (dz uninitialised, g only read); part (nullable)
+// [pg_row_blocks(M)][n_mel] doubles, uninitialised: the column sums of g per 64 rows, summed by launch_pn_bias_finish at
+// nblk = pg_row_blocks(M).  n_mel a multiple of 4 up to PN_PAD_N.  One launch.
+hipError_t launch_mh_pad_colsum(const float* g, int M, int n_mel, float* dz, double* part, hipStream_t st);
+// out [M, n_mel] = p + x; n_mel a multiple of 4.  Out of place.  One launch.
+hipError_t launch_mh_residual(const float* p, const float* x, int M, int n_mel, float* out, hipStream_t st);
 // sets ns_last_error() (api.hip) and returns 1
 int api_fail(const char* msg);
 

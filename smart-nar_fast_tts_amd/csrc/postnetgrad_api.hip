@@ -103,16 +103,6 @@ int common(const std::string& w, const ns_pn_shape* s, const ns_pn_weights* k, i
   return check_aligned(w, {{"x", x}, {"saved", saved}, {"the workspace", ws_mem}, io});
 }
 
-// the weight gradient at the padded width: dz [M, 128] with zero columns [N, 128) -> dwpad [128][Cin][KW] -> dW = its first N rows
-int wgrad_narrow(const float* dz, const float* X, int M, int S, int N, int Cin, int KW, float* partial, float* dwpad, float* dW, hipStream_t st) {
-  PgWgradPlan pl;
-  if (!pg_plan_wgrad(M, PN_PAD_N, Cin, KW, &pl)) return api_fail("ns_pn: the weight gradient's plan refuses this shape");
-  NS_HIP(launch_pg_wgrad(dz, X, M, S, PN_PAD_N, Cin, KW, pl, partial, dwpad, st, PN_PAD_N));
-  NS_HIP(launch_pn_copy(dwpad, dW, (long long)N * Cin * KW, st));
-  t_launches += 3;
-  return 0;
-}
-
 int check_op(const std::string& w, int M, int C, float p_drop, const uint8_t* keep, std::initializer_list<NamedPtr> al) {
   if (M <= 0) return api_fail(w + "M must be positive, got " + std::to_string(M));
   if (C <= 0 || C % 16 != 0 || C > 512) return api_fail(w + "C must be a multiple of 16 up to 512, got " + std::to_string(C));
@@ -239,7 +229,7 @@ extern "C" int ns_pn_backward(const ns_pn_shape* s, const ns_pn_weights* k, int 
     ++t_launches;
     if (gl.w) {
       if (last) {
-        NS_TRY(wgrad_narrow(ws.a, h_in, M, s->T, co, ci, K, ws.partial, ws.dwpad, gl.w, st));
+        NS_TRY(counted.wgrad_narrow(ws.a, h_in, M, s->T, co, ci, K, ws.partial, ws.dwpad, gl.w, st));
       } else {
         PgWgradPlan pl;
         pg_plan_wgrad(M, co, ci, K, &pl);  // (accepted by carve above)
@@ -368,5 +358,5 @@ extern "C" int ns_pn_op_wgrad_narrow(const float* dz, const float* X, int B, int
   float* partial = bump.f((size_t)pl.ws_floats);
   float* dwpad = bump.f((size_t)PN_PAD_N * Cin * KW);
   if (ws_bytes < bump.off) return api_fail(w + "workspace too small: " + std::to_string(bump.off) + " bytes needed");
-  return wgrad_narrow(dz, X, M, S, N, Cin, KW, partial, dwpad, dW, (hipStream_t)stream);
+  return counted.wgrad_narrow(dz, X, M, S, N, Cin, KW, partial, dwpad, dW, (hipStream_t)stream);
 }

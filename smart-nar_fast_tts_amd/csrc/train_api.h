@@ -1,6 +1,6 @@
 // Host-side helpers shared by the handle-less training ABIs (ns_pg_*, ns_ag_*, ns_xg_*, ns_pn_*, ns_va_*, ns_fg_* in the six *grad_api.hip;
 // DESIGN.md section 20): the argument checks whose texts they state alike, the workspace and size-query wrappers, the counted launches
-// of the kernels they share (Conv1D-as-GEMM, weight pack, column-partial finish) and the row-backward argument blocks.  Host-only, no
+// of the kernels they share (Conv1D-as-GEMM, weight pack, column-partial finish, padded weight gradient) and the row-backward argument blocks.  Host-only, no
 // kernels.  Each ABI keeps its own thread-local launch counter and hands it in as a Counted; what differs between the layers
 // (check_dims, Ws, carve, the forward and backward bodies) stays with the layer.
 #pragma once
@@ -142,6 +142,18 @@ struct Counted {
     if (!any) return 0;
     NS_HIP(launch_pg_col_final(part, nblk, F, fin, st));
     ++*launches;
+    return 0;
+  }
+
+  // the weight gradient at the padded width: dz [M, 128] with zero columns [N, 128) -> dwpad [128][Cin][KW] -> dW = its first N rows
+  // (PostNet's last layer, mel_linear): the GEMM, its fixed-order reduce and the copy, three launches
+  int wgrad_narrow(const float* dz, const float* X, int M, int S, int N, int Cin, int KW, float* partial, float* dwpad, float* dW,
+                   hipStream_t st) const {
+    PgWgradPlan pl;
+    if (!pg_plan_wgrad(M, PN_PAD_N, Cin, KW, &pl)) return api_fail(std::string(abi) + ": the weight gradient's plan refuses this shape");
+    NS_HIP(launch_pg_wgrad(dz, X, M, S, PN_PAD_N, Cin, KW, pl, partial, dwpad, st, PN_PAD_N));
+    NS_HIP(launch_pn_copy(dwpad, dW, (long long)N * Cin * KW, st));
+    *launches += 3;
     return 0;
   }
 };

@@ -23,7 +23,10 @@ Python.
 
 ``Prenet`` (transformer/Layers.py:11-26 with the zeroed first frame and the position add of transformer/Models.py:145-162;
 csrc/melencgrad.hip, ``ns_me_*``) and ``FFTBlock2`` (transformer/Layers.py:51-70: ``crs_attn``, ``pos_ffn`` and the row mask) are what
-``stacks.MelEncoder`` is made of."""
+``stacks.MelEncoder`` is made of.
+
+``MelLinear`` (model/fastspeech2_align.py:24,83; csrc/melheadgrad.hip, ``ns_mh_*``) is the ``mel_linear`` between the decoder and the
+PostNet of ``training.FastSpeech2Align``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -433,6 +436,66 @@ class Prenet(HipTrainModule):
             ws, _ = self._workspace(call, save=False)
             self._done(self._lib.ns_me_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.keep), call.p, _lib.ptr(saved), _lib.ptr(g),
                                                 C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward")
+        return outs
+
+
+class MelLinear(HipTrainModule):
+    """Drop-in for ``mel_linear = nn.Linear(decoder_hidden, n_mel_channels)`` (model/fastspeech2_align.py:24,83), forward AND backward
+    in HIP (csrc/melheadgrad.hip, ``ns_mh_*``): ``weight`` [n_mel, d] and ``bias`` [n_mel] with ``nn.Linear``'s initialisation, so
+    ``mel_linear.*`` of a reference checkpoint loads strictly.
+
+        lin = MelLinear(256).to(device)
+        y = lin(x)                   # x [B, T, d] -> y [B, T, n_mel] = x weight^T + bias
+        y.backward(dy)
+
+    ``d`` is 256 or 512 and ``n_mel`` a multiple of 16 up to 128.  No row is masked: the reference masks none here, a padded row of
+    ``y`` equals the bias and feeds the PostNet's batch statistics.  Under ``torch.no_grad()``, or when neither ``x`` nor a parameter
+    requires grad, a call is the forward alone.  Otherwise it is one ``torch.autograd.Function`` (single backward) that keeps nothing
+    but ``x`` and whose backward honours ``needs_input_grad``: the 80-column weight gradient runs at the padded width 128 (pad, GEMM,
+    reduce, copy), the bias gradient is float64 column sums in one order, the data gradient is one pack and the GEMM dispatch."""
+
+    ABI, INPUT = "ns_mh", "x"
+    PARAM_NAMES, FIELDS = ("weight", "bias"), _lib.MH_NAMES
+    WEIGHTS, GRADS = _lib.NsMhWeights, _lib.NsMhGrads
+    WORKSPACES = WorkspaceCache("ns_mh_ws_bytes", ("B", "T", "d", "n_mel"))
+
+    def __init__(self, d, n_mel=80):
+        super().__init__()
+        self.d, self.n_mel = int(d), int(n_mel)
+        if self.d not in (256, 512):
+            raise ValueError(f"MelLinear: d must be 256 or 512, got {d}")
+        if self.n_mel < 16 or self.n_mel > 128 or self.n_mel % 16:
+            raise ValueError(f"MelLinear: n_mel must be a multiple of 16 in [16, 128], got {n_mel}")
+        init = torch.nn.Linear(self.d, self.n_mel)  # (nn.Linear's initialisation, its draws in its order)
+        self.weight, self.bias = init.weight, init.bias
+
+    def forward(self, x):
+        call = self._begin(x, self.d)
+        s = _lib.NsMhShape()
+        s.B, s.T, s.d, s.n_mel = x.shape[0], x.shape[1], self.d, self.n_mel
+        call.shape = s
+        return self._dispatch(call, x)
+
+    def _forward(self, call, save):
+        s, dev = call.shape, call.device
+        with guard(dev):
+            ws, _ = self._workspace(call, save=False)  # (nothing is saved: the backward reads x and g alone)
+            y = torch.empty((s.B, s.T, s.n_mel), dtype=torch.float32, device=dev)
+            self._done(self._lib.ns_mh_forward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(y), _lib.ptr(ws), ws.numel(),
+                                               _lib.stream_ptr(dev)), "forward")
+        return y, None
+
+    def _backward(self, call, saved, g, need):
+        """Gradients of ``(g * y).sum()``: a list (dx, d_weight, d_bias) with None where ``need`` is False."""
+        s, dev = call.shape, call.device
+        if tuple(g.shape) != (s.B, s.T, s.n_mel) or g.dtype != torch.float32 or g.device != dev:
+            raise ValueError(f"grad_output must be a float32 {(s.B, s.T, s.n_mel)} tensor on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+        g = aligned(g)
+        with guard(dev):
+            outs, d = self._grad_block(call, need)
+            ws, _ = self._workspace(call, save=False)
+            self._done(self._lib.ns_mh_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(g), C.byref(d), _lib.ptr(ws),
+                                                ws.numel(), _lib.stream_ptr(dev)), "backward")
         return outs
 
 

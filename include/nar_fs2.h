@@ -1444,6 +1444,57 @@ int ns_mh_op_pad_colsum(const float* g, int M, int n_mel, float* dz, float* d_bi
  * gradient of both operands is grad_output itself.  One launch. */
 int ns_mh_op_residual(const float* p, const float* x, int M, int n_mel, float* out, void* stream);
 
+/* ==== Dropout keep-masks: a counter-based generator, every mask of a training step in one launch ==================================
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  A mask is uint8 (1 = kept, 0 = dropped) over the flat
+ * C order of its [B, S, C] elements, and its bytes are a pure function of (seed, call, stream, element index):
+ *   generator  Philox4x32-10: multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85,
+ *              key = (seed & 0xffffffff, seed >> 32) of the 64-bit seed
+ *   counter    (j, stream, call & 0xffffffff, call >> 32): stream is the 32-bit id of the mask within the call, call the 64-bit draw
+ *              counter, j the block index within the mask
+ *   element e  is word e & 3 of block j = e >> 2 (so a mask has fewer than 2^34 elements)
+ *   keep       = word < thr, thr = floor((1.0 - p) * 4294967296.0) in float64 (ns_km_threshold)
+ * So a mask does not depend on where it lies in an arena, on the masks drawn with it or on the launch geometry.
+ * Arena: the masks of one draw lie back to back in the order given; a slot starts at a multiple of 16 bytes and is
+ * ceil(n / 16) * 16 bytes long; the bytes of a slot behind element n - 1 are written as 0; nothing outside a slot is written.
+ * No atomic, no host read, plain 16-byte vector stores; equal arguments give equal bits. */
+#define NS_KM_ABI_VERSION 1      /* what ns_km_abi_version() returns */
+#define NS_KM_MAX_MASKS 1024     /* masks of one table at most */
+#define NS_KM_GRID_CAP 2048      /* workgroups of one ns_km_draw at most (256 threads, 4096 elements a turn); they loop over the chunks beyond */
+#define NS_KM_TABLE_ROW_BYTES 32 /* a table is n_masks + 1 rows */
+int ns_km_abi_version(void);
+/* Kernel launches the calling thread's last ns_km_draw enqueued (1, or 0 after a refusal; ns_km_host_draw sets 0). */
+int ns_km_last_launches(void);
+/* One mask of a draw. */
+typedef struct ns_km_mask {
+  uint64_t n;      /* elements, in [1, 2^34) */
+  uint32_t stream; /* the mask's id within the call */
+  uint32_t thr;    /* ns_km_threshold of its drop probability; not 0 */
+} ns_km_mask;
+/* *thr = floor((1.0 - p) * 4294967296.0), evaluated in float64: 0.1 -> 3865470566, 0.2 -> 3435973836, 0.5 -> 2147483648.  Nonzero with
+ * ns_last_error() on: a null thr, p outside (0, 1) (a NaN included), a threshold of 0 (p within 2^-32 of 1) or of 2^32 (1.0 - p == 1.0). */
+int ns_km_threshold(double p, uint32_t* thr);
+/* Bytes of the table of n_masks masks: (n_masks + 1) * NS_KM_TABLE_ROW_BYTES; 0 and ns_last_error() for n_masks outside
+ * [1, NS_KM_MAX_MASKS]. */
+size_t ns_km_table_bytes(int n_masks);
+/* Pure host logic: validates the descriptors, lays the slots out in the order given and writes the table ns_km_draw's kernel reads
+ * (per mask {arena byte offset, n, stream, thr, chunks of 4096 elements before it}, then a closing row) into table_host, and the
+ * arena's size into *arena_bytes.  Nonzero with ns_last_error() on: a null pointer, n_masks outside [1, NS_KM_MAX_MASKS], an n of 0
+ * or >= 2^34, a thr of 0, table_bytes below ns_km_table_bytes(n_masks). */
+int ns_km_plan(const ns_km_mask* masks, int n_masks, void* table_host, size_t table_bytes, uint64_t* arena_bytes);
+/* Draws every mask of the table into arena: EXACTLY ONE launch.  table_dev is a DEVICE copy of what ns_km_plan wrote (8-byte aligned;
+ * the upload is the caller's host-to-device copy), arena a device buffer (16-byte aligned) of the planned arena_bytes.  Nonzero with
+ * ns_last_error(), before any HIP call, on: a null or misaligned pointer, n_masks outside [1, NS_KM_MAX_MASKS], an arena shorter than
+ * 16 * n_masks bytes (the least any plan of n_masks masks needs: the table lives on the device and is not read by the host).  The
+ * kernel itself makes no store that would end behind arena + arena_bytes, so a short arena truncates the draw and is never overrun. */
+int ns_km_draw(const void* table_dev, int n_masks, uint64_t seed, uint64_t call, void* arena, size_t arena_bytes, void* stream);
+/* out[4] = Philox4x32-10 of ctr[4] under key[2], on the host (no GPU), through the inline function the kernel compiles.
+ * ctr {0,0,0,0} key {0,0} -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8. */
+int ns_km_op_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+/* ns_km_draw on the host (no GPU): fills arena_host from table_host (what ns_km_plan wrote) through the same inline functions.
+ * Nonzero with ns_last_error() on: a null pointer, n_masks outside [1, NS_KM_MAX_MASKS], a table that is not a plan's (an n or thr it
+ * would refuse, a slot out of place), an arena shorter than the plan's. */
+int ns_km_host_draw(const void* table_host, int n_masks, uint64_t seed, uint64_t call, void* arena_host, size_t arena_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,11 @@ class NsMhGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dx",) + MH_NAMES]
 
 
+class NsKmMask(C.Structure):
+    """``ns_km_mask`` (include/nar_fs2.h): one mask of a keep-mask draw."""
+    _fields_ = [("n", C.c_uint64), ("stream", C.c_uint32), ("thr", C.c_uint32)]
+
+
 class NsMelConfig(C.Structure):
     """``ns_mel_config`` (include/nar_fs2.h)."""
     _fields_ = [(n, C.c_int32) for n in ("filter_length", "hop_length", "win_length", "n_mel")] + [("clip_val", C.c_float)]
@@ -438,7 +443,17 @@ SIGNATURES = {
     "ns_mh_backward": (_I, [C.POINTER(NsMhShape), C.POINTER(NsMhWeights), _P, _P, C.POINTER(NsMhGrads), _P, _Z, _P]),
     "ns_mh_op_pad_colsum": (_I, [_P, _I, _I, _P, _P, _P, _Z, _P]),
     "ns_mh_op_residual": (_I, [_P, _P, _I, _I, _P, _P]),
+    # dropout keep-masks from a counter-based generator, one launch per draw (dropout.KeepMaskRNG; handle-less)
+    "ns_km_abi_version": (_I, []),
+    "ns_km_last_launches": (_I, []),
+    "ns_km_threshold": (_I, [C.c_double, C.POINTER(C.c_uint32)]),
+    "ns_km_table_bytes": (_Z, [_I]),
+    "ns_km_plan": (_I, [C.POINTER(NsKmMask), _I, _P, _Z, C.POINTER(C.c_uint64)]),
+    "ns_km_draw": (_I, [_P, _I, C.c_uint64, C.c_uint64, _P, _Z, _P]),
+    "ns_km_op_philox": (_I, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ns_km_host_draw": (_I, [_P, _I, C.c_uint64, C.c_uint64, _P, _Z]),
 }
+KM_MAX_MASKS, KM_GRID_CAP, KM_TABLE_ROW_BYTES = 1024, 2048, 32  # include/nar_fs2.h NS_KM_*
 
 STATUS_TRUNCATED, STATUS_BAD_TOKEN = 1, 2  # include/nar_fs2.h NS_STATUS_*
 

@@ -129,6 +129,7 @@ class HipTrainModule(CountedModule):
     saved)`` and ``_backward(call, saved, g, need) -> [input gradients, parameter gradients]``."""
 
     INPUT_GRADS = ("dx",)
+    _keep_mask_rng = None  # a dropout.KeepMaskRNG once dropout.attach() set one; None: torch.bernoulli draws the masks
 
     def ordered_parameters(self):
         named = dict(self.named_parameters())
@@ -160,7 +161,7 @@ class HipTrainModule(CountedModule):
     def _keep_masks(self, given, shapes, dev, p, stacked=False):
         """The keep-masks (uint8, one per entry of ``shapes``) of a call at drop probability ``p``: the ``given`` ones validated, else
         drawn with ``torch.bernoulli`` — one draw per mask in order, or, ``stacked`` (the shapes are equal), one draw of all of them —
-        else Nones."""
+        else Nones.  With a generator attached (``dropout.attach``) the draw is its ``take``: consecutive streams, one per mask."""
         n = len(shapes)
         arg, one = ("keep_masks", "a keep-mask") if n > 1 else ("keep_mask", "keep_mask")
         if given is not None:
@@ -173,8 +174,10 @@ class HipTrainModule(CountedModule):
                 if tuple(k.shape) != shape or k.device != dev:
                     raise ValueError(f"{one} must have shape {shape} on {dev}, got {tuple(k.shape)} on {k.device}")
             return tuple(aligned((k != 0).contiguous().view(torch.uint8)) for k in given)
+        if p > 0.0 and self._keep_mask_rng is not None:
+            return self._keep_mask_rng.take(shapes, p, dev)
         if p > 0.0:
-            draws = [(n,) + shapes[0]] if stacked else shapes
+            draws =[(n,) + shapes[0]] if stacked else shapes
             with guard(dev):
                 ks = [torch.bernoulli(torch.full(s, 1.0 - p, dtype=torch.float32, device=dev)).to(torch.uint8) for s in draws]
             return tuple(ks[0]) if stacked else tuple(ks)

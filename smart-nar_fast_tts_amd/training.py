@@ -9,8 +9,10 @@
 The six submodules carry the reference's names in the reference's order (``stacks.TxtEncoder``, ``adaptor.VarianceAdaptor``,
 ``stacks.MelEncoder``, ``stacks.MelDecoder``, ``sublayers.MelLinear``, ``postnet.PostNet``), so ``state_dict()`` is a reference
 checkpoint's ``"model"`` entry, key for key, and what ``save_checkpoint`` writes loads into the inference class
-``model.FastSpeech2Align`` through ``checkpoint.load_checkpoint``.  The only torch kernels on the data path are autograd's fan-in adds:
-two at ``mel`` (the mel loss, the PostNet and the residual meet there), those at ``src_output`` and those inside the parts."""
+``model.FastSpeech2Align`` through ``checkpoint.load_checkpoint``.  With a keep-mask generator attached (``dropout.attach(model,
+dropout.KeepMaskRNG(seed))``: every dropout mask of a step drawn by one HIP launch) the only torch kernels on the data path are
+autograd's fan-in adds: two at ``mel`` (the mel loss, the PostNet and the residual meet there), those at ``src_output`` and those
+inside the parts.  Without one, each mask is drawn with ``torch.bernoulli`` (three torch kernels per mask)."""
 from __future__ import annotations
 
 import os
@@ -96,7 +98,16 @@ class FastSpeech2Align(torch.nn.Module):
     than ``max_seq_len`` (the aligner would cut its maps; the reference's own forward breaks there: shorten the batch or run
     ``eval()``).
 
-    ``launches`` / ``last_launches`` sum the parts' counters and the residual's."""
+    With a ``dropout.KeepMaskRNG`` attached (``dropout.attach``), a ``train()`` forward calls its ``next_call()`` and, when
+    ``max_mel_len`` is given, draws every mask of the step in one ``ns_km_draw`` (``_step_masks`` lists them in the order the forward
+    consumes them); the layers then take views of that arena.  ``prefetch_keep_masks = False`` lets each layer make its own draw: the
+    same bits.  Explicit ``keep_masks`` still override, part by part.
+
+    ``launches`` / ``last_launches`` sum the parts' counters, the residual's and the generator's draws."""
+
+    TAKES_KEEP_MASK_RNG = True   # dropout.attach() sets the generator here as well
+    _keep_mask_rng = None
+    prefetch_keep_masks = True   # False: every layer makes its own ns_km_draw (the same bits; the tests compare the two)
 
     def __init__(self, preprocess_config, model_config):
         super().__init__()
@@ -133,6 +144,46 @@ class FastSpeech2Align(torch.nn.Module):
         return {which: self.book.last.get(which, 0) + sum(m.last_launches.get(which, 0) for m in self._counted())
                 + sum(s.last_launches[which] for s in self._stacks()) for which in ("forward", "backward")}
 
+    def _step_masks(self, km, B, L, T_mel, T):
+        """Every ``(shape, p)`` the attached generator will be asked for in this forward, in the order the forward consumes them:
+        the text encoder layer by layer (attention, feed-forward), the Prenet, the aligner's layers, the predictors in the order
+        the feature levels run them (k1, k2 each), the decoder's layers, the PostNet's.  ``L`` phonemes, ``T_mel`` frames of the
+        reference mel and ``T`` regulated frames, each cut as its stack cuts it; a part whose masks ``km`` supplies, or that is in
+        ``eval()`` or has no dropout, asks for none.  Shapes come from the arguments alone: no host read."""
+        entries = []
+
+        def site(m, p, *shapes):
+            if m.training and p > 0.0:
+                entries.extend((s, p) for s in shapes)
+
+        def stack(s, rows, key):
+            if km.get(key) is None:
+                for layer in s.layer_stack:
+                    attn = getattr(layer, s._attn)
+                    site(attn, attn.p_drop, (B, rows, s.d_model))
+                    site(layer.pos_ffn, layer.pos_ffn.p_drop, (B, rows, s.d_model))
+
+        cut = lambda s, rows: min(rows, s.max_seq_len) if s.training else rows  # noqa: E731  (the train() branch of a stack slices)
+        stack(self.txt_encoder, L, "txt_encoder")
+        T_mel = cut(self.mel_encoder, T_mel)
+        if km.get("prenet") is None:
+            site(self.mel_encoder.prenet, self.mel_encoder.prenet.p_drop, (B, T_mel, Prenet.D))
+        stack(self.mel_encoder, T_mel, "mel_encoder")
+        va, vk = self.variance_adaptor, km.get("variance_adaptor") or {}
+        rows = {"phoneme_level": L, "frame_level": T}
+        order = [("duration", va.duration_predictor, L)]
+        for level in ("phoneme_level", "frame_level"):
+            order += [(n, p, rows[level]) for n, p, lv in (("pitch", va.pitch_predictor, va.pitch_feature_level),
+                                                         ("energy", va.energy_predictor, va.energy_feature_level)) if lv == level]
+        for name, pred, r in order:
+            if vk.get(name) is None:
+                site(pred, pred.dropout, *[(B, r, pred.filter_size)] * 2)
+        T = cut(self.mel_decoder, T)
+        stack(self.mel_decoder, T, "mel_decoder")
+        if km.get("postnet") is None:
+            site(self.postnet, self.postnet.dropout, *[(B, T, c) for c in self.postnet.channels[1:]])
+        return entries
+
     def forward(self, speakers, texts, src_lens, max_src_len, mels=None, mel_lens=None, max_mel_len=None, p_targets=None, e_targets=None,
                 p_control=1.0, e_control=1.0, keep_masks=None):
         if mel_lens is None or mels is None:
@@ -151,6 +202,12 @@ class FastSpeech2Align(torch.nn.Module):
         self.book.begin()
         for m in self._counted():
             m.last_launches = {}
+        rng = self._keep_mask_rng if self.training else None
+        if rng is not None:  # one draw counter per step; all its masks in one launch where the shapes are known without a host read
+            drawn = rng.launches
+            rng.next_call()
+            if self.prefetch_keep_masks and max_mel_len is not None:
+                rng.prefetch(self._step_masks(km, texts.shape[0], texts.shape[1], mels.shape[1], int(max_mel_len)), texts.device)
 
         src_masks = _mask_from_lengths(src_lens, max_src_len)
         mel_masks = _mask_from_lengths(mel_lens, max_mel_len)
@@ -170,6 +227,8 @@ class FastSpeech2Align(torch.nn.Module):
         output = self.mel_linear(output)
 
         postnet_output = add_residual(self.postnet(output, keep_masks=km.get("postnet")), output, book=self.book)
+        if rng is not None:
+            self.book.done(0, "forward", "ns_km_draw", n=rng.launches - drawn)
 
         return (output, postnet_output, p_predictions, e_predictions, log_d_predictions, d_rounded, src_masks, mel_masks, src_lens, mel_lens_out,
                 tgt_alignment, d_targets)
@@ -208,11 +267,15 @@ def train_step(model, loss, optimizer, batch, step, grad_acc_step, grad_clip_thr
     return losses
 
 
-def save_checkpoint(model, optimizer, path):
+def save_checkpoint(model, optimizer, path, rng=None):
     """train.py:150-159: ``{"model": model.state_dict(), "optimizer": optimizer._optimizer.state_dict()}`` written to ``path``.  The
     schedule's learning rate is a numpy float64 (model/optimizer.py:20 computes it with ``np.power``); it is written as the Python float
     of the same value, so that ``torch.load(..., weights_only=True)`` — what ``checkpoint.load_checkpoint`` and ``get_model`` use —
-    takes the file."""
+    takes the file.
+
+    ``rng`` (an extension; a ``dropout.KeepMaskRNG``) adds a third key, ``"keep_mask_rng"``: its ``state_dict()``, plain ints.  A run
+    resumed with ``rng.load_state_dict(torch.load(path, weights_only=True)["keep_mask_rng"])`` draws the masks the saved run would
+    have drawn next.  Without ``rng`` the file has the two keys it always had."""
     def plain(v):
         if isinstance(v, (list, tuple)):
             return type(v)(plain(x) for x in v)
@@ -220,4 +283,7 @@ def save_checkpoint(model, optimizer, path):
 
     opt = optimizer._optimizer.state_dict()
     opt["param_groups"] = [{k: plain(v) for k, v in g.items()} for g in opt["param_groups"]]
-    torch.save({"model": model.state_dict(), "optimizer": opt}, path)
+    ckpt = {"model": model.state_dict(), "optimizer": opt}
+    if rng is not None:
+        ckpt["keep_mask_rng"] = rng.state_dict()
+    torch.save(ckpt, path)

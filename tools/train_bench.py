@@ -40,13 +40,15 @@ def to_device(batch):
     return tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() if isinstance(a, np.ndarray) else a for a in batch)
 
 
-def bench_step(name, pcfg, cfg, sd, batch, steps, warmup):
-    from smart_nar_fast_tts_amd import optim, training
+def bench_step(name, pcfg, cfg, sd, batch, steps, warmup, rng="torch"):
+    from smart_nar_fast_tts_amd import dropout, optim, training
     from smart_nar_fast_tts_amd.loss import FastSpeech2TrainingLoss
 
     m = training.FastSpeech2Align(pcfg, cfg)
     m.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}, strict=True)
     m = m.cuda().train()
+    if rng == "philox":  # every mask of a step from one ns_km_draw (dropout.KeepMaskRNG); "torch": torch.bernoulli, mask by mask
+        dropout.attach(m, dropout.KeepMaskRNG(1234))
     loss = FastSpeech2TrainingLoss(pcfg, cfg)
     ocfg = {"optimizer": dict(betas=[0.9, 0.98], eps=1e-9, weight_decay=0.0, warm_up_step=4000, anneal_steps=[], anneal_rate=1.0)}
     opt = optim.ScheduledOptim(m, ocfg, cfg, 0)
@@ -116,19 +118,22 @@ def main():
     common_args(ap, 10, 2)  # (at least two warm-up steps: the host reads are counted in the second)
     ap.add_argument("--report")
     ap.add_argument("--bench-note")
+    ap.add_argument("--rng", choices=("torch", "philox"), default="torch",
+                    help="who draws the dropout keep-masks: torch.bernoulli per mask (the default), or dropout.KeepMaskRNG, one HIP launch per step")
     args = ap.parse_args()
     cfg = wl.model_config("ljspeech")
     sd = wl.synth_state_dict(cfg, seed=0)
     sd.update(wl.synth_aligner_state_dict(cfg, seed=0))
     meta, _ = load_golden("train_align_tiny")
     results = {"steps": [bench_step("config 2: 16 x 128 phonemes, 1000 frames, ljspeech config", wl.preprocess_config(), cfg, sd, config2_batch(cfg),
-                                    args.steps, args.warmup),
+                                    args.steps, args.warmup, args.rng),
                          bench_step("test shape: 2 x 7 phonemes, 20 frames, 1 + 4 layers", *tc.fixture_config(meta), tc.fixture_state_dict(meta),
-                                    tc.fixture_batch(meta), args.steps, args.warmup)],
+                                    tc.fixture_batch(meta), args.steps, args.warmup, args.rng)],
                "mel_head": bench_mel_head(args.steps, args.warmup)}
     lines = ["# One training step of the trainable FastSpeech2Align", "",
              f"One MI355X, one run, p50 of {args.steps} steps after {args.warmup} warm-up steps, device events around each stage's enqueue.",
-             "Dropout as configured (masks drawn on the device).  Nothing about speed is asserted.", ""]
+             "Dropout as configured (masks drawn on the device" + (": one ns_km_draw per step, --rng philox" if args.rng == "philox" else "")
+             + ").  Nothing about speed is asserted.", ""]
     for r in results["steps"]:
         lines += [f"## {r['name']} ({r['parameters'] / 1e6:.1f} M trainable parameters)", "", "| stage | p50 ms (min - max) | launches | host reads |", "|---|---|---|---|"]
         for s in STAGES:

@@ -530,7 +530,7 @@ class FastSpeech2Align:
     def profile_slots(self, slots=(0, 1, 2), keep: bool = False):
         """Time exactly these launch groups (include/nar_fs2.h NS_PROFILE_SLOT); () switches the hook off.  ``keep``: do not
         discard what was recorded so far (sampling: time every n-th forward of a region, read once at its end)."""
-        mask = 0x10000 if keep else 0
+        mask = _lib.NS["NS_PROFILE_KEEP"] if keep else 0
         for i in slots:
             mask |= 2 << int(i)
         _lib.check(self._lib.ns_profile_enable(self._h, mask), "ns_profile_enable")

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from ._train import guard
 
-CHUNK = 4096  # NS_OPT_CHUNK of include/nar_fs2.h (tests/test_optim_host.py holds the two together)
+CHUNK = _lib.NS["NS_OPT_CHUNK"]
 
 
 def _check_params(params):
@@ -101,11 +101,11 @@ class _Table:
     def grad_norm(self, max_norm: float):
         with guard(self.device):
             _lib.check(self.lib.ns_opt_grad_norm(C.byref(self.plan), _lib.ptr(self.table), self.table.numel(), float(max_norm), _lib.ptr(self.ws),
-                                                 self.ws.numel(), _lib.ptr(self.record), self.st()), "ns_opt_grad_norm")
+                                                 self.ws.numel(), _lib.ptr(self.record, _lib.NsOptRecord), self.st()), "ns_opt_grad_norm")
 
     def scale(self):
         with guard(self.device):
-            _lib.check(self.lib.ns_opt_scale_grads(C.byref(self.plan), _lib.ptr(self.table), self.table.numel(), _lib.ptr(self.record), self.st()),
+            _lib.check(self.lib.ns_opt_scale_grads(C.byref(self.plan), _lib.ptr(self.table), self.table.numel(), _lib.ptr(self.record, _lib.NsOptRecord), self.st()),
                        "ns_opt_scale_grads")
 
     def zero(self):
@@ -242,7 +242,7 @@ class Adam:
             t.grad_norm(grad_clip_thresh)
         with guard(t.device):
             _lib.check(t.lib.ns_opt_adam_step(C.byref(t.plan), _lib.ptr(t.table), t.table.numel(), C.byref(h), _lib.ptr(self._exp_avg),
-                                              _lib.ptr(self._exp_avg_sq), self._exp_avg.numel(), _lib.ptr(t.record), t.st()), "ns_opt_adam_step")
+                                              _lib.ptr(self._exp_avg_sq), self._exp_avg.numel(), _lib.ptr(t.record, _lib.NsOptRecord), t.st()), "ns_opt_adam_step")
         return t.total_norm if grad_clip_thresh is not None else None
 
     def zero_grad(self, set_to_none: bool = False):

@@ -28,6 +28,25 @@ class _ConvNorm(torch.nn.Module):  # the reference's ConvNorm wrapper (transform
         self.conv = torch.nn.Conv1d(cin, cout, kernel_size=k, padding=(k - 1) // 2)
 
 
+class _ByLayer:
+    """Lets the training core, which fills a block by ``setattr(block, field, address)``, write the nested blocks of the C ABI:
+    ``block.gamma2 = a`` is ``block.layer[2].gamma = a``."""
+
+    def __setattr__(self, name, address):
+        if name[-1:].isdigit():
+            setattr(self.layer[int(name[-1])], name[:-1], address)
+        else:
+            super().__setattr__(name, address)
+
+
+class _Weights(_ByLayer, _lib.NsPnWeights):
+    pass
+
+
+class _Grads(_ByLayer, _lib.NsPnGrads):
+    pass
+
+
 class PostNet(HipTrainModule):
     """Drop-in for ``PostNet(n_mel_channels, postnet_embedding_dim, postnet_kernel_size, postnet_n_convolutions)``: the same parameter
     and buffer names, the same ``forward(x [B, T, n_mel]) -> [B, T, n_mel]`` without the residual.
@@ -51,7 +70,7 @@ class PostNet(HipTrainModule):
     ``n_mel_channels`` not a multiple of 16 in [16, 128], an even kernel size or one above 9, fewer than 2 or more than 5 convolutions."""
 
     ABI, INPUT = "ns_pn", "x"
-    WEIGHTS, GRADS = _lib.NsPnWeights, _lib.NsPnGrads
+    WEIGHTS, GRADS = _Weights, _Grads
     WORKSPACES = WorkspaceCache("ns_pn_ws_bytes", ("B", "T", "n_mel", "emb", "K", "n"))
 
     def __init__(self, n_mel_channels=80, postnet_embedding_dim=512, postnet_kernel_size=5, postnet_n_convolutions=5, dropout=0.5):
@@ -75,7 +94,7 @@ class PostNet(HipTrainModule):
             torch.nn.Sequential(_ConvNorm(chans[i], chans[i + 1], k), torch.nn.BatchNorm1d(chans[i + 1])) for i in range(n))
         self.channels = chans
         self.PARAM_NAMES = tuple(f"convolutions.{i}.{s}" for i in range(n) for s in ("0.conv.weight", "0.conv.bias", "1.weight", "1.bias"))
-        self.FIELDS = tuple(f"{p}{i}" for i in range(n) for p in _lib.PN_PARAMS)  # order of ns_pn_grads after dx
+        self.FIELDS = tuple(f"{p}{i}" for i in range(n) for p in _lib.PN_PARAMS)  # order of ns_pn_grads after dx; p{i} is layer[i].p (_ByLayer)
 
     def _marshal(self, x, keep_masks):
         call = self._begin(x, self.n_mel)

@@ -14,7 +14,7 @@ from . import _lib
 from ._handle import StreamWorkspaces
 from ._train import guard
 
-SORT_CAPACITY = 8192  # NS_VT_SORT_CAPACITY of include/nar_fs2.h (tests/test_variance_targets_host.py holds the two together)
+SORT_CAPACITY = _lib.NS["NS_VT_SORT_CAPACITY"]
 
 
 class VarianceTargets:
@@ -50,7 +50,7 @@ class VarianceTargets:
     def _state_on(self, dev) -> torch.Tensor:
         if self._state is None:
             self._state = torch.empty(10, dtype=torch.float64, device=dev)
-            _lib.check(self._lib.ns_vt_state_init(_lib.ptr(self._state), _lib.stream_ptr(dev)), "ns_vt_state_init")
+            _lib.check(self._lib.ns_vt_state_init(_lib.ptr(self._state, _lib.NsVtState), _lib.stream_ptr(dev)), "ns_vt_state_init")
         elif self._state.device != dev:
             raise RuntimeError(f"the running statistics live on {self._state.device}, this batch on {dev}")
         return self._state
@@ -130,7 +130,7 @@ class VarianceTargets:
             _lib.check(self._lib.ns_vt_targets(C.byref(a), _lib.ptr(ws), ws.numel(), st), "ns_vt_targets")
             if fit:
                 state = self._state_on(dev)
-                _lib.check(self._lib.ns_vt_fit(C.byref(a), _lib.ptr(state), _lib.ptr(ws), ws.numel(), st), "ns_vt_fit")
+                _lib.check(self._lib.ns_vt_fit(C.byref(a), _lib.ptr(state, _lib.NsVtState), _lib.ptr(ws), ws.numel(), st), "ns_vt_fit")
         return pt, et, frame_lens, valid
 
     # ---- pass 2 --------------------------------------------------------------------------------
@@ -172,7 +172,7 @@ class VarianceTargets:
             a.valid = valid.data_ptr() if valid is not None else None
             state = self._state_on(dev)
             ws = self.workspace(dev, self._lib.ns_vt_ws_bytes(B, L, T))
-            _lib.check(self._lib.ns_vt_normalize(C.byref(a), _lib.ptr(state), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "ns_vt_normalize")
+            _lib.check(self._lib.ns_vt_normalize(C.byref(a), _lib.ptr(state, _lib.NsVtState), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "ns_vt_normalize")
         return pitch_targets, energy_targets
 
     # ---- the statistics --------------------------------------------------------------------------

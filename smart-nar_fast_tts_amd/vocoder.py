@@ -31,10 +31,7 @@ class AttrDict(dict):
         self.__dict__ = self
 
 
-class NsVocConfig(C.Structure):
-    _fields_ = [("n_mel", C.c_int32), ("initial_channel", C.c_int32), ("n_up", C.c_int32), ("up_rates", C.c_int32 * 4),
-                ("up_kernels", C.c_int32 * 4), ("n_rb", C.c_int32), ("rb_kernels", C.c_int32 * 4),
-                ("rb_dilations", (C.c_int32 * 4) * 4), ("resblock", C.c_int32)]
+NsVocConfig = _lib.STRUCTS["ns_voc_config"]
 
 
 def config_struct(h) -> NsVocConfig:
@@ -174,9 +171,9 @@ class Generator(DeviceModule):
         if B == 0 or T == 0:
             return wav
         if mels.transpose(1, 2).is_contiguous() and mels.data_ptr() % 16 == 0:
-            layout, src = 1, mels  # a transpose(1, 2) view of a [B, T, n_mel] tensor: read in place
+            layout, src = _lib.NS["NS_VOC_MEL_TIME_MAJOR"], mels  # a transpose(1, 2) view of a [B, T, n_mel] tensor: read in place
         else:
-            layout, src = 0, mels.contiguous()
+            layout, src = _lib.NS["NS_VOC_MEL_CHANNEL_MAJOR"], mels.contiguous()
         stream = torch.cuda.current_stream(mels.device).cuda_stream
         nbytes = self.ws_bytes(B, T)
         ws = self._ws.take(self._device, nbytes, stream)

@@ -3,6 +3,7 @@ host-side validation (config / state-dict errors) and the workload definition.  
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -28,13 +29,134 @@ def test_header_symbols_are_bound_and_exported(lib):
         assert hasattr(so, name), name
 
 
-def test_config_struct_matches_header(lib):
+def test_every_prototype_is_bound_with_its_parameter_count(lib):
     L, so = lib
     text = open(os.path.join(ROOT, "include", "nar_fs2.h")).read()
-    body = re.search(r"typedef struct ns_config \{(.*?)\} ns_config;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [f.strip() for decl in re.findall(r"int32_t ([^;]+);", body) for f in decl.split(",")]
-    assert fields == [f for f, _ in L.NsConfig._fields_]
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    protos = re.findall(r"\b(ns_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
+    assert len(protos) == len(L.SIGNATURES) >= 237
+    for name, params in protos:
+        count = 0 if params.strip() == "void" else params.count(",") + 1
+        assert len(L.SIGNATURES[name][1]) == count, name
+        assert list(getattr(so, name).argtypes) == L.SIGNATURES[name][1] and getattr(so, name).restype is L.SIGNATURES[name][0], name
+
+
+def test_every_abi_version_of_the_header_is_what_the_library_returns(lib):
+    L, so = lib
+    versions = {k: v for k, v in L.NS.items() if k.endswith("ABI_VERSION")}
+    assert len(versions) >= 18 and versions["NS_ABI_VERSION"] == 6
+    for macro, value in versions.items():  # NS_PG_ABI_VERSION -> ns_pg_abi_version()
+        assert getattr(so, macro.lower())() == value, macro
+
+
+def test_every_struct_has_the_layout_the_c_compiler_gives_it(lib, tmp_path):
+    """sizeof and every top-level offsetof of every struct the binding derives from the header, printed by a strict-C99 program that
+    includes the header, against ctypes' view of the derived Structure.  Replaces test_config_struct_matches_header (field names of
+    ns_config alone), which this subsumes: a field out of order, of another width or in another struct moves an offset here."""
+    L, so = lib
+    assert len(L.STRUCTS) >= 36 and {"ns_config", "ns_voc_config", "ns_pn_weights", "ns_km_mask"} <= set(L.STRUCTS)
+    lines = ['#include <stdio.h>', '#include "nar_fs2.h"', "int main(void) {"]
+    want = []
+    for name, cls in L.STRUCTS.items():
+        lines.append(f'  printf("{name} %lu\\n", (unsigned long)sizeof({name}));')
+        want.append(f"{name} {C.sizeof(cls)}")
+        for field, _ in cls._fields_:
+            lines.append(f'  printf("{name}.{field} %lu\\n", (unsigned long)offsetof({name}, {field}));')
+            want.append(f"{name}.{field} {getattr(cls, field).offset}")
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}"]) + "\n")
+    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "layout")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.split("\n")[:-1] == want, [(a, b) for a, b in zip(r.stdout.split("\n"), want) if a != b]
+    # the nested PostNet blocks: five layers of seven / four pointers, as csrc/postnetgrad.hip indexes them
+    assert [f for f, _ in L.NsConfig._fields_][:3] == ["n_vocab", "max_seq_len", "d_enc"] and C.sizeof(L.NsConfig) == 24 * 4
+    w, g = L.NsPnWeights(), L.NsPnGrads()
+    assert len(w.layer) == len(g.layer) == L.NS["NS_PN_MAX_LAYERS"] == 5 and C.sizeof(w) == 5 * 7 * 8 and C.sizeof(g) == (5 * 4 + 1) * 8
+
+
+_P, _I32 = C.c_void_p, C.c_int32
+ACCEPTED = (  # header text -> what it must give, exactly
+    ("typedef struct s { int32_t B, S; } s;", "s", [("B", _I32), ("S", _I32)]),
+    ("typedef struct s {\n  float *w, *b;  /* two\n pointers */\n  const int64_t* n;\n} s;", "s", [("w", _P), ("b", _P), ("n", _P)]),
+    ("#define NS_N 3\ntypedef struct s { void* attn[NS_N]; double c[2]; int32_t d[4][NS_N]; } s;", "s",
+     [("attn", _P * 3), ("c", C.c_double * 2), ("d", (_I32 * 3) * 4)]),
+    ("int f(const float* const* rows, int32_t out[8], int64_t plan[2][8], size_t n, double x, uint64_t seed, uint32_t* thr);", "f",
+     (C.c_int, [_P, _P, _P, C.c_size_t, C.c_double, C.c_uint64, _P])),
+    ("const char* f(void);", "f", (C.c_char_p, [])),
+    ("typedef struct h h;\nvoid f(h* m, h** out, const char* name, const uint8_t* mask, float p, int64_t n);", "f",
+     (None, [_P, _P, C.c_char_p, _P, C.c_float, C.c_int64])),
+    ("size_t f(int a,\n         int b /* nullable */);  // trailing", "f", (C.c_size_t, [C.c_int, C.c_int])),
+)
+REFUSED = (  # header text, the line the error must name, a word of the reason
+    ("int ok(void);\nint f(void (*cb)(int), int x);", 2, "declaration"),
+    ("typedef struct s {\n  int32_t a;\n  void (*cb)(int);\n} s;", 3, "declaration"),
+    ("\n\ntypedef union u { int32_t a; float b; } u;", 3, "not a struct typedef"),
+    ("typedef struct s {\n  int32_t a;\n  union { int32_t b; float c; } v;\n} s;", 3, "inside braces"),
+    ("typedef struct s {\n  int32_t a;\n  struct { int32_t b; } v;\n} s;", 3, "inside braces"),
+    ("#define NS_A 1\nint f(void);\n#define NS_A 2", 3, "NS_A is defined twice"),
+    ("int f(void);\ntypedef struct s { int32_t a; float a; } s;", 2, "two fields of one name"),
+    ("typedef struct s {\n  int32_t a : 3;\n} s;", 2, "declaration"),
+    ("int f(int a,\n      long b);", 2, "unknown type name 'long'"),
+    ("int f(ns_undeclared* m);", 1, "unknown type name 'ns_undeclared'"),
+    ("typedef struct s {\n  unsigned int a;\n} s;", 2, "declaration"),
+    ("#define NS_A 2\ntypedef struct s {\n  float a[NS_A];\n  float b[NS_B];\n} s;", 4, "array length"),
+    ("#define NS_F(i) (2 << (i))\ntypedef struct s { float a[NS_F]; } s;", 2, "array length"),
+    ("typedef struct s { int32_t a; } s;\nint f(s by_value);", 2, "by value"),
+    ("int f(uint8_t flag);", 1, "by value"),
+    ("int f(int);", 1, "declaration"),
+    ("int f();", 1, "declaration"),
+    ("int f(void);\n\nint f(void);", 3, "prototype"),
+    ("int f(void);\n#if 0\nint g(void);\n#endif", 2, "preprocessor"),
+    ("enum e { A, B };", 1, "not a struct typedef"),
+    ("static inline int f(void) { return 0; }\nint g(void);", 1, "not a struct typedef"),
+    ("int ok(void);\nint f(void)", 2, "without its ';'"),
+)
+
+
+def test_the_header_reader_accepts_its_subset_exactly_and_refuses_the_rest_by_line():
+    from smart_nar_fast_tts_amd._abi import Abi, HeaderError
+
+    for text, name, want in ACCEPTED:  # ctypes caches array and pointer types, so `is` compares them
+        abi = Abi(text, "snippet.h")
+        if isinstance(want, list):
+            got = abi.structs[name]._fields_
+            assert [n for n, _ in got] == [n for n, _ in want] and all(a is b for (_, a), (_, b) in zip(got, want)), (text, got)
+        else:
+            res, args = abi.signatures[name]
+            assert res is want[0] and len(args) == len(want[1]) and all(a is b for a, b in zip(args, want[1])), (text, res, args)
+    # a pointer to a struct with a body is typed, as parameter; nested structs and constants
+    abi = Abi("#define NS_L 2\n#define NS_K 0x10\n#define NS_F(i) (1 << (i))\n#define NS_S \"x\"\ntypedef struct in { float *w, *b; } in;\n"
+              "typedef struct out { in layer[NS_L]; float* dx; } out;\nint f(const out* o, out** many, in rows[4]);", "snippet.h")
+    assert abi.constants == {"NS_L": 2, "NS_K": 16}
+    assert abi.structs["out"]._fields_[0] == ("layer", abi.structs["in"] * 2) and C.sizeof(abi.structs["out"]) == 40
+    assert abi.signatures["f"] == (C.c_int, [C.POINTER(abi.structs["out"]), _P, _P]) and abi.signatures["f"][1][0] is C.POINTER(abi.structs["out"])
+    assert [n for n in Abi("// a /* b\nint f(void);\n/* c // */ int g(void);", "snippet.h").signatures] == ["f", "g"]  # whichever comment opens first
+    for text, line, why in REFUSED:
+        with pytest.raises(HeaderError) as e:
+            Abi(text, "snippet.h")
+        assert str(e.value).startswith(f"snippet.h:{line}: ") and why in str(e.value), (text, str(e.value))
+
+
+def test_a_missing_header_is_an_import_error_naming_the_path(tmp_path, monkeypatch):
+    """_lib.py finds the header relative to itself: a copy of the two modules with no include/ beside their package says where it looked."""
+    import importlib
+    import shutil
+    import sys
+
+    pkg = tmp_path / "ns_without_header"
+    pkg.mkdir()
+    for f in ("_lib.py", "_abi.py"):
+        shutil.copy(os.path.join(ROOT, "smart-nar_fast_tts_amd", f), pkg / f)
+    (pkg / "__init__.py").write_text("")
+    monkeypatch.syspath_prepend(str(tmp_path))
+    try:
+        with pytest.raises(ImportError, match=re.escape(str(tmp_path / "include" / "nar_fs2.h"))):
+            importlib.import_module("ns_without_header._lib")
+    finally:
+        for name in [n for n in sys.modules if n.startswith("ns_without_header")]:
+            del sys.modules[name]
 
 
 def _cfg(L, **over):

@@ -452,7 +452,7 @@ def test_unwanted_gradients_are_never_written(so):
         shapes = [call.x.shape] + [p.shape for p in call.params]
         for wanted in ({"dx"}, {"w2", "beta1"}, set(names)):
             bufs = {k: torch.full((int(np.prod(s)) + 16,), float("nan"), device="cuda") for k, s in zip(names, shapes)}
-            d = L.NsPnGrads()
+            d = m.GRADS()  # ns_pn_grads, which takes d.w2 for d.layer[2].w
             for k in wanted:
                 setattr(d, k, bufs[k].data_ptr())
             ws = m.WORKSPACES.get(lib, call.shape, call.device)

@@ -60,7 +60,7 @@ def run_cabi(batch, p_level, e_level, stream=None, dirty=None, state=None, rows=
         ws = torch.full((need,), 0xAB if dirty else 0, dtype=torch.uint8, device="cuda")
         if state is None:
             state = torch.full((10,), float("nan"), dtype=torch.float64, device="cuda")
-            _lib.check(lib.ns_vt_state_init(_lib.ptr(state), C.c_void_p(stream.cuda_stream)), "ns_vt_state_init")
+            _lib.check(lib.ns_vt_state_init(_lib.ptr(state, _lib.NsVtState), C.c_void_p(stream.cuda_stream)), "ns_vt_state_init")
         a = _lib.NsVtArgs()
         a.B, a.L, a.T, a.pitch_frame_level, a.energy_frame_level, a.pitch_normalization, a.energy_normalization = B, L, T, int(p_frame), int(e_frame), 1, 1
         a.durations_stride = dpad.shape[1]
@@ -69,9 +69,9 @@ def run_cabi(batch, p_level, e_level, stream=None, dirty=None, state=None, rows=
         st = C.c_void_p(stream.cuda_stream)
         _lib.check(lib.ns_vt_targets(C.byref(a), _lib.ptr(ws), need, st), "ns_vt_targets")
         raw = (pt.clone(), et.clone())
-        _lib.check(lib.ns_vt_fit(C.byref(a), _lib.ptr(state), _lib.ptr(ws), need, st), "ns_vt_fit")
+        _lib.check(lib.ns_vt_fit(C.byref(a), _lib.ptr(state, _lib.NsVtState), _lib.ptr(ws), need, st), "ns_vt_fit")
         if normalize:
-            _lib.check(lib.ns_vt_normalize(C.byref(a), _lib.ptr(state), _lib.ptr(ws), need, st), "ns_vt_normalize")
+            _lib.check(lib.ns_vt_normalize(C.byref(a), _lib.ptr(state, _lib.NsVtState), _lib.ptr(ws), need, st), "ns_vt_normalize")
     stream.synchronize()
     return {"pitch_raw": raw[0].cpu().numpy(), "energy_raw": raw[1].cpu().numpy(), "pitch_norm": pt.cpu().numpy(), "energy_norm": et.cpu().numpy(),
             "frame_lens": fl.cpu().numpy(), "valid": valid.cpu().numpy(), "state": state.cpu().numpy(), "state_dev": state}

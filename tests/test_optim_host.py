@@ -246,6 +246,7 @@ def test_every_refusal_is_reached_without_a_gpu():
 
     def call(name, plan=good, table=table, table_bytes=None, ws=ws, ws_bytes=None, rec=rec, h=None, m=m, v=v, floats=None, max_norm=1.0):
         pp = C.byref(plan) if plan is not None else None
+        rec = C.cast(rec, C.POINTER(_lib.NsOptRecord)) if rec is not None else None  # the header types it: ns_opt_record*
         tb = good.table_bytes if table_bytes is None else table_bytes
         if name == "ns_opt_grad_norm":
             return lib.ns_opt_grad_norm(pp, table, tb, max_norm, ws, good.ws_bytes if ws_bytes is None else ws_bytes, rec, None)

@@ -157,9 +157,10 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
     ok_shape = dict(B=2, T=8, n_mel=80, emb=512, K=5, n=3)
 
     def weights(**over):
-        w = L_.NsPnWeights()
-        for i, (name, _) in enumerate(L_.NsPnWeights._fields_):
-            setattr(w, name, over.get(name, 0x100000 + 0x10000 * i))
+        w, names = L_.NsPnWeights(), L_.PN_PARAMS + L_.PN_BUFFERS  # over: gamma1 = layer[1].gamma
+        for i in range(len(w.layer)):
+            for j, name in enumerate(names):
+                setattr(w.layer[i], name, over.get(f"{name}{i}", 0x100000 + 0x10000 * (i * len(names) + j)))
         return w
 
     def keeps(*addr):
@@ -206,7 +207,7 @@ def test_every_refusal_precedes_the_first_hip_call(lib):
     assert bwd(g=0) != 0 and "null argument" in err()
     assert bwd(g=0xD000004) != 0 and "16-byte aligned" in err()
     d = L_.NsPnGrads()
-    d.gamma1 = 0x1000004
+    d.layer[1].gamma = 0x1000004
     assert bwd(grads=d) != 0 and "every gradient must be 16-byte aligned" in err()
     assert bwd() == 0 and so.ns_pn_last_launches() == 0  # nothing wanted: nothing launched, no HIP call
     assert bwd(p=0.5, keep=three) == 0 and so.ns_pn_last_launches() == 0

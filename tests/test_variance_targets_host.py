@@ -222,6 +222,7 @@ def test_every_refusal_is_reached_without_a_gpu():
              "ns_vt_normalize": lambda a, w, n, s: lib.ns_vt_normalize(a, s, w, n, None)}
 
     def refused(which, a, match, ws=ws, n=need, state=state):
+        state = C.cast(state, C.POINTER(_lib.NsVtState)) if state is not None else None  # the header types it: ns_vt_state*
         for name in which:
             rc = calls[name](C.byref(a) if a is not None else None, ws, n, state)
             msg = lib.ns_last_error().decode()

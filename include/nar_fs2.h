@@ -1495,6 +1495,97 @@ int ns_km_op_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
  * would refuse, a slot out of place), an arena shorter than the plan's. */
 int ns_km_host_draw(const void* table_host, int n_masks, uint64_t seed, uint64_t call, void* arena_host, size_t arena_bytes);
 
+/* ==== Device-resident training set: a reference batch from one gather launch ================================
+ * Handle-less; nothing above changes (every other ABI version stays as it is).  The store is packed, lives on the device and is only
+ * read after its upload: mel [sum T_i, n_mel] fp32 (utterance i owns the rows [mel_off[i], mel_off[i + 1])), pitch and energy fp32 and
+ * text int32 as ragged 1-D arrays whose slots each start at a multiple of four elements (16 bytes; ns_ds_plan pads them), speaker [N]
+ * int32, one int64 offset table [N + 1] and one int32 length vector [N] per ragged array.  One launch turns the utterances
+ * order[first .. first + B) into the reference's collated batch (dataset.py:88-118 and the 11-tuple branch of utils/tools.py:18-54):
+ *   mels [B, Tmax, n_mel] fp32, pitches [B, Pmax] fp32, energies [B, Emax] fp32, texts [B, Lmax] int64, speakers / src_lens /
+ *   mel_lens [B] int64.
+ * EVERY element of every output is written: a valid element is the store's, bit for bit (-0.0 and denormals included), padding is
+ * +0.0, or 0 in texts.  Mel rows move as 16-byte groups, the rest as dwords.  No atomic, no workspace, no host read; the grid is
+ * capped and loops; an utterance may appear twice in a batch. */
+#define NS_DS_ABI_VERSION 1 /* what ns_ds_abi_version() returns */
+#define NS_DS_GRID_CAP 2048 /* workgroups of one ns_ds_gather at most (256 threads, one output group each a turn); they loop beyond */
+int ns_ds_abi_version(void);
+/* Kernel launches the calling thread's last ns_ds_gather / ns_ds_op_gather enqueued (1, or 0 after a refusal; ns_ds_plan and
+ * ns_ds_host_gather set 0). */
+int ns_ds_last_launches(void);
+/* The four length vectors [N], always HOST memory: what every refusal about a batch's maxima is judged from. */
+typedef struct ns_ds_lens {
+  const int32_t* text;   /* L_i, phonemes */
+  const int32_t* mel;    /* T_i, frames */
+  const int32_t* pitch;  /* elements of utterance i's pitch (T_i or L_i: the caller's feature level) */
+  const int32_t* energy; /* likewise */
+} ns_ds_lens;
+/* The four offset tables [N + 1], int64: mel in rows, the others in elements.  Row N is the array's size. */
+typedef struct ns_ds_offsets {
+  int64_t* mel;
+  int64_t* pitch;
+  int64_t* energy;
+  int64_t* text;
+} ns_ds_offsets;
+/* The store.  Every pointer is device memory for ns_ds_gather / ns_ds_op_gather and host memory for ns_ds_host_gather. */
+typedef struct ns_ds_store {
+  const float* mel;       /* [mel_rows, n_mel], 16-byte aligned */
+  const float* pitch;     /* [pitch_elems], 16-byte aligned */
+  const float* energy;    /* [energy_elems], 16-byte aligned */
+  const int32_t* text;    /* [text_elems], 16-byte aligned */
+  const int32_t* speaker; /* [N] */
+  const int64_t* mel_off; /* [N + 1] each, 8-byte aligned: what ns_ds_plan wrote */
+  const int64_t* pitch_off;
+  const int64_t* energy_off;
+  const int64_t* text_off;
+  const int32_t* text_len; /* [N] each: copies of the ns_ds_lens vectors in the store's memory */
+  const int32_t* mel_len;
+  const int32_t* pitch_len;
+  const int32_t* energy_len;
+  int64_t mel_rows; /* the sizes ns_ds_plan returned (bytes / 4 n_mel, bytes / 4): no element at or past them is read */
+  int64_t pitch_elems;
+  int64_t energy_elems;
+  int64_t text_elems;
+  int32_t N;
+  int32_t n_mel; /* a multiple of 4 in [4, 128] */
+} ns_ds_store;
+/* The outputs of one batch (the store's memory space); B * Tmax * n_mel and every other output stay below 2^31 elements. */
+typedef struct ns_ds_batch {
+  float* mels;       /* [B, Tmax, n_mel], 16-byte aligned */
+  float* pitches;    /* [B, Pmax] */
+  float* energies;   /* [B, Emax] */
+  int64_t* texts;    /* [B, Lmax], 8-byte aligned as the three below */
+  int64_t* speakers; /* [B] */
+  int64_t* src_lens; /* [B] */
+  int64_t* mel_lens; /* [B] */
+  int32_t B;
+  int32_t Tmax;
+  int32_t Pmax;
+  int32_t Emax;
+  int32_t Lmax;
+} ns_ds_batch;
+/* Pure host logic, no GPU: lays the N utterances out in the order given.  off->mel[i] = sum of the T before i; a slot of the three 1-D
+ * arrays starts where the one before ends, rounded up to a multiple of four elements.  bytes[4] = the byte sizes of the packed mel,
+ * pitch, energy and text arrays (each at least 16).  Nonzero with ns_last_error() on: a null pointer, N < 1, n_mel not a multiple
+ * of 4 or outside [4, 128], a length below 1. */
+int ns_ds_plan(const ns_ds_lens* lens, int N, int n_mel, const ns_ds_offsets* off, uint64_t bytes[4]);
+/* The batch of order[first .. first + B): EXACTLY ONE launch.  order_dev is the device copy of the epoch's order (int32 [order_len]),
+ * order_host the host's; lens are the host's length vectors.  Nonzero with ns_last_error(), before any HIP call, on: a null or
+ * misaligned pointer, n_mel not a multiple of 4 or outside [4, 128], N < 1, B < 1, first < 0 or first + B > order_len, an order entry
+ * outside [0, N), Tmax / Pmax / Emax / Lmax below the batch's own maximum (from lens), an output of 2^31 elements or more.  The
+ * kernel reads the device copies of the tables; it reads no element at or past the store's stated sizes and writes the outputs only,
+ * whatever those tables hold. */
+int ns_ds_gather(const ns_ds_store* store, const ns_ds_lens* lens, const int32_t* order_dev, const int32_t* order_host, int64_t order_len,
+                 int64_t first, const ns_ds_batch* out, void* stream);
+/* The same launch with at most grid_cap workgroups (in [1, NS_DS_GRID_CAP]): a test hook that makes workgroups loop at a tiny shape. */
+int ns_ds_op_gather(const ns_ds_store* store, const ns_ds_lens* lens, const int32_t* order_dev, const int32_t* order_host,
+                    int64_t order_len, int64_t first, const ns_ds_batch* out, int grid_cap, void* stream);
+/* ns_ds_gather on the host (no GPU): store, order_host and out are host memory; the same index arithmetic through the inline function
+ * the kernel compiles.  Refuses what ns_ds_gather refuses (the alignments included: mel rows move as aligned 16-byte groups here too)
+ * and offset tables that are not a plan's: any of the 4 (N + 1) entries that differs from what ns_ds_plan writes for lens, or a stated
+ * size below the table's last row. */
+int ns_ds_host_gather(const ns_ds_store* store, const ns_ds_lens* lens, const int32_t* order_host, int64_t order_len, int64_t first,
+                      const ns_ds_batch* out);
+
 #ifdef __cplusplus
 }
 #endif

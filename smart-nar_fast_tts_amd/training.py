@@ -5,6 +5,7 @@
     Loss = FastSpeech2TrainingLoss(preprocess_config, model_config)                        # train.py:43
     losses = training.train_step(model, Loss, optimizer, batch, step, grad_acc_step, grad_clip_thresh)   # train.py:80-95
     training.save_checkpoint(model, optimizer, path)                                       # train.py:150-159
+    training.fit(model, Loss, optimizer, train_set, train_config, val_set=val_set)         # train.py:59-167 over a data.DeviceDataset
 
 The six submodules carry the reference's names in the reference's order (``stacks.TxtEncoder``, ``adaptor.VarianceAdaptor``,
 ``stacks.MelEncoder``, ``stacks.MelDecoder``, ``sublayers.MelLinear``, ``postnet.PostNet``), so ``state_dict()`` is a reference
@@ -234,6 +235,16 @@ class FastSpeech2Align(torch.nn.Module):
                 tgt_alignment, d_targets)
 
 
+    def forward_teacher_forced(self, *args, async_status=False, **kwargs):
+        """What ``loss.evaluate`` calls on a model: this module's own forward under ``no_grad`` as a ``model.ForwardOutput`` with no
+        status words (a token id outside the vocabulary raises in the embedding here, and nothing is ever cut off), so ``check()``
+        has nothing to read.  Run it in ``eval()``; ``async_status`` is accepted and changes nothing."""
+        from .model import ForwardOutput
+
+        with torch.no_grad():
+            return ForwardOutput(self(*args, **kwargs))
+
+
 def get_model(args, configs, device, train=True):
     """utils/model.py:11-35 for the training case: ``(model, ScheduledOptim)``, both restored from
     ``{ckpt_path}/{restore_step}.pth.tar`` when ``args.restore_step`` is nonzero, the model in ``train()``."""
@@ -287,3 +298,44 @@ def save_checkpoint(model, optimizer, path, rng=None):
     if rng is not None:
         ckpt["keep_mask_rng"] = rng.state_dict()
     torch.save(ckpt, path)
+
+
+def fit(model, loss, optimizer, train_set, train_config, restore_step=0, val_set=None, rng=None, on_log=None):
+    """train.py:59-167 without tensorboard, tqdm and synthesis, over a ``data.DeviceDataset``: epochs of
+    ``train_set.epoch(batch_size)`` (a new ``torch.randperm`` each), one ``train_step`` per batch, steps counted from
+    ``restore_step + 1``; returns the last step, ``train_config["step"]["total_step"]``, once it has run.
+
+    Every ``log_step`` steps the seven losses are read (the loop's only host read) and handed to ``on_log(step, losses, "train")`` as
+    floats.  Every ``val_step`` steps, with a ``val_set``: ``model.eval()``, ``loss.evaluate(model, val_set.validation(batch_size),
+    loss)``, ``model.train()``, and the seven means go to ``on_log(step, means, "val")``.  Every ``save_step`` steps:
+    ``save_checkpoint(model, optimizer, "{ckpt_path}/{step}.pth.tar", rng=rng)``.  ``rng`` (a ``dropout.KeepMaskRNG``) is only saved
+    here: attach it to the model with ``dropout.attach``.  A loop over existing calls: it adds no arithmetic."""
+    from .loss import evaluate
+
+    opt, every = train_config["optimizer"], train_config["step"]
+    batch_size, grad_acc_step, grad_clip_thresh = opt["batch_size"], opt["grad_acc_step"], opt["grad_clip_thresh"]
+    total_step = every["total_step"]
+    step = int(restore_step) + 1
+    if step > total_step:
+        raise ValueError(f"fit: restore_step {restore_step} is not below total_step {total_step}")
+    if batch_size > len(train_set):
+        raise ValueError(f"fit: batch_size {batch_size} exceeds the {len(train_set)} utterances of the set: no epoch would hold a batch")
+    while True:
+        for batch in train_set.epoch(batch_size):
+            losses = train_step(model, loss, optimizer, batch, step, grad_acc_step, grad_clip_thresh)
+            if step % every["log_step"] == 0:
+                values = torch.stack([v.detach() for v in losses]).cpu().tolist()
+                if on_log is not None:
+                    on_log(step, values, "train")
+            if val_set is not None and step % every["val_step"] == 0:
+                model.eval()
+                means = evaluate(model, val_set.validation(batch_size), loss)
+                model.train()
+                if on_log is not None:
+                    on_log(step, list(means), "val")
+            if step % every["save_step"] == 0:
+                os.makedirs(train_config["path"]["ckpt_path"], exist_ok=True)
+                save_checkpoint(model, optimizer, os.path.join(train_config["path"]["ckpt_path"], "{}.pth.tar".format(step)), rng=rng)
+            if step == total_step:
+                return step
+            step += 1

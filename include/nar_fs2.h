@@ -1294,6 +1294,42 @@ int ns_fg_backward(const ns_fg_shape* shape, const ns_fg_weights* weights, const
  * One launch, two with d_b1. */
 int ns_fg_op_relu_gate(const float* da, const float* h, int M, int d_inner, float* dh, float* d_b1, void* ws, size_t ws_bytes,
                        void* stream);
+/* ---- The opt-in "bf16" matmul mode of the same layer (additions: NS_FG_ABI_VERSION is unchanged) ----------------------------------
+ * Mixed precision with fp32 master weights.  Parameters, gradients, x, h, z, y, biases, the LayerNorm, dropout, the residuals, the ReLU
+ * gate and every column sum stay fp32 / float64 exactly as above; `saved` has the same layout (ns_fg_saved_bytes).  Only the six
+ * contractions change: each rounds BOTH operands to bf16 (round to nearest even, the plain cast: a NaN survives) and accumulates in
+ * fp32 on the bf16 matrix cores:
+ *   h   = relu(conv_K1(bf x, bf w1) + b1)        u = conv_K2(bf h, bf w2) + b2
+ *   dW2 = wgrad(bf du, bf h)                     da = conv(bf du, bf w2 transposed, tap-flipped);   dh = gate(da, saved h)
+ *   dW1 = wgrad(bf dh, bf x)                     dx = conv(bf dh, bf w1 transposed, tap-flipped) + dz   (dz added in fp32)
+ * Taps never cross utterances; a weight-gradient element whose every tap lies outside its utterance is exactly +0.0.  No atomic, no
+ * host read; every sum has one order that depends on the shape alone.  The live weights are rounded into bf16 planes by a pack launch
+ * of each call.  The three module-level entry points take the arguments of their namesakes above and refuse alike; the shape must
+ * also pass the bf16 GEMM and ns_fg_plan_wgrad_bf16 (both hold for every shape the checks above admit).
+ * Launches: forward 4 (pack, h, u, row).  Backward with every output wanted 11: the list of ns_fg_backward with G = 1 (the bf16 GEMM
+ * is always one launch); the same outputs drop the same launches.  ns_fg_last_launches reports them. */
+size_t ns_fg_ws_bytes_bf16(const ns_fg_shape* shape);
+int ns_fg_forward_bf16(const ns_fg_shape* shape, const ns_fg_weights* weights, const float* x, const uint8_t* keep, float p_drop, float* y,
+                       void* saved, void* ws, size_t ws_bytes, void* stream);
+int ns_fg_backward_bf16(const ns_fg_shape* shape, const ns_fg_weights* weights, const float* x, const uint8_t* keep, float p_drop,
+                        const void* saved, const float* g, const ns_fg_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* Host only.  The split of the bf16 weight gradient: the fields of ns_pg_plan_wgrad, with rows of m per range a multiple of the
+ * 32-row stage.  Refuses what ns_pg_plan_wgrad refuses, and Cin that is not a multiple of 32. */
+int ns_fg_plan_wgrad_bf16(int M, int N, int Cin, int KW, int32_t out[8]);
+/* The new launches alone, on caller-supplied inputs (test hooks).  Every pointer 16-byte aligned; N and Cin positive multiples of 32,
+ * KW odd, B * S * max(N, Cin) < 2^31; each refuses before any HIP call.  ws: ns_fg_op_bf16_ws_bytes(B, S, N, Cin, KW) bytes (0 and
+ * ns_last_error() for a refused shape), enough for either op below.
+ * ns_fg_op_wgrad_bf16: dW [N, Cin, KW] (torch layout) = sum_m bf(dz[m, n]) bf(X[m + j - pad, c]) from dz [B*S, N] and X [B*S, Cin]; also
+ * needs a shape ns_fg_plan_wgrad_bf16 accepts (N a multiple of 128).  Two launches (GEMM, reduce).
+ * ns_fg_op_conv_bf16: W [N, Cin, KW] is the torch-layout fp32 weight; the pack launch, then the bf16 GEMM, through the code the
+ * module calls.  transposed == 0, the forward form: y [B*S, N] = act(conv(bf x [B*S, Cin], bf W) + bias) + resid.  transposed != 0, the
+ * data gradient: y [B*S, Cin] = sum_j sum_n bf(x[m - j + pad, n]) bf(W[n][c][j]) + bias + resid from x [B*S, N].  bias and resid are
+ * nullable and added in fp32; act: 0 none, 1 ReLU; y must be neither x nor resid.  Two launches. */
+size_t ns_fg_op_bf16_ws_bytes(int B, int S, int N, int Cin, int KW);
+int ns_fg_op_wgrad_bf16(const float* dz, const float* X, int B, int S, int N, int Cin, int KW, float* dW, void* ws, size_t ws_bytes,
+                        void* stream);
+int ns_fg_op_conv_bf16(const float* x, const float* W, const float* bias, const float* resid, int B, int S, int N, int Cin, int KW,
+                       int transposed, int act, float* y, void* ws, size_t ws_bytes, void* stream);
 
 /* ==== TxtEncoder / MelDecoder: what the training stacks add to their FFT blocks (transformer/Models.py:33-100, 176-244) =============
  * Handle-less, no workspace; nothing above changes (every other ABI version stays as it is).  Four single-launch ops: the two forward

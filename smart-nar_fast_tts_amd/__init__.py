@@ -49,7 +49,8 @@ def __getattr__(name):
         from . import dropout
 
         return dropout.KeepMaskRNG
-    if name in ("MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2", "MelLinear"):
+    if name in ("MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2", "MelLinear",
+                "set_ffn_matmul"):
         from . import sublayers
 
         return getattr(sublayers, name)

@@ -15,7 +15,7 @@ SOURCES = ["gemm_conv.hip", "gemm_bf16x3.hip", "gemm_bf16.hip", "attention.hip",
            "melfront_api.hip", "griffinlim.hip", "griffinlim_api.hip", "vartargets.hip", "vartargets_api.hip",
            "optim.hip", "optim_api.hip", "lossgrad.hip", "lossgrad_api.hip", "predgrad.hip", "predgrad_api.hip",
            "attngrad.hip", "attngrad_api.hip", "xattngrad.hip", "xattngrad_api.hip", "postnetgrad.hip", "postnetgrad_api.hip",
-           "adaptorgrad.hip", "adaptorgrad_api.hip", "ffngrad.hip", "ffngrad_api.hip",
+           "adaptorgrad.hip", "adaptorgrad_api.hip", "ffngrad.hip", "ffngrad_api.hip", "ffngrad_bf16.hip", "ffngrad_bf16_api.hip",
            "stackgrad.hip", "stackgrad_api.hip", "melencgrad.hip", "melencgrad_api.hip",
            "melheadgrad.hip", "melheadgrad_api.hip", "keepmask.hip", "keepmask_api.hip",
            "dataset.hip", "dataset_api.hip"]

@@ -5,9 +5,10 @@
 // and its pack kernel, the attention's LayerNorm + residual + dropout row forward and backward, the column-partial finish.  The launch
 // counts are stated in the header.
 #include "../../include/nar_fs2.h"
-#include "train_api.h"
+#include "ffngrad_api.h"
 
 using namespace ns;
+using namespace ns::fg;
 
 static_assert(sizeof(ns_fg_shape) == 24, "ns_fg_shape layout");
 static_assert(sizeof(ns_fg_weights) == 6 * sizeof(void*) && sizeof(ns_fg_grads) == 7 * sizeof(void*), "ns_fg_weights / ns_fg_grads layout");
@@ -25,8 +26,12 @@ struct Ws {  // the workspace of one shape, carved in this order
   float *a, *b;       // [M, d] each: u (forward); dz, du (backward)
   float* wide;        // [M, d_inner]: da, then dh in place (backward); h of a forward that saves nothing
 };
+}  // namespace
 
-int check_dims(const ns_fg_shape& s, const std::string& w) {
+// what the "bf16" matmul mode's entry points (ffngrad_bf16_api.hip) share with these: ffngrad_api.h
+int* ns::fg::launches() { return &t_launches; }
+
+int ns::fg::check_dims(const ns_fg_shape& s, const std::string& w) {
   if (s.B <= 0 || s.S <= 0) return api_fail(w + "B and S must be positive, got " + std::to_string(s.B) + " x " + std::to_string(s.S));
   if (s.d != 256 && s.d != 512) return api_fail(w + "d must be 256 or 512, got " + std::to_string(s.d));
   if (s.d_inner <= 0 || s.d_inner % 256 != 0) return api_fail(w + "d_inner must be a positive multiple of 256, got " + std::to_string(s.d_inner));
@@ -36,6 +41,18 @@ int check_dims(const ns_fg_shape& s, const std::string& w) {
   return 0;
 }
 
+std::vector<NamedPtr> ns::fg::params(const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_g, const float* ln_b) {
+  return {{"w1", w1}, {"b1", b1}, {"w2", w2}, {"b2", b2}, {"ln_g", ln_g}, {"ln_b", ln_b}};
+}
+
+// the gate and, where d_b1 is wanted, the fixed-order sum of its partials: one or two launches
+int ns::fg::relu_gate(const float* da, const float* h, int M, int di, float* dh, float* d_b1, double* part, hipStream_t st) {
+  NS_HIP(launch_fg_relu_gate(da, h, M, di, dh, d_b1 ? part : nullptr, st));
+  ++t_launches;
+  return counted.col_finish(part, pg_row_blocks(M), di, {d_b1}, {}, st);
+}
+
+namespace {
 int carve(const ns_fg_shape& s, void* base, Ws* ws, size_t* bytes, const std::string& w) {
   const int M = s.B * s.S, d = s.d, di = s.d_inner, nblk = pg_row_blocks(M);
   int rec[2][8];
@@ -56,10 +73,6 @@ int carve(const ns_fg_shape& s, void* base, Ws* ws, size_t* bytes, const std::st
   return 0;
 }
 
-std::vector<NamedPtr> params(const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_g, const float* ln_b) {
-  return {{"w1", w1}, {"b1", b1}, {"w2", w2}, {"b2", b2}, {"ln_g", ln_g}, {"ln_b", ln_b}};
-}
-
 // what ns_fg_forward and ns_fg_backward check alike, in this order, and the carved workspace
 int common(const std::string& w, const ns_fg_shape* s, const ns_fg_weights* k, const float* x, const uint8_t* keep, float p_drop, const void* saved,
            void* ws_mem, size_t ws_bytes, NamedPtr io, Ws* ws) {
@@ -68,13 +81,6 @@ int common(const std::string& w, const ns_fg_shape* s, const ns_fg_weights* k, c
   NS_TRY(check_drop({keep}, p_drop, w));
   NS_TRY(check_aligned(w, {{"x", x}, {"saved", saved}, {"the workspace", ws_mem}, io}));
   return carve_checked(carve, counted.abi, *s, ws_mem, ws_bytes, ws, w);
-}
-
-// the gate and, where d_b1 is wanted, the fixed-order sum of its partials: one or two launches
-int relu_gate(const float* da, const float* h, int M, int di, float* dh, float* d_b1, double* part, hipStream_t st) {
-  NS_HIP(launch_fg_relu_gate(da, h, M, di, dh, d_b1 ? part : nullptr, st));
-  ++t_launches;
-  return counted.col_finish(part, pg_row_blocks(M), di, {d_b1}, {}, st);
 }
 }  // namespace
 

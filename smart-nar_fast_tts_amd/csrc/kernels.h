@@ -487,6 +487,20 @@ hipError_t launch_va_lr_bwd(const float* g, const int32_t* cum, int B, int L, in
 // dh [M, F] = h > 0 ? da : +0.0 (a select; dh may be da), F a multiple of 256; part (nullable) [pg_row_blocks(M)][PG_SLOTS][F] doubles,
 // uninitialised: slot 0 of a block = the column sums of its rows of dh, summed by launch_pg_col_final at this F.  One launch.
 hipError_t launch_fg_relu_gate(const float* da, const float* h, int M, int F, float* dh, double* part, hipStream_t st);
+// ---- opt-in "bf16" matmul mode of the same layer (ffngrad_bf16.hip) ------------------------------------------
+// The weight gradient with both operands rounded to bf16 (nearest even) and fp32 accumulation: k_pg_wgrad's tile, split and partial
+// layout at FGB_STAGE rows of m per LDS stage; Cin a multiple of 32.  The plan has pg_plan_wgrad's fields and refusals.
+constexpr int FGB_STAGE = 32;
+bool fg_plan_wgrad_bf16(int M, int N, int Cin, int KW, PgWgradPlan* out);
+// dW [N][Cin][KW] (torch layout); partial: plan.ws_floats floats.  Two launches: the GEMM, and k_pg_wgrad_reduce (predgrad.hip).
+hipError_t launch_fg_wgrad_bf16(const float* dz, const float* X, int M, int S, int N, int Cin, int KW, const PgWgradPlan& pl, float* partial,
+                                float* dW, hipStream_t st);
+__global__ void k_pg_wgrad_reduce(const float* __restrict__ partial, int ranges, int N, int Cin, int KW, float* __restrict__ dW);
+// w [N][Cin][KW] (torch layout, fp32) -> wp [N][KW][Cin] and / or wt [Cin][KW][N] with wt[c][j][n] = w[n][c][KW-1-j], both bf16 rounded
+// to nearest even: the planes launch_conv_gemm_bf16 reads through ConvGemm::Wbf (N and Cin multiples of 32: no channel padding).
+// Either output may be null; w == nullptr skips the entry.  Two weights per launch.
+struct FgPackBf { const float* w; unsigned short* wp; unsigned short* wt; int N, Cin, KW; };
+hipError_t launch_fg_pack_bf16(const FgPackBf& a, const FgPackBf& b, hipStream_t st);
 // ---- TxtEncoder / MelDecoder training stacks (stackgrad.hip; transformer/Models.py:33-100, 176-244) ---------
 // d_table [n_vocab, D] = the sum of g [M, D]'s rows per token id, float64 in ascending m, rounded once; row 0 (PAD) and an id no row
 // carries are +0.0; a token outside [0, n_vocab) contributes nothing; g at a PAD row is not read.  D a multiple of 256.  One launch.

@@ -113,6 +113,31 @@ struct Counted {
     return 0;
   }
 
+  // the same contraction from the bf16 plane Wbf [N][KW][Cin] (k_fg_pack_bf16) with X rounded to bf16 in the kernel and fp32
+  // accumulation (gemm_bf16.hip): the "bf16" matmul mode's sibling of conv.  Bias, activation and residual stay fp32, in the
+  // kernel's own plain epilogue.  Always one launch.
+  int conv_bf16(const float* X, int ldx, const unsigned short* Wbf, const float* bias, const float* resid, float* Y, int M, int S, int N, int Cin,
+                int KW, int pad, int act, hipStream_t st) const {
+    ConvGemm p;
+    memset(&p, 0, sizeof(p));
+    p.X = X; p.ldx = ldx; p.Wbf = Wbf; p.bias = bias; p.resid = resid; p.ldr = N; p.Y = Y; p.ldy = N;
+    p.M = M; p.N = N; p.Cin = Cin; p.KW = KW; p.pad = pad; p.S = S; p.act = act; p.epi = EPI_NONE;
+    if (!conv_gemm_bf16_ok(M, N, Cin, KW, EPI_NONE)) return api_fail(std::string(abi) + ": the bf16 Conv1D-as-GEMM refuses this shape");
+    NS_HIP(launch_conv_gemm_bf16(p, st));
+    ++*launches;
+    return 0;
+  }
+
+  // k_fg_pack_bf16 over `count` weights, two per launch
+  int pack_bf16(const FgPackBf* v, int count, hipStream_t st) const {
+    const FgPackBf none{nullptr, nullptr, nullptr, 0, 0, 0};
+    for (int i = 0; i < count; i += 2) {
+      NS_HIP(launch_fg_pack_bf16(v[i], i + 1 < count ? v[i + 1] : none, st));
+      ++*launches;
+    }
+    return 0;
+  }
+
   // Y [M, N] = X [M, K] W[N][K]^T + bias + resid: the same at KW = 1
   int gemm(const float* X, const float* W, const float* bias, const float* resid, float* Y, int M, int S, int N, int K, hipStream_t st) const {
     return conv(X, K, W, bias, resid, Y, M, S, N, K, 1, 0, ACT_NONE, st);

@@ -262,15 +262,27 @@ class PositionwiseFeedForward(HipTrainModule):
     nothing.  Otherwise it is one ``torch.autograd.Function`` (single backward) that keeps ``h = relu(w_1(x))`` and ``z = dropout(w_2(h))
     + x`` ((d_hid + d_in) B S floats) and whose backward honours ``needs_input_grad``.  The ReLU backward gates on the saved ``h``.
 
-    Raises on what it cannot do: d_in not 256 or 512, d_hid not a positive multiple of 256, an even kernel size."""
+    ``matmul`` selects how the six contractions of the layer (``h``, ``u``, the two weight gradients, the two data gradients) are
+    computed: ``"fp32"`` (the default) is exact fp32 on the fp32 matrix cores; ``"bf16"`` is opt-in mixed precision with fp32 master
+    weights (``ns_fg_*_bf16``, csrc/ffngrad_bf16.hip): both operands of each contraction are rounded to bf16 (nearest even) and summed
+    in fp32 on the bf16 matrix cores, while the parameters, their gradients, ``x``, ``h``, ``z``, ``y``, the biases, the LayerNorm, the
+    dropout, the residuals, the ReLU gate and every column sum stay as in ``"fp32"``.  The parameter names, ``state_dict()`` and what is
+    saved for the backward do not depend on it; ``set_matmul(mode)`` switches a built module (``set_ffn_matmul`` a whole tree).
+
+    Raises on what it cannot do: d_in not 256 or 512, d_hid not a positive multiple of 256, an even kernel size, a ``matmul`` that is
+    neither ``"fp32"`` nor ``"bf16"``."""
 
     ABI, INPUT = "ns_fg", "the input"
     PARAM_NAMES, FIELDS = FFN_PARAM_NAMES, _lib.FG_NAMES
     WEIGHTS, GRADS = _lib.NsFgWeights, _lib.NsFgGrads
-    WORKSPACES = WorkspaceCache("ns_fg_ws_bytes", ("B", "S", "d", "d_inner", "K1", "K2"))
+    # per matmul mode: the entry points' suffix and the workspace cache (its own size query)
+    MATMUL = {"fp32": ("", WorkspaceCache("ns_fg_ws_bytes", ("B", "S", "d", "d_inner", "K1", "K2"))),
+              "bf16": ("_bf16", WorkspaceCache("ns_fg_ws_bytes_bf16", ("B", "S", "d", "d_inner", "K1", "K2")))}
+    WORKSPACES = MATMUL["fp32"][1]
 
-    def __init__(self, d_in, d_hid, kernel_size, dropout=0.1):
+    def __init__(self, d_in, d_hid, kernel_size, dropout=0.1, matmul="fp32"):
         super().__init__()
+        self.set_matmul(matmul)
         who = type(self).__name__
         k1, k2 = (int(k) for k in kernel_size)
         if d_in not in (256, 512):
@@ -286,6 +298,13 @@ class PositionwiseFeedForward(HipTrainModule):
         self.w_1 = torch.nn.Conv1d(d_in, d_hid, kernel_size=k1, padding=(k1 - 1) // 2)
         self.w_2 = torch.nn.Conv1d(d_hid, d_in, kernel_size=k2, padding=(k2 - 1) // 2)
         self.layer_norm = torch.nn.LayerNorm(d_in)
+
+    def set_matmul(self, mode):
+        """Selects ``"fp32"`` or ``"bf16"`` for the calls from now on (a forward and its backward must run in one mode)."""
+        if mode not in self.MATMUL:
+            raise ValueError(f"{type(self).__name__}: matmul must be 'fp32' or 'bf16', got {mode!r}")
+        self.matmul = mode
+        self._suffix, self.WORKSPACES = self.MATMUL[mode]
 
     def _marshal(self, x, keep_mask):
         call = self._begin(x, self.d_in)
@@ -305,8 +324,9 @@ class PositionwiseFeedForward(HipTrainModule):
         with guard(dev):
             ws, saved = self._workspace(call, save)
             y = torch.empty((s.B, s.S, s.d), dtype=torch.float32, device=dev)
-            self._done(self._lib.ns_fg_forward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.keep), call.p, _lib.ptr(y),
-                                               _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "forward")
+            entry = "ns_fg_forward" + self._suffix
+            self._done(getattr(self._lib, entry)(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.keep), call.p, _lib.ptr(y),
+                                                 _lib.ptr(saved), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "forward", entry=entry)
         return y, saved
 
     def _backward(self, call, saved, g, need):
@@ -318,9 +338,29 @@ class PositionwiseFeedForward(HipTrainModule):
         with guard(dev):
             outs, d = self._grad_block(call, need)
             ws, _ = self._workspace(call, save=False)
-            self._done(self._lib.ns_fg_backward(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.keep), call.p, _lib.ptr(saved),
-                                                _lib.ptr(g), C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward")
+            entry = "ns_fg_backward" + self._suffix
+            self._done(getattr(self._lib, entry)(C.byref(s), C.byref(call.weights), _lib.ptr(call.x), _lib.ptr(call.keep), call.p, _lib.ptr(saved),
+                                                 _lib.ptr(g), C.byref(d), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)), "backward", entry=entry)
         return outs
+
+
+def set_ffn_matmul(module, mode) -> int:
+    """Switches every ``PositionwiseFeedForward`` under ``module`` — a layer, a stack such as ``model.mel_decoder``, a whole model — to
+    ``mode`` (``"fp32"`` or ``"bf16"``) and returns how many it switched; parameters, ``state_dict()`` and checkpoints are untouched.
+
+        sublayers.set_ffn_matmul(model.mel_decoder, "bf16")      # the advised start
+
+    Start at ``mel_decoder``: nothing downstream of it takes a discrete decision, so the rounding only moves the mel by bf16-sized
+    amounts.  In the mel encoder (and the text encoder) the feed-forward output feeds the aligner and the duration path, where a
+    flipped rounding can move a duration by a frame; switching those is a training-dynamics choice, not an error."""
+    if mode not in PositionwiseFeedForward.MATMUL:
+        raise ValueError(f"set_ffn_matmul: mode must be 'fp32' or 'bf16', got {mode!r}")
+    n = 0
+    for m in module.modules():
+        if isinstance(m, PositionwiseFeedForward):
+            m.set_matmul(mode)
+            n += 1
+    return n
 
 
 class FFTBlock(torch.nn.Module):

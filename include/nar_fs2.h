@@ -1235,6 +1235,35 @@ int ns_va_op_lr_fwd(const float* x, const int64_t* duration, int B, int L, int D
 /* d_x [B, L, D] = the sum of g [B, T, D] over t in [cum[l-1], min(cum[l], T)) in t order; +0.0 for duration 0.  Frames at or past an
  * utterance's total are never read.  One launch. */
 int ns_va_op_lr_bwd(const float* g, const int32_t* cum, int B, int L, int D, int T, float* d_x, void* stream);
+/* ---- the Gaussian length regulator in the hard one's place (model/modules.py:162-192 wired as length_regulator = "gaussian") --------
+ * Additions to the family; NS_VA_ABI_VERSION stays 1.  With c_l = cumsum(d)_l - d_l / 2, d = max(duration, 0), and
+ * lim_b = min(max(mel_len_b, 0), T):
+ *   w_lt = expf(-0.01f (t - c_l)^2) / (sum_l expf(-0.01f (t - c_l)^2) + 1e-20f)
+ *   out[b, t] = sum_l w_lt x[b, l] for t < lim_b, +0.0 at and past it          d_x[b, l] = sum_{t < lim_b} w_lt g[b, t]
+ * Only x takes a gradient (the durations are integers, the range is the constant 10).  The backward generates the forward's own
+ * weights, bit for bit, and sums in t order on the fp32 matrix cores; no atomic, no host read; equal inputs give equal bits.
+ * Every launching call returns nonzero with ns_last_error(), before any HIP call, on: a null argument, a misaligned pointer (16 bytes
+ * for the float tensors and the workspace, 8 for int64), a non-positive size, B > 65535, D not a multiple of 4, B * L * D or
+ * B * T * D >= 2^31, T >= 2^20 (below it the fp32 centres are exact), a workspace smaller than ns_va_gu_ws_bytes. */
+/* Bytes of the workspace of ns_va_op_gu_fwd and ns_va_op_gu_bwd at this shape (the larger of the two; D does not enter); 0 and
+ * ns_last_error() for a refused shape. */
+size_t ns_va_gu_ws_bytes(int B, int L, int T);
+/* duration [B, L] int64 -> mel_len [B] (int64, the uncropped total of max(d, 0)) and saved [B, L] (fp32, the centres: all the backward
+ * keeps besides mel_len); out [B, T, D] from x [B, L, D] by the launch the inference side makes on the dense grid.  Three launches
+ * (prepare, centres, upsample).  out NULL: the prepare launch alone (x and T are not read; ws as for T = 1) — for a caller that must
+ * read mel_len before it can choose T. */
+int ns_va_op_gu_fwd(const float* x, const int64_t* duration, int B, int L, int D, int T, float* out, float* saved, int64_t* mel_len, void* ws,
+                    size_t ws_bytes, void* stream);
+/* d_x [B, L, D] from g [B, T, D], the saved centres and own_len [B] (int64: the forward's mel_len; NULL: every row below T is live, the
+ * reference module's plain form).  Rows of g at or past lim_b, and rows further than 102 frames from every centre of a 32-phoneme tile,
+ * are never read by that tile.  w_out (nullable) [B, L, T]: the weights the backward used, +0.0 where it used none (B * L * T < 2^31).
+ * Two launches (denominators, contraction). */
+int ns_va_op_gu_bwd(const float* g, const float* saved, const int64_t* own_len, int B, int L, int D, int T, float* d_x, float* w_out, void* ws,
+                    size_t ws_bytes, void* stream);
+/* The same with the 102-frame band switched off: every tile walks every row below lim_b.  The same bits for finite g; for
+ * tools/gaussian_grad_bench.py and the band's test only. */
+int ns_va_op_gu_bwd_unbanded(const float* g, const float* saved, const int64_t* own_len, int B, int L, int D, int T, float* d_x, float* w_out,
+                             void* ws, size_t ws_bytes, void* stream);
 
 /* ==== PositionwiseFeedForward: a training forward and its backward (transformer/SubLayers.py:62-95) ================================
  * Handle-less; nothing above changes (every other ABI version stays as it is).  With x [B, S, d], M = B * S rows, "same"-padded

@@ -4,8 +4,8 @@
 Submodules are imported lazily: ``workload`` is pure numpy and importable
 anywhere; ``model`` / ``ops`` need the HIP C-ABI library and fail loudly
 when it is missing.  ``FastSpeech2Loss``, ``FastSpeech2TrainingLoss`` and ``evaluate`` (``loss``), ``TacotronSTFT``, ``get_mel_from_wav``,
-``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``), the trainable ``VariancePredictor`` (``predictor``), ``MultiHeadAttention`` / ``MultiHeadCrossAttention`` / ``PositionwiseFeedForward`` / ``FFTBlock`` / ``Prenet`` / ``FFTBlock2`` (``sublayers``) the trainable ``PostNet`` (``postnet``) and the trainable ``VarianceAdaptor`` with its ``VarianceEmbedding`` and ``LengthRegulator`` (``adaptor``) and the trainable ``TxtEncoder`` / ``MelDecoder`` / ``MelEncoder`` stacks with their ``WordEmbedding`` and ``mask_rows`` (``stacks``), the trainable ``MelLinear`` (``sublayers``) and the ``training`` module (the trainable ``FastSpeech2Align``, ``get_model``, ``train_step``, ``save_checkpoint``, ``add_residual``) and the ``dropout`` module (``KeepMaskRNG``, ``attach``, ``detach``: dropout keep-masks from a counter-based generator in HIP) and the ``data`` module (``DeviceDataset``, ``plan_epoch``: the training set resident on the device, a batch per gather launch) resolve on first use."""
-__all__ = ["workload", "FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim", "VariancePredictor", "MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2", "PostNet", "VarianceAdaptor", "VarianceEmbedding", "LengthRegulator", "TxtEncoder", "MelDecoder", "MelEncoder", "WordEmbedding", "mask_rows", "MelLinear", "training", "dropout", "KeepMaskRNG", "data", "DeviceDataset"]
+``STFT``, ``griffin_lim``, ``mel_to_wave`` and ``inv_mel_spec`` (``audio``), ``VarianceTargets`` (``targets``), ``ScheduledOptim`` (``optim``), the trainable ``VariancePredictor`` (``predictor``), ``MultiHeadAttention`` / ``MultiHeadCrossAttention`` / ``PositionwiseFeedForward`` / ``FFTBlock`` / ``Prenet`` / ``FFTBlock2`` (``sublayers``) the trainable ``PostNet`` (``postnet``) and the trainable ``VarianceAdaptor`` with its ``VarianceEmbedding``, ``LengthRegulator`` and ``GaussianUpsampling`` (``adaptor``) and the trainable ``TxtEncoder`` / ``MelDecoder`` / ``MelEncoder`` stacks with their ``WordEmbedding`` and ``mask_rows`` (``stacks``), the trainable ``MelLinear`` (``sublayers``) and the ``training`` module (the trainable ``FastSpeech2Align``, ``get_model``, ``train_step``, ``save_checkpoint``, ``add_residual``) and the ``dropout`` module (``KeepMaskRNG``, ``attach``, ``detach``: dropout keep-masks from a counter-based generator in HIP) and the ``data`` module (``DeviceDataset``, ``plan_epoch``: the training set resident on the device, a batch per gather launch) resolve on first use."""
+__all__ = ["workload", "FastSpeech2Loss", "FastSpeech2TrainingLoss", "evaluate", "TacotronSTFT", "get_mel_from_wav", "STFT", "griffin_lim", "mel_to_wave", "inv_mel_spec", "VarianceTargets", "ScheduledOptim", "VariancePredictor", "MultiHeadAttention", "MultiHeadCrossAttention", "PositionwiseFeedForward", "FFTBlock", "Prenet", "FFTBlock2", "PostNet", "VarianceAdaptor", "VarianceEmbedding", "LengthRegulator", "GaussianUpsampling", "TxtEncoder", "MelDecoder", "MelEncoder", "WordEmbedding", "mask_rows", "MelLinear", "training", "dropout", "KeepMaskRNG", "data", "DeviceDataset"]
 
 
 def __getattr__(name):
@@ -58,7 +58,7 @@ def __getattr__(name):
         from . import postnet
 
         return postnet.PostNet
-    if name in ("VarianceAdaptor", "VarianceEmbedding", "LengthRegulator"):
+    if name in ("VarianceAdaptor", "VarianceEmbedding", "LengthRegulator", "GaussianUpsampling"):
         from . import adaptor
 
         return getattr(adaptor, name)

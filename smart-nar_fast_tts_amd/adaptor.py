@@ -181,6 +181,99 @@ class LengthRegulator(CountedModule):
         return dx
 
 
+class _GaussianFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, owner, x, duration, T):
+        out, mel_len, centres = owner._forward(x, duration, T)
+        ctx.owner, ctx.centres, ctx.mel_len, ctx.dims = owner, centres, mel_len, tuple(x.shape)  # the fp32 centres and the totals are all the backward keeps
+        ctx.mark_non_differentiable(mel_len)
+        return out, mel_len
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        dx = ctx.owner._backward(g, ctx.centres, ctx.mel_len, ctx.dims) if ctx.needs_input_grad[1] else None
+        return None, dx, None, None
+
+
+class GaussianUpsampling(CountedModule):
+    """The reference's ``GaussianUpsampling`` (model/modules.py:162-192) in the ``LengthRegulator``'s place and with its signature:
+    ``forward(x [B, L, d], duration [B, L], max_len=None) -> (out [B, max_len, d], mel_len [B] int64)``.  With
+    ``c_l = cumsum(d)_l - d_l / 2`` (``d = max(duration, 0)``) frame ``t`` of an utterance is ``sum_l w_lt x_l``,
+    ``w_lt = exp(-0.01 (t - c_l)^2) / (sum_l exp(-0.01 (t - c_l)^2) + 1e-20)``; frames at or past the utterance's total are ``+0.0``, frames at
+    or past ``max_len`` are dropped, and ``mel_len`` stays the uncropped total — what ``model.FastSpeech2Align`` computes with
+    ``model_config["length_regulator"] = "gaussian"`` (the same launch, so the same bits).  Three launches (prepare, centres, upsample).
+    ``max_len=None`` pads to the batch maximum, which costs ONE device-to-host read of ``mel_len`` and one more prepare launch; pass
+    ``max_len`` to stay asynchronous.
+
+    The backward is two launches: the denominators, then ``d_x[b, l] = sum_t w_lt grad_output[b, t]`` over the live frames in ``t`` order
+    on the fp32 matrix cores, with the forward's own weights bit for bit; a frame further than 102 frames from every centre of a
+    32-phoneme tile has weight exactly ``+0.0`` for it and is not read.  A padded phoneme (duration 0) sits at the utterance's total and
+    takes the gradient the transpose gives it, as it feeds the forward.  ``duration`` is an integer tensor (a floating one is
+    truncated) and takes no gradient; the range is the reference's constant 10.  No parameters."""
+
+    ABI = "ns_va"
+
+    def forward(self, x, duration, max_len=None):
+        need_gpu("GaussianUpsampling", "x", x)
+        if x.dtype != torch.float32 or x.dim() != 3 or x.numel() == 0 or x.shape[2] % 4 != 0:
+            raise ValueError(f"x must be a non-empty float32 [B, L, d] tensor with d a multiple of 4, got {x.dtype} {tuple(x.shape)}")
+        if tuple(duration.shape) != tuple(x.shape[:2]) or duration.device != x.device or duration.dtype == torch.bool:
+            raise ValueError(f"duration must be a [B, L] = {tuple(x.shape[:2])} tensor on {x.device}, got {tuple(duration.shape)} on {duration.device}")
+        if max_len is not None and int(max_len) <= 0:
+            raise ValueError(f"max_len must be positive or None, got {max_len}")
+        T = None if max_len is None else int(max_len)
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _GaussianFunction.apply(self, x, duration, T)
+        return self._forward(x, duration, T)[:2]
+
+    def _workspace(self, B, L, T, dev):
+        n = self._lib.ns_va_gu_ws_bytes(B, L, T)
+        if n == 0:
+            _lib.check(1, "ns_va_gu_ws_bytes")
+        return torch.empty(n, dtype=torch.uint8, device=dev)
+
+    def _forward(self, x, duration, T):
+        dev = x.device
+        B, L, D = x.shape
+        xa, da = aligned(x.detach()), duration.detach().to(torch.int64).contiguous()
+        with guard(dev):
+            centres = torch.empty((B, L), dtype=torch.float32, device=dev)
+            mel_len = torch.empty((B,), dtype=torch.int64, device=dev)
+            st = _lib.stream_ptr(dev)
+            add = False
+            if T is None:  # the prepare launch alone, then the one read of the batch maximum
+                ws = self._workspace(B, L, 1, dev)
+                self._done(self._lib.ns_va_op_gu_fwd(None, _lib.ptr(da), B, L, D, 0, None, _lib.ptr(centres), _lib.ptr(mel_len), _lib.ptr(ws), ws.numel(),
+                                                     st), "forward", "ns_va_op_gu_fwd")
+                T = int(mel_len.max().item())
+                if T <= 0:
+                    raise ValueError("GaussianUpsampling: every duration is zero and max_len is None: there is no frame to pad to")
+                add = True
+            ws = self._workspace(B, L, T, dev)
+            out = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+            self._done(self._lib.ns_va_op_gu_fwd(_lib.ptr(xa), _lib.ptr(da), B, L, D, T, _lib.ptr(out), _lib.ptr(centres), _lib.ptr(mel_len), _lib.ptr(ws),
+                                                 ws.numel(), st), "forward", "ns_va_op_gu_fwd", add=add)
+        return out, mel_len, centres
+
+    def _backward(self, g, centres, mel_len, dims, w_out=None):
+        dev = centres.device
+        B, L, D = dims
+        if g.dim() != 3 or g.shape[0] != B or g.shape[2] != D or g.dtype != torch.float32 or g.device != dev:
+            raise ValueError(f"grad_output must be a float32 [{B}, T, {D}] tensor on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+        g = aligned(g)
+        T = g.shape[1]
+        with guard(dev):
+            ws = self._workspace(B, L, T, dev)
+            dx = torch.empty((B, L, D), dtype=torch.float32, device=dev)
+            self._done(self._lib.ns_va_op_gu_bwd(_lib.ptr(g), _lib.ptr(centres), _lib.ptr(mel_len), B, L, D, T, _lib.ptr(dx), _lib.ptr(w_out), _lib.ptr(ws),
+                                                 ws.numel(), _lib.stream_ptr(dev)), "backward", "ns_va_op_gu_bwd")
+        return dx
+
+
+REGULATORS = {"hard": LengthRegulator, "gaussian": GaussianUpsampling}
+
+
 class VarianceAdaptor(torch.nn.Module):
     """Drop-in for ``VarianceAdaptor(preprocess_config, model_config)`` on its teacher-forced branch: the reference's state-dict keys
     (``pitch_bins``, ``energy_bins`` — Parameters with ``requires_grad=False`` — ``pitch_embedding.weight``, ``energy_embedding.weight``,
@@ -189,7 +282,9 @@ class VarianceAdaptor(torch.nn.Module):
     log_duration_prediction, duration_rounded, mel_len, mel_mask)``, where ``duration_rounded`` is ``duration_target`` itself and ``mel_mask``
     is passed through.  All four mixes of ``phoneme_level`` / ``frame_level`` for pitch and energy: a phoneme-level feature is predicted and
     embedded before the length regulator (mask ``src_mask``), a frame-level one after it (mask ``mel_mask``); energy reads ``x`` with the
-    pitch embedding already added.
+    pitch embedding already added.  ``model_config["length_regulator"]`` (an extension key, absent = ``"hard"``) chooses what sits in
+    ``self.length_regulator``: ``"hard"`` the ``LengthRegulator``, ``"gaussian"`` the ``GaussianUpsampling`` — neither has parameters, so
+    the state-dict keys do not depend on it; any other value raises ``ValueError``.
 
     The bin edges come from ``<preprocessed_path>/stats.json`` through ``workload.variance_bins``, or from ``workload.SYNTH_STATS`` where
     that file is absent; a loaded checkpoint replaces them.  ``pitch_target``, ``energy_target`` and ``duration_target`` must all be
@@ -203,7 +298,10 @@ class VarianceAdaptor(torch.nn.Module):
 
     def __init__(self, preprocess_config, model_config):
         super().__init__()
-        self.length_regulator = LengthRegulator()
+        kind = model_config.get("length_regulator", "hard")  # the inference side's extension key (model.FastSpeech2Align)
+        if kind not in REGULATORS:
+            raise ValueError(f"model_config['length_regulator'] must be one of {tuple(REGULATORS)}, got {kind!r}")
+        self.length_regulator = REGULATORS[kind]()
         self.duration_predictor = VariancePredictor(model_config)
         self.pitch_predictor = VariancePredictor(model_config)
         self.energy_predictor = VariancePredictor(model_config)

@@ -18,7 +18,7 @@ SOURCES = ["gemm_conv.hip", "gemm_bf16x3.hip", "gemm_bf16.hip", "attention.hip",
            "adaptorgrad.hip", "adaptorgrad_api.hip", "ffngrad.hip", "ffngrad_api.hip", "ffngrad_bf16.hip", "ffngrad_bf16_api.hip",
            "stackgrad.hip", "stackgrad_api.hip", "melencgrad.hip", "melencgrad_api.hip",
            "melheadgrad.hip", "melheadgrad_api.hip", "keepmask.hip", "keepmask_api.hip",
-           "dataset.hip", "dataset_api.hip"]
+           "dataset.hip", "dataset_api.hip", "gaussgrad.hip", "gaussgrad_api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 # attention keeps its O^T / S^T accumulators in architectural VGPRs (gfx950 has one unified 512-entry file): the
 # online softmax touches them with VALU ops, and in AGPR form hipcc shuttles all 64+16 registers through

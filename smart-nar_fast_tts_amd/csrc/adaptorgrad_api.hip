@@ -35,6 +35,8 @@ int check_lr(const std::string& w, int B, int L, int D, int T, bool need_T) {
 }
 }  // namespace
 
+int& ns::va_launch_counter() { return t_launches; }  // gaussgrad_api.hip books its launches here
+
 extern "C" int ns_va_abi_version(void) { return NS_VA_ABI_VERSION; }
 extern "C" int ns_va_last_launches(void) { return t_launches; }
 

@@ -483,6 +483,19 @@ hipError_t launch_va_duration_scan(const long long* duration, int B, int L, int3
 // d_x[b, l, :] = the sum of g[b, t, :] over t in [cum[l-1], min(cum[l], T)) in t order, float64, rounded once; +0.0 for an empty range.
 // One wave per phoneme, 16-byte lanes.
 hipError_t launch_va_lr_bwd(const float* g, const int32_t* cum, int B, int L, int D, int T, float* d_x, hipStream_t st);
+// the calling thread's ns_va_* launch counter (adaptorgrad_api.hip), for the family's entry points in other files
+int& va_launch_counter();
+// ---- Gaussian length regulator, training side (gaussgrad.hip; model/modules.py:162-192) ----------------------
+// dur_f [B, L] = (float)max(duration, 0) for launch_gaussian_upsampling, mel_len [B] = the integer total, centres [B, L] = the serial
+// fp32 scan k_gauss_centers makes from dur_f (the same bits)
+hipError_t launch_gu_prepare(const long long* duration, int B, int L, float* dur_f, float* centres, long long* mel_len, hipStream_t st);
+// S [B, T] = sum_l expf(-0.01f (t - c_l)^2) + 1e-20f in k_gauss_upsample's order, written for t < lim_b = min(max(own_len[b], 0), T)
+// (own_len nullable: T)
+hipError_t launch_gu_denominators(const float* centres, const long long* own_len, int B, int L, int T, float* S, hipStream_t st);
+// d_x [B, L, D] = sum_{t < lim_b} (expf(-0.01f (t - c_l)^2) / S_t) g[b, t] in t order on the fp32 matrix cores; band: walk only the
+// frames within 102 of the tile's centres (an identity); w_out (nullable) [B, L, T]: the weights used, +0.0 where none was
+hipError_t launch_gu_bwd(const float* g, const float* centres, const float* S, const long long* own_len, int B, int L, int D, int T, bool band,
+                         float* d_x, float* w_out, hipStream_t st);
 // ---- PositionwiseFeedForward training backward (ffngrad.hip; transformer/SubLayers.py:62-95) ----------------
 // dh [M, F] = h > 0 ? da : +0.0 (a select; dh may be da), F a multiple of 256; part (nullable) [pg_row_blocks(M)][PG_SLOTS][F] doubles,
 // uninitialised: slot 0 of a block = the column sums of its rows of dh, summed by launch_pg_col_final at this F.  One launch.

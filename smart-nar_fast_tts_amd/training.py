@@ -91,6 +91,10 @@ class FastSpeech2Align(torch.nn.Module):
     ``lens=``, so with ``max_src_len`` and ``max_mel_len`` given the call makes no device-to-host read.  ``d_targets`` are
     ``mel_encoder.durations()`` of the last alignment map under ``no_grad`` (the reference's ``_calculate_duration`` is undefined).
 
+    ``model_config["length_regulator"] = "gaussian"`` (the inference class's extension key) is read by the ``VarianceAdaptor``: the decoder
+    is then trained on the Gaussian regulator's blended frames (``adaptor.GaussianUpsampling``, forward the inference side's launch,
+    backward in HIP); the checkpoint has the same keys and loads strictly into ``model.FastSpeech2Align`` built with the same key.
+
     ``keep_masks`` (an extension) is a dict of dropout keep-masks handed down unchanged: ``txt_encoder`` / ``mel_encoder`` /
     ``mel_decoder`` (pairs per layer), ``prenet`` (one mask), ``variance_adaptor`` (its dict), ``postnet`` (its list).
 
